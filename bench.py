@@ -8,7 +8,7 @@ One step = one pass of the hot path over `--batches-per-step` batches of synthet
 Workload = BASELINE.json configs[1] (n = 4096 G1 MSM over the trusted-setup points, random Fr scalars), batched;
 N > 1 shards whole blobs across ranks (weak scaling, table replicated, no data-path collective).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
 `--gpus N` with N > 1 and no WORLD_SIZE in the environment launches the N ranks itself
 (python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ...); under an external
 launcher the world size must equal --gpus.  Rank 0 prints ONE JSON line.
@@ -99,6 +99,25 @@ def make_blobs(torch, nblobs, seed, device):
     b = torch.randint(0, 256, (nblobs, N, 32), dtype=torch.uint8, generator=g, device=device)
     b[:, :, 0] = 0
     return b.reshape(nblobs, BLOB)
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(d, commitments, status, suffix=""):
+    """--dump-outputs: what the timed path handed back in its last step, as float32 .npy files under d — `commitments`
+    (one row of 48 compressed-commitment bytes per blob, in step order), `status` (the per-blob return code, 0 = ok) and
+    `blob_index` (which blobs of the step the rows are).  Above DUMP_LIMIT_BYTES in all, a fixed seeded sample of blobs."""
+    import numpy as np
+
+    idx = np.arange(len(status))
+    row_bytes = 4 * (commitments.shape[1] + 2)
+    room = DUMP_LIMIT_BYTES - 3 * 4096  # .npy headers
+    if len(idx) * row_bytes > room:
+        idx = np.sort(np.random.default_rng(0).choice(len(idx), room // row_bytes, replace=False))
+    os.makedirs(d, exist_ok=True)
+    for name, a in (("commitments", commitments[idx]), ("status", status[idx]), ("blob_index", idx)):
+        np.save(os.path.join(d, name + suffix + ".npy"), a.astype(np.float32))
 
 
 def host_cores():
@@ -275,7 +294,12 @@ def main():
     ap.add_argument("--no-large", action="store_true", help="alias of --no-extras")
     ap.add_argument("--no-counters", action="store_true", help="skip the rocprofv3 counter passes over the headline kernel")
     ap.add_argument("--no-multi", action="store_true", help="skip the in-process multi-GPU leg (kzgamd_*_batch_multi)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the commitments and per-blob status of the last step to DIR/*.npy "
+                         "(float32; one set per rank, suffixed _rank<r>, when there are several)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.no_large:
         args.no_extras = True
 
@@ -359,6 +383,9 @@ def main():
     sync_all()
     wall = time.perf_counter() - t0
     prof = kzg.msm_get_profile(handle)  # over the timed region (with several streams: launches share the GPU)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, torch.cat(outs).reshape(-1, 48).cpu().numpy(), torch.cat(stats).cpu().numpy(),
+                     "" if world == 1 else "_rank%d" % rank)
     # the same kernel on launches that run alone (one stream, back to back), after the timed region: its own duration,
     # which is what rocprofv3 --streams 1 measures and what the VALU utilisation is quoted on
     kzg.msm_set_profile(handle, True)

@@ -2,7 +2,7 @@
 # The reference's own generic test-suite and criterion benches, instantiated for the MI355X backend
 # (rust-kzg_amd/rust-backend/{tests,benches}: the counterpart of blst/tests and blst/benches), on a box that has a
 # Rust toolchain, a checkout of the reference and an MI355X.  The build image has no cargo: there the same vectors
-# run through tests/ (ctypes) and tests/c_abi_harness.c (C) instead.  SURVEY.md §4, /root/reference/run-c-kzg-4844-tests.sh.
+# run through tests/ (ctypes) and tests/c_abi_harness.c (C) instead.  SURVEY.md §4, the reference's run-c-kzg-4844-tests.sh.
 #
 #   bench/run_reference_suite.sh /path/to/rust-kzg [test|bench|all]
 #

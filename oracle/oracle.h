@@ -8,7 +8,7 @@
  *
  * The field / curve arithmetic itself lives in the third-party `blst` crate
  * (pinned 0.3.16, reference Cargo.lock:530-533) whose sources are NOT under
- * /root/reference, so it is restated here from the published algorithms
+ * the reference checkout, so it is restated here from the published algorithms
  * (Montgomery CIOS; EFD add-2008-s / madd-2008-s XYZZ formulas; ZCash
  * compressed-point format) using the in-tree statements of the same constants
  * (zkcrypto/bls12_381/src/fp.rs:70-104, scalar.rs:75-173) and anchored on the

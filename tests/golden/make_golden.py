@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Generate tests/golden/* from the reference's own test data (run in the build container only).
+"""Generate tests/golden/* from the reference's own test data: python tests/golden/make_golden.py /path/to/rust-kzg
 
 Reads ONLY data files / constant tables the reference's tests hold:
   kzg-bench/src/trusted_setup.txt                     -> trusted_setup.txt (verbatim data file)
@@ -19,7 +19,7 @@ import sys
 
 import yaml
 
-REF = "/root/reference"
+REF = sys.argv[1] if len(sys.argv) > 1 else "rust-kzg"  # a checkout of grandinetech/rust-kzg
 OUT = os.path.dirname(os.path.abspath(__file__))
 TV = os.path.join(REF, "kzg-bench/src/test_vectors")
 

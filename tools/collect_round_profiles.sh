@@ -3,7 +3,7 @@
 #   2. PMC passes over the headline kernel (--streams 1, so that a launch runs alone): HBM traffic, VALU counters, clock
 #   3. kernel trace + stats and PMC passes of the NTT kernels (tools/ntt_bench.py)
 #   4. kernel trace of one 2^20 MSM (tools/prof_2p20.py)
-R=$GRAFT_REPO_ROOT
+R=$(cd $(dirname $0)/.. && pwd)
 TAG=${TAG:-r05}
 mkdir -p $R/gpurun_out
 timeout 1500 python $R/bench.py > $R/gpurun_out/bench_final.json 2> $R/gpurun_out/bench_final.err; tail -2 $R/gpurun_out/bench_final.err

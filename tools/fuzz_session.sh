@@ -1,4 +1,4 @@
-R=${GRAFT_REPO_ROOT:-$(cd $(dirname $0)/.. && pwd)}
+R=$(cd $(dirname $0)/.. && pwd)
 SEED=${SEED:-41}
 mkdir -p $R/gpurun_out
 LOG=$R/gpurun_out/long_fuzz_$SEED.log

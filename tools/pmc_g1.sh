@@ -1,6 +1,6 @@
 # counters of the G1 stage kernels at low and high occupancy (same kernel form): bash tools/pmc_g1.sh [variant]
+R=$(cd $(dirname $0)/.. && pwd)
 cd /tmp && export TMPDIR=/tmp
-R=$GRAFT_REPO_ROOT
 V=${1:-0,0,65536}
 for pass in "SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_WAVE_CYCLES SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_WAVES SQ_INST_CYCLES_VMEM" "GRBM_GUI_ACTIVE" "SQ_IFETCH SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_WAIT_INST_LDS" "FETCH_SIZE" "WRITE_SIZE"; do
   tag=$(echo $pass | cut -d' ' -f1)

@@ -1,5 +1,5 @@
 # rocprofv3 counter passes over the headline kernel, GLV wide table vs the 255-bit table (same box)
-R=$GRAFT_REPO_ROOT
+R=$(cd $(dirname $0)/.. && pwd)
 cd /tmp && export TMPDIR=/tmp
 for g in 1 0; do
   rm -rf $R/gpurun_out/fbw_pmc_g$g $R/gpurun_out/fbw_pmc2_g$g

@@ -1,6 +1,6 @@
 # per-dispatch durations of the G1 transform stages of ONE fft_g1 of 2^15 points per stage form (run on the GPU box)
+R=$(cd $(dirname $0)/.. && pwd)
 cd /tmp && export TMPDIR=/tmp
-R=$GRAFT_REPO_ROOT
 MODE=${1:---only-fft}
 for v in ${VARIANTS:-0,0,0 0,0,65536 0,65536,65536}; do
   rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_$v -o x -- python $R/tools/time_g1.py $MODE $v > /tmp/log_$v.txt 2>&1

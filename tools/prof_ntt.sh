@@ -1,5 +1,5 @@
 # rocprofv3 passes over tools/ntt_bench.py: kernel stats, then SQ counters (own passes, no extra trace domains)
-R=$GRAFT_REPO_ROOT
+R=$(cd $(dirname $0)/.. && pwd)
 TAG=${1:-ntt}
 cd /tmp && export TMPDIR=/tmp
 rm -rf $R/gpurun_out/prof_$TAG*

@@ -1,5 +1,5 @@
 # PMC passes over one NTT shape: tools/prof_ntt_one.sh <tag> <scale> <n>x<batch>
-R=$GRAFT_REPO_ROOT
+R=$(cd $(dirname $0)/.. && pwd)
 TAG=$1; SCALE=$2; SHAPE=$3
 cd /tmp && export TMPDIR=/tmp
 rm -rf $R/gpurun_out/pmc_$TAG*

@@ -1,5 +1,5 @@
 import sys, os, time, ctypes as C
-sys.path.insert(0, "/root/repo/tools")
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import extra_bench as eb
 kzg = eb.load_pkg()
 blob = bytes(131072)

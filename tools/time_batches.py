@@ -1,5 +1,5 @@
 import os, sys, time, ctypes as C
-ROOT = os.environ.get("GRAFT_REPO_ROOT", "/root/repo")
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import torch
 from conftest import load_package
