@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""bench.py — blob_to_kzg_commitment throughput on MI355X (BASELINE.json metric), plus one driver-timed figure
-with its own roofline object for every other BASELINE.json config.
+"""bench.py — blob_to_kzg_commitment throughput on MI355X (BASELINE.json metric); with --full, also one driver-timed
+figure with its own roofline object for every other BASELINE.json config.
 
 One step = one pass of the hot path over `--batches-per-step` batches of synthetic blobs per GPU:
   B blobs (4096 x 32-byte field elements each, already resident in HBM)
@@ -8,10 +8,16 @@ One step = one pass of the hot path over `--batches-per-step` batches of synthet
 Workload = BASELINE.json configs[1] (n = 4096 G1 MSM over the trusted-setup points, random Fr scalars), batched;
 N > 1 shards whole blobs across ranks (weak scaling, table replicated, no data-path collective).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 `--gpus N` with N > 1 and no WORLD_SIZE in the environment launches the N ranks itself
 (python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ...); under an external
 launcher the world size must equal --gpus.  Rank 0 prints ONE JSON line.
+
+A plain run does what the headline figure needs and nothing else: set up, warm up, time the steps, dump the outputs
+if asked, print the line.  `--full` adds everything else, after the timed region: the headline kernel's roofline and
+VALU figures (with launches of their own and rocprofv3 counter passes), the other configurations (proofs, NTT, MSM
+sweep, host-buffer calls, cells, concurrent callers, in-process multi-GPU, table budgets), the CPU baseline that also
+checks the GPU's commitments against the oracle, and the multi-rank all-gather; the --no-* options leave parts of it out.
 """
 import argparse
 import csv
@@ -231,7 +237,7 @@ def collect_counters(batch, timeout_s=90):
         return None, "rocprofv3 not found: counter fields come from the committed profile if its kernels are these"
     passes = ["FETCH_SIZE", "WRITE_SIZE", "SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_WAVES", "GRBM_GUI_ACTIVE"]
     child = [sys.executable, os.path.abspath(__file__), "--steps", "2", "--warmup", "1", "--batches-per-step", "2",
-             "--batch", str(batch), "--streams", "1", "--no-cpu-baseline", "--no-extras", "--no-counters"]
+             "--batch", str(batch), "--streams", "1"]  # a plain run: the headline steps only
     out = {}
     tmp = tempfile.mkdtemp(prefix="kzg_pmc_", dir="/tmp")
     # the child is a plain one-GPU run, whatever launched this process (a torchrun rank passes its rendezvous on)
@@ -289,11 +295,14 @@ def main():
     ap.add_argument("--batches-per-step", type=int, default=8, help="batches per GPU per step, each with its own blobs")
     ap.add_argument("--streams", type=int, default=4,
                     help="1: batches back to back on one stream; 2-4: consecutive batches rotate over that many streams")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="headline only: skip the NTT / MSM sweep / proof / host-buffer legs")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline steps, also measure and check everything else: roofline and counters, CPU "
+                         "baseline, the other configurations, the in-process multi-GPU leg (the --no-* options drop parts)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the NTT / MSM sweep / proof / host-buffer legs")
     ap.add_argument("--no-large", action="store_true", help="alias of --no-extras")
-    ap.add_argument("--no-counters", action="store_true", help="skip the rocprofv3 counter passes over the headline kernel")
-    ap.add_argument("--no-multi", action="store_true", help="skip the in-process multi-GPU leg (kzgamd_*_batch_multi)")
+    ap.add_argument("--no-counters", action="store_true", help="with --full: skip the rocprofv3 counter passes over the headline kernel")
+    ap.add_argument("--no-multi", action="store_true", help="with --full: skip the in-process multi-GPU leg (kzgamd_*_batch_multi)")
     ap.add_argument("--dump-outputs", metavar="DIR",
                     help="after the timed steps, write the commitments and per-blob status of the last step to DIR/*.npy "
                          "(float32; one set per rank, suffixed _rank<r>, when there are several)")
@@ -302,6 +311,8 @@ def main():
         ap.error("--steps must be at least 1")
     if args.no_large:
         args.no_extras = True
+    if not args.full:  # a plain run: the headline figure only
+        args.no_extras = args.no_cpu_baseline = args.no_counters = args.no_multi = True
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # self-launch: one rank per GPU over RCCL
@@ -386,14 +397,15 @@ def main():
     if args.dump_outputs:
         dump_outputs(args.dump_outputs, torch.cat(outs).reshape(-1, 48).cpu().numpy(), torch.cat(stats).cpu().numpy(),
                      "" if world == 1 else "_rank%d" % rank)
-    # the same kernel on launches that run alone (one stream, back to back), after the timed region: its own duration,
-    # which is what rocprofv3 --streams 1 measures and what the VALU utilisation is quoted on
-    kzg.msm_set_profile(handle, True)
-    for k in range(min(NB, 4)):
-        kzg.blob_to_kzg_commitment_device(outs[k].data_ptr(), stats[k].data_ptr(), scratch[0].data_ptr(), batch_ptr[k], B,
-                                          settings, streams[0].cuda_stream)
-    torch.cuda.synchronize()
-    prof_alone = kzg.msm_get_profile(handle)
+    if args.full:
+        # the same kernel on launches that run alone (one stream, back to back), after the timed region: its own duration,
+        # which is what rocprofv3 --streams 1 measures and what the VALU utilisation is quoted on
+        kzg.msm_set_profile(handle, True)
+        for k in range(min(NB, 4)):
+            kzg.blob_to_kzg_commitment_device(outs[k].data_ptr(), stats[k].data_ptr(), scratch[0].data_ptr(), batch_ptr[k], B,
+                                              settings, streams[0].cuda_stream)
+        torch.cuda.synchronize()
+        prof_alone = kzg.msm_get_profile(handle)
     kzg.msm_set_profile(handle, False)
     assert all(int(st.sum().item()) == 0 for st in stats)
     tmax = torch.tensor([wall], dtype=torch.float64, device=dev)
@@ -408,7 +420,7 @@ def main():
         devices = gathered
 
     gather_ms = None
-    if dist is not None:
+    if dist is not None and args.full:
         # the one collective a sharded batch needs: all ranks' 48-byte results of one batch, gathered as
         # device tensors (ncclAllGather over RCCL); outside the timed region, timed on its own
         import importlib.util as _u
@@ -460,7 +472,7 @@ def main():
     pm, pm_src, pm_valid = pmc_summary()
     kern = "k_fbw_accum" if info.get("wide_table") else "k_accum"
     own_ms = None
-    if prof is not None:
+    if prof is not None and args.full:
         accum_ms, total_ms, cnt = prof
         alg_bytes = ALG_BYTES_PER_COMMIT * B
         own_ms = prof_alone[0] if (prof_alone and NS > 1) else accum_ms

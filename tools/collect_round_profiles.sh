@@ -6,7 +6,7 @@
 R=$(cd $(dirname $0)/.. && pwd)
 TAG=${TAG:-r05}
 mkdir -p $R/gpurun_out
-timeout 1500 python $R/bench.py > $R/gpurun_out/bench_final.json 2> $R/gpurun_out/bench_final.err; tail -2 $R/gpurun_out/bench_final.err
+timeout 1500 python $R/bench.py --full > $R/profiles/${TAG}_bench.json  # the round's full bench line
 cd /tmp && export TMPDIR=/tmp
 rm -rf $R/gpurun_out/prof_* $R/gpurun_out/pmc_*
 B="python $R/bench.py --steps 3 --warmup 1 --batches-per-step 4 --no-cpu-baseline --no-extras --no-counters"

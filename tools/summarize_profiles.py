@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Turn the raw rocprofv3 output tools/collect_round_profiles.sh left under gpurun_out/ into the committed
-summaries under profiles/ (round tag TAG, default r04): bench line, kernel statistics (headline 4-stream run, 1-stream run, NTT,
+summaries under profiles/ (round tag TAG, default r04): kernel statistics (headline 4-stream run, 1-stream run, NTT,
 2^20 MSM timeline), the PMC counter files and r02_pmc_summary.json (what bench.py reads for roofline.traffic and
 the VALU figures, labelled with this file as their source)."""
 import collections
@@ -78,8 +78,7 @@ def compact_counter_files(limit=200 * 1024):
 
 
 def main():
-    bench = json.load(open(os.path.join(G, "bench_final.json")))
-    shutil.copy(os.path.join(G, "bench_final.json"), os.path.join(P, TAG + "_bench.json"))
+    bench = json.load(open(os.path.join(P, TAG + "_bench.json")))  # written there by collect_round_profiles.sh
     B = bench["config"]["blobs_per_batch"]
     cfg = bench["config"]
     for name in ("headline", "streams1", "ntt", "2p20", "cells", "proofs", "conc", "verify", "fftg1"):
