@@ -322,6 +322,14 @@ C_KZG_RET kzgamd_compute_cells_and_kzg_proofs_batch(Cell *cells, KZGProof *proof
  * cells) is C_KZG_BADARGS, as there. */
 C_KZG_RET recover_cells_and_kzg_proofs(Cell *recovered_cells, KZGProof *recovered_proofs, const uint64_t *cell_indices,
                                        const Cell *cells, uint64_t num_cells, const CKZGSettings *s);
+/* n independent recoveries in one call, the result of n calls of recover_cells_and_kzg_proofs (das.rs:209-241).
+ * Blob b gives num_cells[b] cells. Its indices and cells are the next num_cells[b] entries of cell_indices / cells
+ * (concatenated in blob order). recovered_cells: n x 128 cells; recovered_proofs: n x 128 proofs, or NULL.
+ * Each blob is validated as in the single call. On any failure: the code of the first failing blob, and the outputs
+ * are unspecified. n = 0: C_KZG_OK. */
+C_KZG_RET kzgamd_recover_cells_and_kzg_proofs_batch(Cell *recovered_cells, KZGProof *recovered_proofs,
+                                                    const uint64_t *cell_indices, const Cell *cells,
+                                                    const uint64_t *num_cells, size_t n, const CKZGSettings *s);
 C_KZG_RET verify_cell_kzg_proof_batch(bool *ok, const Bytes48 *commitments_bytes, const uint64_t *cell_indices,
                                       const Cell *cells, const Bytes48 *proofs_bytes, uint64_t num_cells,
                                       const CKZGSettings *s);

@@ -69,6 +69,7 @@ EXPORTS = [
     "compute_kzg_proof", "compute_blob_kzg_proof", "kzgamd_compute_blob_kzg_proof_batch", "compute_challenge",
     "bytes_to_kzg_commitment", "bytes_from_bls_field", "compute_cells_and_kzg_proofs",
     "recover_cells_and_kzg_proofs", "verify_cell_kzg_proof_batch", "compute_verify_cell_kzg_proof_batch_challenge",
+    "kzgamd_recover_cells_and_kzg_proofs_batch",
     "kzgamd_compute_cells_and_kzg_proofs_batch", "kzgamd_compute_challenges_and_evaluate_batch",
     "kzgamd_blob_to_kzg_commitment_batch", "kzgamd_blob_to_kzg_commitment_device", "kzgamd_settings_msm_handle",
     "kzgamd_msm_reserve", "kzgamd_msm_device", "kzgamd_set_device", "kzgamd_get_device", "kzgamd_settings_device",
@@ -251,6 +252,7 @@ def lib():
     L.compute_cells_and_kzg_proofs.argtypes = [vp, vp, vp, sp]
     L.kzgamd_compute_cells_and_kzg_proofs_batch.restype = C.c_int
     L.kzgamd_compute_cells_and_kzg_proofs_batch.argtypes = [vp, vp, vp, sz, sp]
+    L.kzgamd_recover_cells_and_kzg_proofs_batch.argtypes = [vp, vp, vp, vp, vp, sz, sp]
     L.kzgamd_settings_msm_handle.restype = vp
     L.kzgamd_settings_msm_handle.argtypes = [sp]
     L.kzgamd_msm_reserve.restype = RustError
@@ -848,6 +850,32 @@ def recover_cells_and_kzg_proofs(cell_indices, cells: bytes, settings: KZGSettin
     if rc != C_KZG_OK:
         raise KzgAmdError("recover_cells_and_kzg_proofs: C_KZG_RET %d" % rc)
     return out_cells.raw, (out_proofs.raw if out_proofs else None)
+
+
+def recover_cells_and_kzg_proofs_batch(indices_per_blob, cells_per_blob, settings: KZGSettings, want_proofs=True):
+    """kzgamd_recover_cells_and_kzg_proofs_batch (das.rs:209-241): blob b gives the cells cells_per_blob[b] (bytes,
+    2048 per cell) at the indices indices_per_blob[b] -> (list of n cells bytes 128*2048, list of n proofs bytes 128*48
+    | None), what n calls of recover_cells_and_kzg_proofs give"""
+    n = len(indices_per_blob)
+    counts = [len(ix) for ix in indices_per_blob]
+    if len(cells_per_blob) != n or any(len(c) != 2048 * k for c, k in zip(cells_per_blob, counts)):
+        # cells that do not match their indices cannot be expressed through (pointer, num_cells)
+        raise KzgAmdError("kzgamd_recover_cells_and_kzg_proofs_batch: C_KZG_RET %d" % C_KZG_BADARGS)
+    flat = [i for ix in indices_per_blob for i in ix]
+    idx = (C.c_uint64 * max(len(flat), 1))(*flat)
+    num = (C.c_uint64 * max(n, 1))(*counts)
+    cells = b"".join(cells_per_blob)
+    out_cells = C.create_string_buffer(max(n, 1) * 128 * 2048)
+    out_proofs = C.create_string_buffer(max(n, 1) * 128 * 48) if want_proofs else None
+    rc = lib().kzgamd_recover_cells_and_kzg_proofs_batch(out_cells, out_proofs, idx, cells, num, n, C.byref(settings.c))
+    if rc != C_KZG_OK:
+        raise KzgAmdError("kzgamd_recover_cells_and_kzg_proofs_batch: C_KZG_RET %d" % rc)
+    raw = out_cells.raw
+    got = [raw[b * 262144:(b + 1) * 262144] for b in range(n)]
+    if not want_proofs:
+        return got, None
+    raw = out_proofs.raw
+    return got, [raw[b * 6144:(b + 1) * 6144] for b in range(n)]
 
 
 def verify_cell_kzg_proof_batch(commitments: bytes, cell_indices, cells: bytes, proofs: bytes, settings: KZGSettings):

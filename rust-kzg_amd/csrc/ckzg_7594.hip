@@ -182,25 +182,17 @@ void enqueue_cell_proofs(KzgAmdSettings* dev, size_t n, hipStream_t st, bool fk2
     }
 }
 
-// compute_cells_and_kzg_proofs (kzg/src/das.rs:244-292) for n blobs; cells / proofs may be null (not both)
-void cells_and_proofs(uint8_t* cells, KZGProof* proofs, const Blob* blobs, size_t n, const CKZGSettings* cs,
-                      KzgAmdSettings* dev) {
-    std::lock_guard<std::mutex> lk(dev->mu);
-    kzgamd::DeviceGuard on_device(dev->device);
-    CK_HIP(on_device.err);
-    if (!dev->d_roots8192) {
-        CK_HIP(hipMalloc(&dev->d_roots8192, (2 * N + 1) * sizeof(ff::Fr)));
-        CK_HIP(hipMemcpy(dev->d_roots8192, cs->roots_of_unity, (2 * N + 1) * sizeof(ff::Fr), hipMemcpyHostToDevice));
-    }
-    // Cell proofs: FK20 for batches (the reference's algorithm: 64 transforms of 128 scalars, 128 MSMs of 64 points
-    // over x_ext_fft_columns, two G1 transforms of 128 points — ~25x fewer point additions than 128 MSMs of 4096, but
-    // the G1 transforms are 14 serial stages of a 128-bit scalar multiplication each: tens of ms of latency whatever
-    // the batch).  A few blobs: the direct form, one more fixed-base MSM per cell over the monomial table.
-    // Tuning key fk20 = 0 / 1 forces one or the other.
-    bool fk20 = proofs && n >= FK20_MIN_BLOBS;
-    if (dev->cfg_fk20 >= 0) fk20 = proofs && dev->cfg_fk20 != 0;
+// The proof form for the cell proofs of n blobs (true: FK20), its handle built.  Caller holds dev->mu on the device.
+// FK20 for batches (the reference's algorithm: 64 transforms of 128 scalars, 128 MSMs of 64 points over
+// x_ext_fft_columns, two G1 transforms of 128 points — ~25x fewer point additions than 128 MSMs of 4096, but the G1
+// transforms are 14 serial stages of a 128-bit scalar multiplication each: tens of ms of latency whatever the batch).
+// A few blobs: the direct form, one more fixed-base MSM per cell over the monomial table.  Tuning key fk20 = 0 / 1
+// forces one or the other.
+bool prepare_cell_proofs(KzgAmdSettings* dev, const CKZGSettings* cs, size_t n) {
+    bool fk20 = n >= FK20_MIN_BLOBS;
+    if (dev->cfg_fk20 >= 0) fk20 = dev->cfg_fk20 != 0;
     if (dev->fk20_unavailable) fk20 = false;
-    if (proofs && fk20) {
+    if (fk20) {
         // no HBM left for the FK20 table (creation throws, or succeeds without a wide table): the direct form computes
         // the same proofs; the useless handle is dropped and the choice remembered
         try {
@@ -215,7 +207,24 @@ void cells_and_proofs(uint8_t* cells, KZGProof* proofs, const Blob* blobs, size_
             fk20 = false;
         }
     }
-    if (proofs && !fk20 && !dev->msm_monomial) dev->msm_monomial = kzgamd::msm_create(dev->d_monomial, N, true, true, true, kzgamd::G1_TRUSTED, &dev->opt);
+    if (!fk20 && !dev->msm_monomial) dev->msm_monomial = kzgamd::msm_create(dev->d_monomial, N, true, true, true, kzgamd::G1_TRUSTED, &dev->opt);
+    return fk20;
+}
+
+void ensure_roots8192(KzgAmdSettings* dev, const CKZGSettings* cs) {
+    if (dev->d_roots8192) return;
+    CK_HIP(hipMalloc(&dev->d_roots8192, (2 * N + 1) * sizeof(ff::Fr)));
+    CK_HIP(hipMemcpy(dev->d_roots8192, cs->roots_of_unity, (2 * N + 1) * sizeof(ff::Fr), hipMemcpyHostToDevice));
+}
+
+// compute_cells_and_kzg_proofs (kzg/src/das.rs:244-292) for n blobs; cells / proofs may be null (not both)
+void cells_and_proofs(uint8_t* cells, KZGProof* proofs, const Blob* blobs, size_t n, const CKZGSettings* cs,
+                      KzgAmdSettings* dev) {
+    std::lock_guard<std::mutex> lk(dev->mu);
+    kzgamd::DeviceGuard on_device(dev->device);
+    CK_HIP(on_device.err);
+    ensure_roots8192(dev, cs);
+    const bool fk20 = proofs && prepare_cell_proofs(dev, cs, n);
     dev->ensure(n);
     dev->ensure_cells(n);
     if (proofs && fk20) dev->ensure_fk20(n);
@@ -302,6 +311,85 @@ __global__ void __launch_bounds__(256) k_fr_mul(ff::Fr* __restrict__ out, const 
 __global__ void __launch_bounds__(64) k_fr_inverse(ff::Fr* __restrict__ data, size_t n) {
     const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t < n) data[t] = ff::inverse_bgcd(data[t]);
+}
+
+// ---------------- batched recovery (kzgamd_recover_cells_and_kzg_proofs_batch): one launch per step for all blobs
+// The vanishing polynomial of blob b is V(X) = Z(X^64), Z with the roots w128^rbl7(i) of its missing cells i.  At the
+// domain point w8192^j, V = Z(w128^(j mod 128)); at the coset point 7 w8192^j, V = Z(7^64 w128^(j mod 128)).  So the
+// two transforms of the single call (vanishing_poly_eval, vanishing_poly_over_coset) are 128-periodic, and the
+// inverse of the second one takes 128 inversions per blob instead of 8192.
+struct RecBlob {           // host-built, 8 words per blob (KzgAmdSettings::d_rec_info)
+    u32 first;             // its first cell in the stage's concatenated cells
+    u32 drop_null;         // fewer than 128 cells: a Fr::null()-valued element is missing (see k_rec_scatter)
+    u32 pad[2];
+    u32 have[4];           // bit c: cell c given (the given cells are in ascending index order)
+};
+static_assert(sizeof(RecBlob) == 8 * sizeof(u32), "RecBlob is 8 words");
+
+// Zs[b][t] = prod_{i missing} (w128^t - w128^rbl7(i)),  Zc[b][t] = 1 / prod_{i missing} (7^64 w128^t - w128^rbl7(i));
+// one thread per (blob, t).  w128^t = roots8192[64 t].  Nothing missing: both all ones.  Zc is never a zero inverse:
+// 7^64 is not a 128th root of unity.
+__global__ void __launch_bounds__(64) k_rec_vanishing(ff::Fr* __restrict__ zs, ff::Fr* __restrict__ zc, const RecBlob* __restrict__ info,
+                                                      const ff::Fr* __restrict__ roots8192, ff::Fr seven64, size_t nblobs) {
+    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= nblobs * 128) return;
+    const RecBlob& rb = info[t >> 7];
+    const ff::Fr w = roots8192[64 * (t & 127)];
+    const ff::Fr wc = ff::mul(seven64, w);
+    ff::Fr ps = ff::Fr::one(), pc = ff::Fr::one();
+#pragma unroll 1
+    for (u32 i = 0; i < 128; ++i) {
+        if ((rb.have[i >> 5] >> (i & 31)) & 1u) continue;
+        const ff::Fr a = roots8192[64 * brev32(i, 7)];
+        ps = ff::mul(ps, ff::sub(w, a));
+        pc = ff::mul(pc, ff::sub(wc, a));
+    }
+    zs[t] = ps;
+    zc[t] = ff::inverse_bgcd(pc);
+}
+
+// The given cells of every blob (32-byte big-endian elements as the caller passed them, < r checked on the host) ->
+// A = E (.) Zs in natural order, blob b at b * 8192: brp slot s = 64 c + j of cell c lands at brev13(s), whose
+// residue mod 128 is rbl7(c).  A missing cell is zero; with drop_null a Fr::null()-valued element too (k_rec_scatter).
+// One thread per (blob, slot); the rank of cell c among the given ones is the popcount of the lower bits of `have`.
+__global__ void __launch_bounds__(256) k_rec_scatter_batch(ff::Fr* __restrict__ a, const u32* __restrict__ cells_be,
+                                                           const RecBlob* __restrict__ info, const ff::Fr* __restrict__ zs,
+                                                           ff::Fr null_mont, size_t nblobs) {
+    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= nblobs * 2 * N) return;
+    const size_t b = t >> 13;
+    const u32 s = (u32)t & (2 * N - 1), c = s >> 6, j = s & 63;
+    const RecBlob& rb = info[b];
+    ff::Fr v = ff::Fr::zero();
+    if ((rb.have[c >> 5] >> (c & 31)) & 1u) {
+        u32 rank = __builtin_popcount(rb.have[c >> 5] & ((1u << (c & 31)) - 1u));
+        for (u32 w = 0; w < (c >> 5); ++w) rank += __builtin_popcount(rb.have[w]);
+        const u32* src = cells_be + ((size_t)(rb.first + rank) * CELL_SIZE + j) * 8;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) v.v[k] = __builtin_bswap32(src[7 - k]);
+        v = ff::to_mont(v);
+        if (rb.drop_null && v == null_mont) v = ff::Fr::zero();
+    }
+    const u32 p = brev32(s, 13);
+    a[b * 2 * N + p] = fmul(v, zs[b * 128 + (p & 127)]);
+}
+
+// x[b][j] *= pw[j] (the coset shifts 7^j / 7^-j, j < 8192); mono (optional) also gets the first 4096 of every blob
+__global__ void __launch_bounds__(256) k_rec_mul_pow(ff::Fr* __restrict__ x, const ff::Fr* __restrict__ pw, ff::Fr* __restrict__ mono,
+                                                     size_t nblobs) {
+    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= nblobs * 2 * N) return;
+    const size_t j = t & (2 * N - 1);
+    const ff::Fr v = fmul(x[t], pw[j]);
+    x[t] = v;
+    if (mono && j < N) mono[(t >> 13) * N + j] = v;
+}
+
+// x[b][j] *= tab[b][j mod 128]
+__global__ void __launch_bounds__(256) k_rec_mul_periodic(ff::Fr* __restrict__ x, const ff::Fr* __restrict__ tab, size_t nblobs) {
+    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= nblobs * 2 * N) return;
+    x[t] = fmul(x[t], tab[(t >> 13) * 128 + (t & 127)]);
 }
 
 }  // namespace
@@ -501,7 +589,7 @@ void verify_cells(bool* ok, const Bytes48* commitments_bytes, const uint64_t* ce
         std::lock_guard<std::mutex> lk(dev->mu);
         kzgamd::DeviceGuard on_device(dev->device);
         CK_HIP(on_device.err);
-        dev->ensure_recover();
+        dev->ensure_recover(1);
         dev->ensure_vcells(n);
         if (!dev->d_roots8192) {
             CK_HIP(hipMalloc(&dev->d_roots8192, (2 * N + 1) * sizeof(ff::Fr)));
@@ -597,7 +685,7 @@ void recover_cells(Cell* recovered_cells, KZGProof* recovered_proofs, const uint
     CK_HIP(on_device.err);
     dev->ensure(1);
     dev->ensure_cells(1);
-    dev->ensure_recover();
+    dev->ensure_recover(1);
     hipStream_t st = dev->stream;
     const size_t E = 2 * N;
     ff::Fr *A = dev->d_rec[0], *B = dev->d_rec[1], *C = dev->d_rec[2], *D = dev->d_rec[3];
@@ -658,6 +746,121 @@ void recover_cells(Cell* recovered_cells, KZGProof* recovered_proofs, const uint
     CK_HIP(hipStreamSynchronize(st));
 }
 
+// Blobs per stage of a recovery batch: the workspace is ~2.6 MB per blob, plus 16 MB of quotient vectors per blob in
+// the direct proof form (ensure_q)
+constexpr size_t REC_STAGE = 256;
+constexpr size_t REC_STAGE_DIRECT = 32;
+
+// FsFr::from_bytes' range test on 32 big-endian bytes; the first byte settles almost every element (r = 0x73ed...)
+inline bool fr_be32_below_r(const uint8_t* in) {
+    if (in[0] != 0x73) return in[0] < 0x73;
+    ff::Fr v;
+    return fr_from_be32_checked(v, in);
+}
+
+// recover_cells_and_kzg_proofs_batch (kzg/src/das.rs:209-241): n independent recoveries.  Every blob is validated on the
+// host first, with recover_cells' checks; then per stage of <= REC_STAGE blobs: k_rec_vanishing, k_rec_scatter_batch
+// (= E (.) Zs), four batched 8192-point transforms with the coset shifts and (.) Zc between them, k_cells_out — the
+// field values of the single call's six-transform sequence — and the cell proofs of the recovered polynomials as
+// cells_and_proofs makes them (same form choice, cells copied back on stream2 while the proofs run).
+void recover_cells_batch(Cell* recovered_cells, KZGProof* recovered_proofs, const uint64_t* cell_indices, const Cell* cells,
+                         const uint64_t* num_cells, size_t n, const CKZGSettings* cs, KzgAmdSettings* dev) {
+    std::vector<RecBlob> info(n);
+    std::vector<size_t> first(n + 1, 0);
+    for (size_t b = 0; b < n; ++b) {
+        const uint64_t nc = num_cells[b];
+        CK_REQUIRE(nc <= CELLS_PER_EXT_BLOB, "Cell length cannot be larger than CELLS_PER_EXT_BLOB");
+        CK_REQUIRE(nc >= CELLS_PER_EXT_BLOB / 2, "Impossible to recover");
+        const size_t f = first[b];
+        for (size_t i = 0; i < nc; ++i)
+            for (size_t j = 0; j < CELL_SIZE; ++j) CK_REQUIRE(fr_be32_below_r(cells[f + i].bytes + 32 * j), "Invalid scalar");
+        RecBlob& rb = info[b];
+        memset(&rb, 0, sizeof rb);
+        for (size_t i = 0; i < nc; ++i) {
+            const uint64_t c = cell_indices[f + i];
+            CK_REQUIRE(c < CELLS_PER_EXT_BLOB, "Invalid cell index");
+            if (i + 1 < nc) CK_REQUIRE(cell_indices[f + i + 1] > c, "Indices must be in strictly ascending order");
+            rb.have[c >> 5] |= 1u << (c & 31);
+        }
+        rb.drop_null = nc != CELLS_PER_EXT_BLOB;
+        first[b + 1] = f + (size_t)nc;
+    }
+    ff::Fr nul;
+    for (int k = 0; k < 8; ++k) nul.v[k] = 0xffffffffu;
+    nul = ff::to_mont(nul);  // Fr::null() = from_u64_arr([u64::MAX; 4]): (2^256 - 1) mod r, Montgomery form
+    ff::Fr seven64 = ff::Fr::zero();
+    seven64.v[0] = 7;
+    seven64 = ff::to_mont(seven64);
+    for (int k = 0; k < 6; ++k) seven64 = ff::mul(seven64, seven64);  // 7^64
+
+    std::lock_guard<std::mutex> lk(dev->mu);
+    kzgamd::DeviceGuard on_device(dev->device);
+    CK_HIP(on_device.err);
+    ensure_roots8192(dev, cs);
+    const bool fk20 = recovered_proofs && prepare_cell_proofs(dev, cs, n);
+    // equal stages, so that none of them is a small remainder
+    const size_t stage_max = recovered_proofs && !fk20 ? REC_STAGE_DIRECT : REC_STAGE;
+    const size_t nstages = (n + stage_max - 1) / stage_max, per = (n + nstages - 1) / nstages;
+    dev->ensure_recover(per);
+    dev->ensure_cells(per);
+    if (recovered_proofs && fk20) dev->ensure_fk20(per);
+    if (recovered_proofs && !fk20) dev->ensure_q(per);
+    hipStream_t st = dev->stream;
+    const bool side_copy = recovered_proofs && dev->stream2 && dev->stream2 != st;
+    if (side_copy && !dev->ev_cells) CK_HIP(hipEventCreateWithFlags(&dev->ev_cells, hipEventDisableTiming));
+    const size_t E = 2 * N;
+    ff::Fr *A = dev->d_rec[0], *D = dev->d_rec[1], *Zs = dev->d_rec[2], *Zc = dev->d_rec[3];
+    const RecBlob* d_info = reinterpret_cast<const RecBlob*>(dev->d_rec_info);
+    for (size_t s0 = 0; s0 < n; s0 += per) {
+        const size_t m = std::min(per, n - s0), c0 = first[s0], ncells = first[s0 + m] - c0;
+        std::vector<RecBlob> sinfo(info.begin() + s0, info.begin() + s0 + m);
+        for (size_t b = 0; b < m; ++b) sinfo[b].first = (u32)(first[s0 + b] - c0);
+        const unsigned grid = (unsigned)(m * E / 256);
+        auto ntt = [&](ff::Fr* out, const ff::Fr* in, int inverse) {
+            if (kzgamd_ntt_fr_device(dev->ntt, out, in, E, m, inverse, st) != 0) throw CkErr{C_KZG_ERROR, "ntt"};
+        };
+        try {
+            CK_HIP(hipMemcpyAsync(dev->d_rec_info, sinfo.data(), m * sizeof(RecBlob), hipMemcpyHostToDevice, st));
+            CK_HIP(hipMemcpyAsync(dev->d_rec_in, cells + c0, ncells * BYTES_PER_CELL, hipMemcpyHostToDevice, st));
+            hipLaunchKernelGGL(k_rec_vanishing, dim3((unsigned)(m * 128 / 64)), dim3(64), 0, st, Zs, Zc, d_info,
+                               (const ff::Fr*)dev->d_roots8192, seven64, m);
+            hipLaunchKernelGGL(k_rec_scatter_batch, dim3(grid), dim3(256), 0, st, A, (const u32*)dev->d_rec_in, d_info,
+                               (const ff::Fr*)Zs, nul, m);
+            ntt(D, A, 1);                                                                     // extended_evaluation_times_zero_coeffs
+            hipLaunchKernelGGL(k_rec_mul_pow, dim3(grid), dim3(256), 0, st, D, (const ff::Fr*)dev->d_pow7, (ff::Fr*)nullptr, m);
+            ntt(A, D, 0);                                                                     // ... over the coset
+            hipLaunchKernelGGL(k_rec_mul_periodic, dim3(grid), dim3(256), 0, st, A, (const ff::Fr*)Zc, m);
+            ntt(D, A, 1);                                                                     // coset_ifft
+            hipLaunchKernelGGL(k_rec_mul_pow, dim3(grid), dim3(256), 0, st, D, (const ff::Fr*)dev->d_pow7inv,
+                               recovered_proofs ? dev->d_fr_b : (ff::Fr*)nullptr, m);          // reconstructed_poly_coeff
+            ntt(A, D, 0);                                                                     // its evaluations, natural order
+            hipLaunchKernelGGL(k_cells_out, dim3(grid), dim3(256), 0, st, reinterpret_cast<u32*>(dev->d_fr_ext), (const ff::Fr*)A, m);
+            CK_HIP(hipGetLastError());
+            uint8_t* out_cells = recovered_cells[s0 * CELLS_PER_EXT_BLOB].bytes;
+            if (side_copy) CK_HIP(hipEventRecord(dev->ev_cells, st));
+            if (recovered_proofs) enqueue_cell_proofs(dev, m, st, fk20);
+            if (side_copy) {
+                CK_HIP(hipStreamWaitEvent(dev->stream2, dev->ev_cells, 0));
+                CK_HIP(hipMemcpyAsync(out_cells, dev->d_fr_ext, m * E * 32, hipMemcpyDeviceToHost, dev->stream2));
+            } else {
+                CK_HIP(hipMemcpyAsync(out_cells, dev->d_fr_ext, m * E * 32, hipMemcpyDeviceToHost, st));
+            }
+            if (recovered_proofs)
+                CK_HIP(hipMemcpyAsync(recovered_proofs + s0 * CELLS_PER_EXT_BLOB, dev->d_proofs, m * CELLS_PER_EXT_BLOB * 48,
+                                      hipMemcpyDeviceToHost, st));
+        } catch (...) {
+            // a copy into the caller's buffers may be in flight on either stream: nothing of it may outlive this call
+            (void)hipStreamSynchronize(st);
+            if (side_copy) (void)hipStreamSynchronize(dev->stream2);
+            throw;
+        }
+        // the next stage overwrites the workspace; both streams drain first (also on the way out of a failure)
+        const hipError_t e1 = hipStreamSynchronize(st);
+        if (side_copy) CK_HIP(hipStreamSynchronize(dev->stream2));
+        CK_HIP(e1);
+    }
+}
+
 }  // namespace
 
 // c_bindings.rs:290-355 -> DAS::verify_cell_kzg_proof_batch (kzg/src/das.rs:294-389)
@@ -684,6 +887,18 @@ extern "C" C_KZG_RET recover_cells_and_kzg_proofs(Cell* recovered_cells, KZGProo
     if (!dev) return C_KZG_BADARGS;
     if (num_cells && (!cell_indices || !cells)) return C_KZG_BADARGS;
     return guarded([&] { recover_cells(recovered_cells, recovered_proofs, cell_indices, cells, (size_t)num_cells, s, dev); });
+}
+
+// das.rs:209-241 (recover_cells_and_kzg_proofs_batch); recovered_proofs may be NULL
+extern "C" C_KZG_RET kzgamd_recover_cells_and_kzg_proofs_batch(Cell* recovered_cells, KZGProof* recovered_proofs,
+                                                               const uint64_t* cell_indices, const Cell* cells,
+                                                               const uint64_t* num_cells, size_t n, const CKZGSettings* s) {
+    if (!recovered_cells) return C_KZG_BADARGS;
+    KzgAmdSettings* dev = lookup(s);
+    if (!dev) return C_KZG_BADARGS;
+    if (n == 0) return C_KZG_OK;
+    if (!num_cells || !cell_indices || !cells) return C_KZG_BADARGS;  // every blob needs >= 64 cells
+    return guarded([&] { recover_cells_batch(recovered_cells, recovered_proofs, cell_indices, cells, num_cells, n, s, dev); });
 }
 
 // blst/src/eip_7594.rs:35-97: the Fiat-Shamir scalar of a cell batch (no settings: the inputs are only parsed —

@@ -373,9 +373,11 @@ struct KzgAmdSettings {
     // EIP-7594 cell verification / recovery state, built on first use
     std::vector<uint8_t> mono64_bytes;  // g1_values_monomial[0..64) compressed (the interpolation-polynomial commitment)
     AffPt* d_mono64 = nullptr;          // ... decoded and subgroup-checked once, as MSM slots
-    ff::Fr* d_rec[4] = {nullptr, nullptr, nullptr, nullptr};  // recovery: four vectors of 8192 field elements
-    u32* d_rec_in = nullptr;         // up to 128 cells as canonical limbs
-    u32* d_rec_idx = nullptr;        // their cell indices
+    ff::Fr* d_rec[4] = {nullptr, nullptr, nullptr, nullptr};  // recovery: four vectors of 8192 field elements per blob
+    u32* d_rec_in = nullptr;         // up to 128 cells per blob (the single call: canonical limbs; a batch: the bytes as given)
+    u32* d_rec_idx = nullptr;        // the single call's cell indices (128)
+    u32* d_rec_info = nullptr;       // a batch: 8 words per blob (ckzg_7594.hip, RecBlob)
+    size_t cap_rec = 0;              // blobs d_rec / d_rec_in / d_rec_info hold
     ff::Fr* d_pow7 = nullptr;        // 7^i and 7^-i, i < 8192 (coset shifts, das.rs:463-491)
     ff::Fr* d_pow7inv = nullptr;
     bool fk20_unavailable = false;   // the FK20 table could not be built (no HBM left): batches use the direct form
@@ -398,25 +400,41 @@ struct KzgAmdSettings {
         CK_HIP(hipMalloc(&d_vc_pw, cap * sizeof(ff::Fr)));
         cap_vc = cap;
     }
-    void ensure_recover() {
-        if (d_rec[0]) return;
-        for (int k = 0; k < 4; ++k) CK_HIP(hipMalloc(&d_rec[k], 2 * N * sizeof(ff::Fr)));
-        CK_HIP(hipMalloc(&d_rec_in, 2 * N * 32));
-        CK_HIP(hipMalloc(&d_rec_idx, 128 * sizeof(u32)));
-        CK_HIP(hipMalloc(&d_pow7, 2 * N * sizeof(ff::Fr)));
-        CK_HIP(hipMalloc(&d_pow7inv, 2 * N * sizeof(ff::Fr)));
-        std::vector<ff::Fr> p(2 * N), q(2 * N);
-        ff::Fr seven = ff::Fr::zero();
-        seven.v[0] = 7;
-        seven = ff::to_mont(seven);
-        const ff::Fr inv7 = ff::inverse_bgcd(seven);
-        p[0] = q[0] = ff::Fr::one();
-        for (size_t i = 1; i < 2 * N; ++i) {
-            p[i] = ff::mul(p[i - 1], seven);
-            q[i] = ff::mul(q[i - 1], inv7);
+    // the coset tables and the single call's index buffer once; the per-blob buffers for nblobs blobs (kept, grown on demand)
+    void ensure_recover(size_t nblobs) {
+        if (!d_pow7inv) {
+            if (!d_rec_idx) CK_HIP(hipMalloc(&d_rec_idx, 128 * sizeof(u32)));
+            if (!d_pow7) CK_HIP(hipMalloc(&d_pow7, 2 * N * sizeof(ff::Fr)));
+            CK_HIP(hipMalloc(&d_pow7inv, 2 * N * sizeof(ff::Fr)));
+            std::vector<ff::Fr> p(2 * N), q(2 * N);
+            ff::Fr seven = ff::Fr::zero();
+            seven.v[0] = 7;
+            seven = ff::to_mont(seven);
+            const ff::Fr inv7 = ff::inverse_bgcd(seven);
+            p[0] = q[0] = ff::Fr::one();
+            for (size_t i = 1; i < 2 * N; ++i) {
+                p[i] = ff::mul(p[i - 1], seven);
+                q[i] = ff::mul(q[i - 1], inv7);
+            }
+            CK_HIP(hipMemcpy(d_pow7, p.data(), p.size() * sizeof(ff::Fr), hipMemcpyHostToDevice));
+            CK_HIP(hipMemcpy(d_pow7inv, q.data(), q.size() * sizeof(ff::Fr), hipMemcpyHostToDevice));
         }
-        CK_HIP(hipMemcpy(d_pow7, p.data(), p.size() * sizeof(ff::Fr), hipMemcpyHostToDevice));
-        CK_HIP(hipMemcpy(d_pow7inv, q.data(), q.size() * sizeof(ff::Fr), hipMemcpyHostToDevice));
+        if (nblobs <= cap_rec) return;
+        release_recover();
+        for (int k = 0; k < 4; ++k) CK_HIP(hipMalloc(&d_rec[k], nblobs * 2 * N * sizeof(ff::Fr)));
+        CK_HIP(hipMalloc(&d_rec_in, nblobs * 2 * N * 32));
+        CK_HIP(hipMalloc(&d_rec_info, nblobs * 8 * sizeof(u32)));
+        cap_rec = nblobs;
+    }
+    void release_recover() {
+        for (int k = 0; k < 4; ++k) {
+            if (d_rec[k]) (void)hipFree(d_rec[k]);
+            d_rec[k] = nullptr;
+        }
+        if (d_rec_in) (void)hipFree(d_rec_in);
+        if (d_rec_info) (void)hipFree(d_rec_info);
+        d_rec_in = d_rec_info = nullptr;
+        cap_rec = 0;
     }
     std::vector<kzgamd::pairing::G2Jac> g2_monomial;  // [tau^i]G2, i < 65 (host; the pairing checks use [1])
     std::vector<ff::Fr> brp_roots;  // brp_roots_of_unity[0..8192) (host copy, Montgomery)
@@ -450,12 +468,10 @@ struct KzgAmdSettings {
             if (pipe[j]) (void)hipStreamDestroy(pipe[j]);
         }
         if (d_brp_roots) (void)hipFree(d_brp_roots);
-        for (int k = 0; k < 4; ++k)
-            if (d_rec[k]) (void)hipFree(d_rec[k]);
+        release_recover();
         if (d_vc_cells) (void)hipFree(d_vc_cells);
         if (d_vc_cols) (void)hipFree(d_vc_cols);
         if (d_vc_pw) (void)hipFree(d_vc_pw);
-        if (d_rec_in) (void)hipFree(d_rec_in);
         if (d_rec_idx) (void)hipFree(d_rec_idx);
         if (d_pow7) (void)hipFree(d_pow7);
         if (d_pow7inv) (void)hipFree(d_pow7inv);

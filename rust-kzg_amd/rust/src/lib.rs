@@ -332,6 +332,9 @@ pub mod ckzg {
         pub fn compute_cells_and_kzg_proofs(cells: *mut Cell, proofs: *mut KZGProof, blob: *const Blob, s: &CKZGSettings) -> CKzgRet;
         pub fn recover_cells_and_kzg_proofs(recovered_cells: *mut Cell, recovered_proofs: *mut KZGProof, cell_indices: *const u64,
                                             cells: *const Cell, num_cells: u64, s: &CKZGSettings) -> CKzgRet;
+        pub fn kzgamd_recover_cells_and_kzg_proofs_batch(recovered_cells: *mut Cell, recovered_proofs: *mut KZGProof,
+                                                         cell_indices: *const u64, cells: *const Cell, num_cells: *const u64,
+                                                         n: usize, s: &CKZGSettings) -> CKzgRet;
         pub fn verify_cell_kzg_proof_batch(ok: *mut bool, commitments_bytes: *const Bytes48, cell_indices: *const u64,
                                            cells: *const Cell, proofs_bytes: *const Bytes48, num_cells: u64, s: &CKZGSettings) -> CKzgRet;
         // batched and multi-GPU forms (new API, include/kzg_mi355x.h): contiguous slabs of the batch per settings object
