@@ -184,6 +184,35 @@ int kzgamd_das_fft_extension_device(void *ctx, void *d_odds, const void *d_evens
                                     size_t nbatch, void *stream);
 /* host copies of the settings arrays (FFTSettings getters, kzg/src/lib.rs:465-481); counts in elements */
 int kzgamd_ntt_roots(void *ctx, blst_fr *roots /*W+1*/, blst_fr *reverse_roots /*W+1*/, blst_fr *brp_roots /*W*/);
+/* Generic FK20 data-availability proofs for any polynomial length n = n2 / 2 and chunk length:
+ * FK20SingleSettings (chunk_len = 1, blst/src/types/fk20_single_settings.rs:38-111) and FK20MultiSettings
+ * (blst/src/types/fk20_multi_settings.rs:60-175), npoly polynomials per call.  With k2 = n2 / chunk_len the handle keeps
+ * the k2 x chunk_len points fft_g1(x_i)[j] on the GPU, either for a scalar multiplication per product (form 1, always
+ * available) or as a wide fixed-base table of k2 base sets (form 2: taken when the table fits cfg->table_budget_bytes —
+ * k2 * chunk_len * 2^9 * 13 slots of 128 B at the least; "fk20_table=0" in cfg->tuning: never, "fk20_table=1": required.
+ * fk20_table is a key of this entry point alone, read from cfg->tuning only: it is not in kzgamd_tuning_keys() and the
+ * other handle types refuse it like any unknown key).  Proofs equal the
+ * reference's as group elements.  The setup points must lie in G1 (both forms split scalars with the endomorphism).
+ *
+ * kzgamd_fk20_new: FK20SingleSettings::new / FK20MultiSettings::new.  `ntt` = kzgamd_ntt_new(scale) with 2^scale >= n2
+ * (roots are taken with stride max_width / k2, as fft_g1 does).  The FK20 handle keeps `ntt` by pointer and uses it in
+ * every call: free the FK20 handle FIRST, the NTT handle after it.  g1_monomial = [s^i]G, i < num_g1, Jacobian; needs
+ * num_g1 >= n2/2 - chunk_len.  *err (may be NULL): 0 ok, 1 n2 > max width, 2 n2 not a power of two, 3 n2 < 2,
+ * 4 chunk_len > n2/2, 5 chunk_len not a power of two (or 0), 6 too few setup points — the reference's checks in the
+ * reference's order — negative = NULL argument (-1), malformed configuration (-2), fk20_table = 1 without room (-3) or a
+ * device error.  Returns NULL on any error.  kzgamd_fk20_free gives every byte of HBM back.
+ *
+ * kzgamd_fk20_da: npoly polynomials of n = n2/2 Montgomery coefficients each (contiguous) -> npoly x (n2 / chunk_len)
+ * proofs, Jacobian.  optimized != 0: data_availability_optimized (natural order); 0: data_availability (bit-reversed per
+ * polynomial).  0 ok, 3 n != n2/2, -1 NULL argument, other negatives = device error.  npoly = 0: ok, nothing written.
+ * Thread-safe like every handle (calls on one handle take turns; fft_g1 / ntt_fr calls on `ntt` may run beside them).
+ *
+ * kzgamd_fk20_info: n2, chunk_len and the form in use (1 = direct, 2 = table); any pointer may be NULL. */
+void *kzgamd_fk20_new(void *ntt, const blst_p1 *g1_monomial, size_t num_g1, size_t n2, size_t chunk_len,
+                      const KzgAmdConfig *cfg, int *err);
+void kzgamd_fk20_free(void *fk);
+int kzgamd_fk20_da(void *fk, blst_p1 *out, const blst_fr *polys, size_t n, size_t npoly, int optimized);
+int kzgamd_fk20_info(void *fk, size_t *n2, size_t *chunk_len, int *form);
 /* The tile plan the NTT kernel runs for (kind, T) — host-only, no GPU needed (rust-kzg_amd/csrc/ntt_plan.h):
  * kind 0 = whole transform of 2^T <= 4096 points, 1 = first pass of a longer one, 2 = later pass; rounds[4*r..] =
  * {first stage, stages, barrier after, element bit}; tab[(r*1024 + thread)*4..] = {idxA, idxB, lds(idxA), lds(idxB)}.

@@ -65,6 +65,7 @@ EXPORTS = [
     "kzgamd_device_count", "kzgamd_version", "kzgamd_msm_create_device", "kzgamd_generate_points",
     "kzgamd_ntt_new", "kzgamd_ntt_free", "ntt_fr", "das_fft_extension", "kzgamd_ntt_fr_device", "kzgamd_ntt_roots", "kzgamd_ntt_plan_dump", "kzgamd_ntt_das_plan_dump", "kzgamd_das_fft_extension_device",
     "fft_g1", "kzgamd_fft_g1_batch", "kzgamd_g1_sum",
+    "kzgamd_fk20_new", "kzgamd_fk20_free", "kzgamd_fk20_da", "kzgamd_fk20_info",
     "load_trusted_setup", "load_trusted_setup_file", "free_trusted_setup", "blob_to_kzg_commitment",
     "compute_kzg_proof", "compute_blob_kzg_proof", "kzgamd_compute_blob_kzg_proof_batch", "compute_challenge",
     "bytes_to_kzg_commitment", "bytes_from_bls_field", "compute_cells_and_kzg_proofs",
@@ -209,6 +210,14 @@ def lib():
     L.fft_g1.argtypes = [vp, vp, vp, sz, C.c_int]
     L.kzgamd_fft_g1_batch.restype = C.c_int
     L.kzgamd_fft_g1_batch.argtypes = [vp, vp, vp, sz, sz, C.c_int]
+    L.kzgamd_fk20_new.restype = vp
+    L.kzgamd_fk20_new.argtypes = [vp, vp, sz, sz, sz, cp, C.POINTER(C.c_int)]
+    L.kzgamd_fk20_free.restype = None
+    L.kzgamd_fk20_free.argtypes = [vp]
+    L.kzgamd_fk20_da.restype = C.c_int
+    L.kzgamd_fk20_da.argtypes = [vp, vp, vp, sz, sz, C.c_int]
+    L.kzgamd_fk20_info.restype = C.c_int
+    L.kzgamd_fk20_info.argtypes = [vp, C.POINTER(sz), C.POINTER(sz), C.POINTER(C.c_int)]
     L.kzgamd_ntt_roots.restype = C.c_int
     L.kzgamd_ntt_roots.argtypes = [vp, vp, vp, vp]
     sp = C.POINTER(CKZGSettings)
@@ -664,6 +673,72 @@ class FFTSettings:
         if self.handle:
             lib().kzgamd_ntt_free(self.handle)
             self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+FK20_ERRORS = {
+    1: "n2 must be less than or equal to kzg settings max width",
+    2: "n2 must be a power of two",
+    3: "n2 must be greater than or equal to 2",
+    4: "chunk_len must be greater or equal to n2 / 2",
+    5: "chunk_len must be a power of two",
+    6: "the setup has fewer than n2 / 2 - chunk_len G1 points",
+}
+
+
+class FK20Settings:
+    """FK20SingleSettings (chunk_len = 1) / FK20MultiSettings of the reference over an FFTSettings handle
+    (blst/src/types/fk20_single_settings.rs, fk20_multi_settings.rs); errors carry the reference's messages.  Keeps the
+    FFTSettings object alive; close() (or leaving the `with` block) frees the GPU state."""
+
+    def __init__(self, fft_settings, g1_monomial, num_g1, n2, chunk_len=1, config=None):
+        self.fs = fft_settings
+        self.handle = None
+        err = C.c_int(0)
+        self.handle = lib().kzgamd_fk20_new(fft_settings.handle, _addr(g1_monomial), num_g1, n2, chunk_len, _cfgp(config), C.byref(err))
+        self.err = err.value
+        if not self.handle:
+            raise KzgAmdError(FK20_ERRORS.get(err.value, "kzgamd_fk20_new failed: %d (no GPU, bad configuration, or fk20_table=1 without room)" % err.value))
+        self.n2, self.chunk_len = n2, chunk_len
+
+    @classmethod
+    def new(cls, fft_settings, g1_monomial, num_g1, n2, chunk_len=1, config=None):
+        return cls(fft_settings, g1_monomial, num_g1, n2, chunk_len, config)
+
+    def data_availability(self, polys, npoly=1, optimized=False):
+        """polys: blst_fr[npoly * n2/2] (Montgomery).  Returns a new (BlstP1 * (npoly * n2/chunk_len)), Jacobian:
+        bit-reversed per polynomial (data_availability) or in natural order (optimized=True)."""
+        if not self.handle:
+            raise KzgAmdError("FK20Settings is closed")
+        n = self.n2 // 2
+        out = (BlstP1 * max(1, npoly * (self.n2 // self.chunk_len)))()
+        rc = lib().kzgamd_fk20_da(self.handle, out, _addr(polys), n, npoly, 1 if optimized else 0)
+        if rc != 0:
+            raise KzgAmdError("kzgamd_fk20_da: %d" % rc)
+        return out
+
+    def info(self):
+        """(n2, chunk_len, form): form 1 = a scalar multiplication per product, 2 = wide fixed-base table"""
+        a, b, f = C.c_size_t(0), C.c_size_t(0), C.c_int(0)
+        if lib().kzgamd_fk20_info(self.handle, C.byref(a), C.byref(b), C.byref(f)) != 0:
+            raise KzgAmdError("kzgamd_fk20_info failed")
+        return a.value, b.value, f.value
+
+    def close(self):
+        if self.handle:
+            lib().kzgamd_fk20_free(self.handle)
+            self.handle = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
 
     def __del__(self):
         try:

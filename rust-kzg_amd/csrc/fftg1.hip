@@ -48,13 +48,7 @@ constexpr int NTHREADS = 64;        // one wave per workgroup: long serial lanes
 constexpr int MAXTHREADS = 256;     // ... or four waves per workgroup once there is a wave for every SIMD (block_threads)
 constexpr int BOUND = 512;          // launch bound of the long-lane kernels: two waves per SIMD must fit (<= 256 registers)
 
-// one root (or n^-1) split for the two lanes of a butterfly: 127-bit magnitudes and their signs
-struct RootSplit {
-    u32 k[2][4];
-    u32 neg[2];
-    u32 pad[2];
-};
-static_assert(sizeof(RootSplit) == 48, "RootSplit");
+using kzgamd::RootSplit;  // one root (or n^-1) split for the two lanes of a butterfly (ntt_internal.h)
 
 __device__ __forceinline__ u32 brev(u32 v, int bits) { return bits == 0 ? 0u : __builtin_bitreverse32(v) >> (32 - bits); }
 
@@ -274,6 +268,43 @@ __global__ void __launch_bounds__(BOUND) k_g1_scale_chain(Xyzz* __restrict__ dat
     if (half == 0 && r == 0) data[unit >> 1] = acc;
 }
 
+// out[u] = scalars[u] * bases[u % nbase]: k_g1_scale_chain with the scalar of every product read from device memory
+// (the transformed Toeplitz coefficients of FK20, split by the caller) and the point from a table of bases.  A half
+// whose scalar is zero, or whose base is the identity, contributes the identity (nothing is multiplied).
+template <int G>
+__global__ void __launch_bounds__(BOUND) k_g1_varmul_chain(Xyzz* __restrict__ out, const Xyzz* __restrict__ bases, size_t nbase,
+                                                            const RootSplit* __restrict__ sc, Xyzz* __restrict__ tab, size_t total) {
+    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;  // total = 2 * G * products
+    if (t >= total) return;
+    const int r = (int)(t % G);
+    const size_t unit = t / G, nunits = total / G;
+    const int half = (int)(unit & 1);
+    const size_t u = unit >> 1;
+    const RootSplit* rs = sc + u;
+    const u32 k0 = rs->k[half][0], k1 = rs->k[half][1], k2 = rs->k[half][2], k3 = rs->k[half][3];
+    Xyzz acc = bases[u % nbase];
+    const bool mul = !g1::is_inf(acc) && (k0 | k1 | k2 | k3) != 0;
+    if (mul) grp::apply_half(acc, rs->neg[half] != 0, half);
+    else g1::set_inf(acc);
+    Xyzz* slots = tab + unit;
+    const Xyzz* partner = tab + (unit ^ 1) + (size_t)grp::SLOT_HALF * nunits;
+    grp::run_chain<G>(acc, mul, k0, k1, k2, k3, slots, nunits, true, 1, [&](int) { return grp::TailOp{partner, false}; }, r);
+    if (half == 0 && r == 0) out[u] = acc;
+}
+
+// one level of the sum over the `group` products of a position: element m < h of every group takes element m + h;
+// the last level (h == 1) writes the sums next to each other into out
+__global__ void __launch_bounds__(256) k_g1_group_sum(Xyzz* __restrict__ out, Xyzz* __restrict__ prod, size_t group, size_t h,
+                                                      size_t total) {
+    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;  // total = groups * h
+    if (t >= total) return;
+    const size_t g = t / h, m = t % h;
+    Xyzz a = prod[g * group + m];
+    g1::dadd(a, prod[g * group + m + h]);
+    if (h == 1) out[g] = a;
+    else prod[g * group + m] = a;
+}
+
 // XYZZ -> blst Jacobian, one lane per point
 __global__ void __launch_bounds__(256) k_g1_store(ff::Fp* __restrict__ out, const Xyzz* __restrict__ data, size_t total) {
     const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -459,6 +490,24 @@ __global__ void __launch_bounds__(64) k_g1_scale_mul_wide(Xyzz* __restrict__ h, 
     wide_half_mul(p, k, inv_n.neg[half] != 0, half, lc, ws, lane);
     g1w::store(h + unit, p, lc, lane);
 }
+// the same with the scalar of every product from device memory: h[2u], h[2u + 1] = the halves of scalars[u] * bases[u % nbase]
+// (k_g1_scale_sum_wide adds them); a zero half-scalar leaves the identity
+__global__ void __launch_bounds__(64) k_g1_varmul_wide(Xyzz* __restrict__ h, const Xyzz* __restrict__ bases, size_t nbase,
+                                                       const RootSplit* __restrict__ sc) {
+    __shared__ WideScratch ws;
+    const int lane = threadIdx.x;
+    const size_t unit = blockIdx.x;
+    const int half = (int)(unit & 1);
+    const size_t u = unit >> 1;
+    const RootSplit* rs = sc + u;
+    u32 k[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) k[i] = rs->k[half][i];
+    const fpw::Lane lc = fpw::lane_consts(lane);
+    g1w::WPt p = g1w::load(bases + u % nbase, lane);
+    wide_half_mul(p, k, rs->neg[half] != 0, half, lc, ws, lane);
+    g1w::store(h + unit, p, lc, lane);
+}
 __global__ void __launch_bounds__(64) k_g1_scale_sum_wide(Xyzz* __restrict__ data, const Xyzz* __restrict__ h) {
     __shared__ u32 sh[16];
     const int lane = threadIdx.x;
@@ -544,6 +593,28 @@ void enqueue_scale(NttCtx* ctx, Xyzz* data, Xyzz* tab, const RootSplit& inv_n, s
     }
 }
 
+// out[g] = the sum of the `group` products scalars[u] * bases[u % nbase] of position g: the lanes-per-product form by the
+// number of half-products as enqueue_scale picks it, then log2(group) levels of pairwise sums
+void enqueue_varmul_sum(NttCtx* ctx, Xyzz* out, Xyzz* prod, Xyzz* tab, const Xyzz* bases, size_t nbase, const RootSplit* sc,
+                        size_t nprod, size_t group, hipStream_t st) {
+    Xyzz* dst = group == 1 ? out : prod;
+    if (2 * nprod <= ctx->g1_wide_max) {
+        hipLaunchKernelGGL(k_g1_varmul_wide, dim3((unsigned)(2 * nprod)), dim3(64), 0, st, tab, bases, nbase, sc);
+        hipLaunchKernelGGL(k_g1_scale_sum_wide, dim3((unsigned)nprod), dim3(64), 0, st, dst, (const Xyzz*)tab);
+    } else if (2 * nprod <= ctx->g1_quad_max) {
+        hipLaunchKernelGGL(k_g1_varmul_chain<4>, grid_for(8 * nprod), dim3(block_threads(8 * nprod)), 0, st, dst, bases, nbase, sc, tab, 8 * nprod);
+    } else if (2 * nprod <= ctx->g1_pair_max) {
+        hipLaunchKernelGGL(k_g1_varmul_chain<2>, grid_for(4 * nprod), dim3(block_threads(4 * nprod)), 0, st, dst, bases, nbase, sc, tab, 4 * nprod);
+    } else {
+        hipLaunchKernelGGL(k_g1_varmul_chain<1>, grid_for(2 * nprod), dim3(block_threads(2 * nprod)), 0, st, dst, bases, nbase, sc, tab, 2 * nprod);
+    }
+    const size_t groups = nprod / group;
+    for (size_t h = group / 2; h >= 1; h /= 2) {
+        const size_t total = groups * h;
+        hipLaunchKernelGGL(k_g1_group_sum, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, out, prod, group, h, total);
+    }
+}
+
 void ensure_g1(NttCtx* ctx, size_t total, size_t tab_lanes) {
     if (!ctx->d_kroots) {
         std::vector<RootSplit> split(ctx->W + 1);
@@ -592,8 +663,8 @@ void ensure_g1_tab(NttCtx* ctx, size_t tab_lanes) {
 // result in natural order, or nullptr on an allocation failure.  scale_inverse = false leaves out the n^-1 of an inverse
 // transform (a caller that can fold it into its scalars saves one scalar multiplication per point).  The per-lane tables are shared by the handle: one
 // stream at a time (the c-kzg layer calls this under its settings lock and synchronises before it returns).
-void* kzgamd::fftg1_device(NttCtx* ctx, void* data_v, void* scratch_v, size_t n, size_t nbatch, int inverse, hipStream_t st,
-                           bool scale_inverse) {
+static void* fftg1_enqueue(NttCtx* ctx, void* data_v, void* scratch_v, size_t n, size_t nbatch, int inverse, hipStream_t st,
+                           bool scale_inverse, void* tab_v) {
     if (!ctx || n == 0 || (n & (n - 1)) || n > ctx->W) return nullptr;
     try {
         const size_t total = n * nbatch, bf = total / 2;
@@ -602,9 +673,9 @@ void* kzgamd::fftg1_device(NttCtx* ctx, void* data_v, void* scratch_v, size_t n,
         // stream, under the same mutex) uses too.  The tables stay in use by the kernels enqueued here after this
         // returns: one stream at a time per handle, as stated above.
         std::lock_guard<std::mutex> lk(ctx->mu);
-        ensure_g1_tab(ctx, 2 * total);
+        ensure_g1_tab(ctx, tab_v ? 0 : 2 * total);  // with the caller's tables: the split roots only
         Xyzz* bufs[2] = {(Xyzz*)scratch_v, (Xyzz*)data_v};
-        Xyzz* tab = (Xyzz*)ctx->d_tab;
+        Xyzz* tab = tab_v ? (Xyzz*)tab_v : (Xyzz*)ctx->d_tab;
         hipLaunchKernelGGL(k_g1_brp_xyzz, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, bufs[0],
                            (const Xyzz*)data_v, (u32)n, logn, total);
         Xyzz* res = bufs[enqueue_stages(ctx, bufs, tab, n, nbatch, inverse, st)];
@@ -620,6 +691,30 @@ void* kzgamd::fftg1_device(NttCtx* ctx, void* data_v, void* scratch_v, size_t n,
     } catch (const NttErr&) {
         return nullptr;
     }
+}
+
+void* kzgamd::fftg1_device(NttCtx* ctx, void* data_v, void* scratch_v, size_t n, size_t nbatch, int inverse, hipStream_t st,
+                           bool scale_inverse) {
+    return fftg1_enqueue(ctx, data_v, scratch_v, n, nbatch, inverse, st, scale_inverse, nullptr);
+}
+
+void* kzgamd::fftg1_device_tab(NttCtx* ctx, void* data_v, void* scratch_v, size_t n, size_t nbatch, int inverse, hipStream_t st,
+                               void* tab_v) {
+    if (!tab_v) return nullptr;
+    return fftg1_enqueue(ctx, data_v, scratch_v, n, nbatch, inverse, st, false, tab_v);
+}
+
+void kzgamd::g1_varmul_sum_device(NttCtx* ctx, void* out, void* prod, void* tab, const void* bases, size_t nbase,
+                                  const RootSplit* d_scalars, size_t nprod, size_t group, hipStream_t st) {
+    if (nprod == 0) return;
+    enqueue_varmul_sum(ctx, (Xyzz*)out, (Xyzz*)prod, (Xyzz*)tab, (const Xyzz*)bases, nbase, d_scalars, nprod, group, st);
+}
+
+void kzgamd::g1_jacobian_to_xyzz(void* d_xyzz, const void* d_p1, size_t count, hipStream_t st) {
+    if (count) hipLaunchKernelGGL(k_g1_load, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, st, (Xyzz*)d_xyzz, (const ff::Fp*)d_p1, 1u, 0, count);
+}
+void kzgamd::g1_xyzz_to_jacobian(void* d_p1, const void* d_xyzz, size_t count, hipStream_t st) {
+    if (count) hipLaunchKernelGGL(k_g1_store, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, st, (ff::Fp*)d_p1, (const Xyzz*)d_xyzz, count);
 }
 
 extern "C" int kzgamd_fft_g1_batch(void* vctx, blst_p1* out, const blst_p1* in, size_t n, size_t nbatch, int inverse) {

@@ -2472,6 +2472,10 @@ void msm_destroy(MsmContext* ctx) {
 }
 int msm_device(MsmContext* ctx) { return ctx->device; }
 bool msm_has_wide_table(MsmContext* ctx) { return ctx->fbw; }
+bool msm_wide_table_fits(size_t n, const Options* opt) {
+    bool glv = false;
+    return choose_wide_window(n, true, &glv, opt ? opt->table_budget_gb : -1) != 0;
+}
 bool msm_private_workspace(MsmContext* ctx, hipStream_t stream) {
     std::lock_guard<std::mutex> lk(ctx->mu);
     return &ctx->workspace_for(stream) != &ctx->ws;

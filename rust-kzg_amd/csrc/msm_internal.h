@@ -27,6 +27,8 @@ void msm_reset_points(MsmContext* ctx, const void* d_affpts, size_t n);
 void msm_enqueue(MsmContext* ctx, void* d_out, const void* d_scalars, size_t npoints, size_t nbatch, int mont,
                  hipStream_t stream, int out_mode, bool reserve_only = false, size_t nseg = 0);
 bool msm_has_wide_table(MsmContext* ctx);
+// whether a prepared handle over n points (all in G1) would get a wide table within opt's budget and the free HBM
+bool msm_wide_table_fits(size_t n, const Options* opt);
 // true when `stream` has a workspace of its own on this handle (created if there is room): its enqueues use no events
 // and may be captured into a graph
 bool msm_private_workspace(MsmContext* ctx, hipStream_t stream);

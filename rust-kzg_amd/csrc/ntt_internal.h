@@ -121,9 +121,30 @@ struct NttCtx {
 
 namespace kzgamd {
 struct Options;
+// one scalar (a root, n^-1, an FK20 coefficient) split for the two lanes of a G1 scalar multiplication: the 127-bit
+// magnitudes of its GLV halves (glv.hip.h) and their signs
+struct RootSplit {
+    ff::u32 k[2][4];
+    ff::u32 neg[2];
+    ff::u32 pad[2];
+};
+static_assert(sizeof(RootSplit) == 48, "RootSplit");
 // ntt.hip: what kzgamd_ntt_new_ex calls once the configuration is resolved (config.h); NULL on failure
 void* ntt_create(unsigned scale, const Options& opt);
 // fftg1.hip: G1 transforms of device-resident g1::Xyzz data, see there
 void* fftg1_device(NttCtx* ctx, void* data_xyzz, void* scratch_xyzz, size_t n, size_t nbatch, int inverse, hipStream_t st,
                    bool scale_inverse = true);
+// The same (never scaled) with per-lane tables of the caller's — 9 * n * nbatch g1::Xyzz — instead of the handle's:
+// callers with tables of their own may run beside each other and beside fft_g1 on one handle (generic FK20, fk20.hip).
+void* fftg1_device_tab(NttCtx* ctx, void* data_xyzz, void* scratch_xyzz, size_t n, size_t nbatch, int inverse, hipStream_t st,
+                       void* tab_xyzz);
+// fftg1.hip: out[g] = sum_{i < group} scalars[g * group + i] * bases[(g * group + i) % nbase], g < nprod / group — the
+// pointwise products of FK20, the scalars read per product from device memory, already split (one RootSplit each).
+// prod: nprod g1::Xyzz of workspace (unused when group == 1), tab: 18 * nprod g1::Xyzz; group: a power of two.  Zero
+// scalars and identity bases give the identity.  Enqueued on `st`, nothing synchronised.
+void g1_varmul_sum_device(NttCtx* ctx, void* out_xyzz, void* prod_xyzz, void* tab_xyzz, const void* bases_xyzz, size_t nbase,
+                          const RootSplit* d_scalars, size_t nprod, size_t group, hipStream_t st);
+// fftg1.hip: blst Jacobian <-> g1::Xyzz for `count` device-resident points, natural order
+void g1_jacobian_to_xyzz(void* d_xyzz, const void* d_p1, size_t count, hipStream_t st);
+void g1_xyzz_to_jacobian(void* d_p1, const void* d_xyzz, size_t count, hipStream_t st);
 }  // namespace kzgamd

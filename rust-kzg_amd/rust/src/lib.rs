@@ -56,6 +56,13 @@ extern "C" {
     fn das_fft_extension(ctx: *mut c_void, odds: *mut blst_fr, evens: *const blst_fr, half_n: usize) -> c_int;
     fn fft_g1(ctx: *mut c_void, out: *mut blst_p1, input: *const blst_p1, n: usize, inverse: c_int) -> c_int;
     fn kzgamd_g1_sum(out: *mut blst_p1, input: *const blst_p1, n: usize);
+
+    fn kzgamd_fk20_new(ntt: *mut c_void, g1_monomial: *const blst_p1, num_g1: usize, n2: usize, chunk_len: usize,
+                       cfg: *const KzgAmdConfig, err: *mut c_int) -> *mut c_void;
+    fn kzgamd_fk20_free(fk: *mut c_void);
+    fn kzgamd_fk20_da(fk: *mut c_void, out: *mut blst_p1, polys: *const blst_fr, n: usize, npoly: usize,
+                      optimized: c_int) -> c_int;
+    fn kzgamd_fk20_info(fk: *mut c_void, n2: *mut usize, chunk_len: *mut usize, form: *mut c_int) -> c_int;
 }
 
 fn check(err: RustError, what: &str) -> Result<(), String> {
@@ -293,6 +300,69 @@ impl GpuNtt {
 impl Drop for GpuNtt {
     fn drop(&mut self) {
         unsafe { kzgamd_ntt_free(self.ctx) }
+    }
+}
+
+/// Generic FK20 handle (`kzgamd_fk20_new`): `FK20SingleSettings` (chunk_len = 1) / `FK20MultiSettings` of the reference
+/// (blst/src/types/fk20_single_settings.rs, fk20_multi_settings.rs) over a `GpuNtt`.  Holds the NTT handle alive: the
+/// C handle keeps it by pointer and must be freed first (field order = drop order).
+pub struct GpuFk20 {
+    ctx: *mut c_void,
+    _ntt: std::sync::Arc<GpuNtt>,
+    n2: usize,
+    chunk_len: usize,
+}
+unsafe impl Send for GpuFk20 {}
+unsafe impl Sync for GpuFk20 {}
+
+impl GpuFk20 {
+    /// Errors carry the reference's messages (fk20_multi_settings.rs:61-73), in the reference's order.
+    pub fn new(ntt: std::sync::Arc<GpuNtt>, g1_monomial: &[blst_p1], n2: usize, chunk_len: usize,
+               cfg: Option<&KzgAmdConfig>) -> Result<Self, String> {
+        let mut err: c_int = 0;
+        let cfg_ptr = cfg.map_or(core::ptr::null(), |c| c as *const KzgAmdConfig);
+        let ctx = unsafe {
+            kzgamd_fk20_new(ntt.ctx, g1_monomial.as_ptr(), g1_monomial.len(), n2, chunk_len, cfg_ptr, &mut err)
+        };
+        if ctx.is_null() {
+            return Err(match err {
+                1 => String::from("n2 must be less than or equal to kzg settings max width"),
+                2 => String::from("n2 must be a power of two"),
+                3 => String::from("n2 must be greater than or equal to 2"),
+                4 => String::from("chunk_len must be greater or equal to n2 / 2"),
+                5 => String::from("chunk_len must be a power of two"),
+                6 => String::from("the setup has fewer than n2 / 2 - chunk_len G1 points"),
+                e => format!("kzgamd_fk20_new failed: {e}"),
+            });
+        }
+        Ok(Self { ctx, _ntt: ntt, n2, chunk_len })
+    }
+
+    /// `npoly` polynomials of n2 / 2 coefficients each -> npoly * n2 / chunk_len proofs; `optimized`: natural order
+    /// (`data_availability_optimized`), else bit-reversed per polynomial (`data_availability`).
+    pub fn data_availability(&self, polys: &[blst_fr], npoly: usize, optimized: bool) -> Result<Vec<blst_p1>, String> {
+        let n = self.n2 / 2;
+        if polys.len() != n * npoly {
+            return Err(String::from("n2 must be a power of two"));
+        }
+        let mut out = vec![blst_p1::default(); npoly * (self.n2 / self.chunk_len)];
+        match unsafe { kzgamd_fk20_da(self.ctx, out.as_mut_ptr(), polys.as_ptr(), n, npoly, optimized as c_int) } {
+            0 => Ok(out),
+            e => Err(format!("GPU FK20 failed: {e}")),
+        }
+    }
+
+    /// (n2, chunk_len, form): form 1 = a scalar multiplication per product, 2 = wide fixed-base table
+    pub fn info(&self) -> (usize, usize, i32) {
+        let (mut a, mut b, mut f) = (0usize, 0usize, 0 as c_int);
+        unsafe { kzgamd_fk20_info(self.ctx, &mut a, &mut b, &mut f) };
+        (a, b, f as i32)
+    }
+}
+
+impl Drop for GpuFk20 {
+    fn drop(&mut self) {
+        unsafe { kzgamd_fk20_free(self.ctx) }
     }
 }
 
