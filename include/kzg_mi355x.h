@@ -47,6 +47,8 @@ typedef struct { uint64_t l[4]; } blst_fr;
 typedef struct { uint64_t l[6]; } blst_fp;
 typedef struct { blst_fp x, y; } blst_p1_affine;     /* infinity = all-zero (blst/src/types/g1.rs:303-316) */
 typedef struct { blst_fp x, y, z; } blst_p1;          /* Jacobian; infinity = Z == 0 */
+typedef struct { blst_fp fp[2]; } blst_fp2;
+typedef struct { blst_fp2 x, y, z; } blst_p2;          /* Jacobian over Fp2; infinity = Z == 0 */
 
 /* sppark's error struct, returned by value (arkworks3-sppark-wlc/sppark/util/rusterror.h:15-27):
  * code 0 = ok; message is malloc'ed (caller frees) or NULL */
@@ -213,6 +215,54 @@ void *kzgamd_fk20_new(void *ntt, const blst_p1 *g1_monomial, size_t num_g1, size
 void kzgamd_fk20_free(void *fk);
 int kzgamd_fk20_da(void *fk, blst_p1 *out, const blst_fr *polys, size_t n, size_t npoly, int optimized);
 int kzgamd_fk20_info(void *fk, size_t *n2, size_t *chunk_len, int *form);
+/* Generic polynomial KZG, the proving and checking calls of KZGSettings (blst/src/types/kzg_settings.rs:138-277):
+ * commit_to_poly, compute_proof_single, compute_proof_multi, check_proof_single, check_proof_multi — for any setup
+ * [s^i]G, batched.  Scalars are Montgomery blst_fr, points Jacobian, results equal the reference's as group elements.
+ * The quotient of p by X^n - x^n is computed on the GPU (rust-kzg_amd/csrc/kzg.hip: one lane per residue class mod n
+ * when the call has lane_form_min such lanes, otherwise a scan over chunks of `chunk` steps — kzgamd_kzg_info gives
+ * both); a call makes one upload, one batched MSM and one download (per slice of pairs, when its workspace would take
+ * more than a share of the free HBM).
+ *
+ * kzgamd_kzg_new: `ntt` = kzgamd_ntt_new(scale); the coset of length n is x * <roots[max_width / n]>.  The handle keeps
+ * `ntt` by pointer and uses it in every call: free the KZG handle FIRST, the NTT handle after it.  g1_monomial = [s^i]G,
+ * i < num_g1, Jacobian, any points of the curve (the bases are tested for G1 at creation like prepare_msm's; cfg gives
+ * the table budget and the tuning of the MSM handle over them).  g2_monomial = [s^i]G2, i < num_g2, copied; NULL / 0: a
+ * handle that proves but does not check.  *err (may be NULL): 0 ok, 1 num_g1 == 0; negative = NULL argument (-1),
+ * malformed configuration (-2) or a device error.  Returns NULL on any error.  kzgamd_kzg_free gives every byte of HBM
+ * back.  Thread-safe like every handle (calls on one handle take turns; calls on `ntt` may run beside them).
+ *
+ * kzgamd_kzg_commit: out[b] = sum_i polys[b * len + i] * g1_monomial[i], b < npoly (commit_to_poly, :138-153).
+ * 0 ok, 1 len > num_g1 ("Polynomial is longer than secret g1"), -1 NULL argument, other negatives = device error.
+ * len = 0: identities; npoly = 0: ok, nothing written.
+ *
+ * kzgamd_kzg_open: every (polynomial, x) pair of npoly polynomials of len coefficients and nx points in one call:
+ * proofs[b * nx + k] = commitment to q with p_b = q (X^n - x_k^n) + r, deg r < n — compute_proof_single (:155-176) for
+ * n = 1, compute_proof_multi (:198-234) for n > 1.  0 ok, 2 len == 0 ("Polynomial must not be empty"), 3 n is zero or
+ * not a power of two, 1 len - n > num_g1, 4 ys != NULL and n > max width of `ntt`; negatives as above.  len <= n gives
+ * the identity (the reference's zero-length quotient, blst/src/types/poly.rs:167-170, 226-229).  npoly = 0 or nx = 0:
+ * ok, nothing written.  ys (may be NULL; an addition over the reference, whose callers evaluate with Poly::eval):
+ * ys[(b * nx + k) * n + i] = p_b(x_k w^i), w = roots[max_width / n] — from the remainder, by one batched transform.
+ *
+ * kzgamd_kzg_check: count tuples (commitment, proof, x, n values) in one call; ok[t] = the pairing equation holds:
+ *   n = 1 (check_proof_single, :178-196):  e(com - [y]g1_monomial[0], G2) == e(proof, [s]G2 - [x]G2)
+ *   n > 1 (check_proof_multi, :236-277):   e(com - [I(s)]G, G2) == e(proof, [s^n]G2 - [x^n]G2), I = the interpolation
+ *         polynomial of the values on the coset: ifft(ys), coefficient i times x^-i.
+ * The G1 sides run on the GPU for all tuples together, the G2 sides and one pairing per tuple on the host (as in the
+ * reference).  0 ok, 3 n is zero or not a power of two, 4 n > max width, 6 num_g2 <= n (or no G2 setup), 1 n > num_g1,
+ * 5 x == 0 in a tuple with n > 1 — the reference feeds inverse(0) into its arithmetic there (:253-261), which has no
+ * meaningful result; negatives as above.  count = 0: ok, nothing written.
+ *
+ * kzgamd_kzg_info: the setup sizes, the chunk length of the scan form and the number of lanes (pairs x n) from which
+ * the lane form is taken; any pointer may be NULL. */
+void *kzgamd_kzg_new(void *ntt, const blst_p1 *g1_monomial, size_t num_g1, const blst_p2 *g2_monomial, size_t num_g2,
+                     const KzgAmdConfig *cfg, int *err);
+void kzgamd_kzg_free(void *kz);
+int kzgamd_kzg_info(void *kz, size_t *num_g1, size_t *num_g2, size_t *chunk, size_t *lane_form_min);
+int kzgamd_kzg_commit(void *kz, blst_p1 *out, const blst_fr *polys, size_t len, size_t npoly);
+int kzgamd_kzg_open(void *kz, blst_p1 *proofs, blst_fr *ys, const blst_fr *polys, size_t len, size_t npoly,
+                    const blst_fr *xs, size_t nx, size_t n);
+int kzgamd_kzg_check(void *kz, bool *ok, const blst_p1 *commitments, const blst_p1 *proofs, const blst_fr *xs,
+                     const blst_fr *ys, size_t n, size_t count);
 /* The tile plan the NTT kernel runs for (kind, T) — host-only, no GPU needed (rust-kzg_amd/csrc/ntt_plan.h):
  * kind 0 = whole transform of 2^T <= 4096 points, 1 = first pass of a longer one, 2 = later pass; rounds[4*r..] =
  * {first stage, stages, barrier after, element bit}; tab[(r*1024 + thread)*4..] = {idxA, idxB, lds(idxA), lds(idxB)}.
@@ -236,9 +286,6 @@ typedef struct { uint8_t bytes[48]; } Bytes48;
 typedef struct { uint8_t bytes[BYTES_PER_BLOB]; } Blob;
 typedef Bytes48 KZGCommitment;
 typedef Bytes48 KZGProof;
-
-typedef struct { blst_fp fp[2]; } blst_fp2;
-typedef struct { blst_fp2 x, y, z; } blst_p2;          /* Jacobian over Fp2; infinity = Z == 0 */
 
 /* Same layout as the reference's CKZGSettings (kzg/src/eth/c_bindings.rs:55-108).  The host arrays are
  * owned by the library and freed by free_trusted_setup; the device-resident state (fixed-base MSM table)

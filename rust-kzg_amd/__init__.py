@@ -66,6 +66,7 @@ EXPORTS = [
     "kzgamd_ntt_new", "kzgamd_ntt_free", "ntt_fr", "das_fft_extension", "kzgamd_ntt_fr_device", "kzgamd_ntt_roots", "kzgamd_ntt_plan_dump", "kzgamd_ntt_das_plan_dump", "kzgamd_das_fft_extension_device",
     "fft_g1", "kzgamd_fft_g1_batch", "kzgamd_g1_sum",
     "kzgamd_fk20_new", "kzgamd_fk20_free", "kzgamd_fk20_da", "kzgamd_fk20_info",
+    "kzgamd_kzg_new", "kzgamd_kzg_free", "kzgamd_kzg_info", "kzgamd_kzg_commit", "kzgamd_kzg_open", "kzgamd_kzg_check",
     "load_trusted_setup", "load_trusted_setup_file", "free_trusted_setup", "blob_to_kzg_commitment",
     "compute_kzg_proof", "compute_blob_kzg_proof", "kzgamd_compute_blob_kzg_proof_batch", "compute_challenge",
     "bytes_to_kzg_commitment", "bytes_from_bls_field", "compute_cells_and_kzg_proofs",
@@ -218,6 +219,18 @@ def lib():
     L.kzgamd_fk20_da.argtypes = [vp, vp, vp, sz, sz, C.c_int]
     L.kzgamd_fk20_info.restype = C.c_int
     L.kzgamd_fk20_info.argtypes = [vp, C.POINTER(sz), C.POINTER(sz), C.POINTER(C.c_int)]
+    L.kzgamd_kzg_new.restype = vp
+    L.kzgamd_kzg_new.argtypes = [vp, vp, sz, vp, sz, cp, C.POINTER(C.c_int)]
+    L.kzgamd_kzg_free.restype = None
+    L.kzgamd_kzg_free.argtypes = [vp]
+    L.kzgamd_kzg_info.restype = C.c_int
+    L.kzgamd_kzg_info.argtypes = [vp, C.POINTER(sz), C.POINTER(sz), C.POINTER(sz), C.POINTER(sz)]
+    L.kzgamd_kzg_commit.restype = C.c_int
+    L.kzgamd_kzg_commit.argtypes = [vp, vp, vp, sz, sz]
+    L.kzgamd_kzg_open.restype = C.c_int
+    L.kzgamd_kzg_open.argtypes = [vp, vp, vp, vp, sz, sz, vp, sz, sz]
+    L.kzgamd_kzg_check.restype = C.c_int
+    L.kzgamd_kzg_check.argtypes = [vp, vp, vp, vp, vp, vp, sz, sz]
     L.kzgamd_ntt_roots.restype = C.c_int
     L.kzgamd_ntt_roots.argtypes = [vp, vp, vp, vp]
     sp = C.POINTER(CKZGSettings)
@@ -732,6 +745,99 @@ class FK20Settings:
     def close(self):
         if self.handle:
             lib().kzgamd_fk20_free(self.handle)
+            self.handle = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+KZG_ERRORS = {
+    1: "Polynomial is longer than secret g1",
+    2: "Polynomial must not be empty",
+    3: "n must be a power of two",
+    4: "Supplied list is longer than the available max width",
+    5: "x must not be zero: the interpolation on the coset divides by it",
+    6: "the setup has too few G2 points",
+}
+
+
+class PolyKZGSettings:
+    """The proving and checking calls of the reference's KZGSettings (blst/src/types/kzg_settings.rs:138-277) over an
+    FFTSettings handle and a monomial setup, batched; errors carry the reference's messages.  Keeps the FFTSettings
+    object alive; close() (or leaving the `with` block) frees the GPU state."""
+
+    def __init__(self, fft_settings, g1_monomial, num_g1, g2_monomial=None, num_g2=0, config=None):
+        self.fs = fft_settings
+        self.handle = None
+        err = C.c_int(0)
+        g2 = _addr(g2_monomial) if g2_monomial is not None and num_g2 else None
+        self.handle = lib().kzgamd_kzg_new(fft_settings.handle, _addr(g1_monomial) if num_g1 else None, num_g1, g2,
+                                           num_g2 if g2 else 0, _cfgp(config), C.byref(err))
+        self.err = err.value
+        if not self.handle:
+            raise KzgAmdError("the setup has no G1 points" if err.value == 1 else
+                              "kzgamd_kzg_new failed: %d (no GPU, NULL argument or bad configuration)" % err.value)
+
+    def _live(self):
+        if not self.handle:
+            raise KzgAmdError("PolyKZGSettings is closed")
+
+    @staticmethod
+    def _raise(what, rc):
+        raise KzgAmdError(KZG_ERRORS.get(rc, "%s: %d" % (what, rc)))
+
+    def commit(self, polys, length, npoly=1):
+        """commit_to_poly for npoly polynomials of `length` Montgomery coefficients each.  Returns (BlstP1 * npoly)."""
+        self._live()
+        out = (BlstP1 * max(1, npoly))()
+        rc = lib().kzgamd_kzg_commit(self.handle, out, _addr(polys) if npoly * length else None, length, npoly)
+        if rc != 0:
+            self._raise("kzgamd_kzg_commit", rc)
+        return out
+
+    def open(self, polys, length, npoly, xs, nx, n=1, want_ys=True):
+        """compute_proof_single (n = 1) / compute_proof_multi for every (polynomial, x) pair.  Returns
+        (proofs: BlstP1 * (npoly * nx), ys: BlstFr * (npoly * nx * n) or None); ys[(b * nx + k) * n + i] = p_b(x_k w^i)."""
+        self._live()
+        pairs = npoly * nx
+        proofs = (BlstP1 * max(1, pairs))()
+        ys = (BlstFr * max(1, pairs * n))() if want_ys else None
+        rc = lib().kzgamd_kzg_open(self.handle, proofs, ys, _addr(polys) if npoly * length else None, length, npoly,
+                                   _addr(xs) if nx else None, nx, n)
+        if rc != 0:
+            self._raise("kzgamd_kzg_open", rc)
+        return proofs, ys
+
+    def check(self, commitments, proofs, xs, ys, n=1, count=1):
+        """check_proof_single (n = 1) / check_proof_multi for `count` tuples.  Returns a list of count booleans."""
+        self._live()
+        ok = (C.c_bool * max(1, count))()
+        rc = lib().kzgamd_kzg_check(self.handle, ok, _addr(commitments), _addr(proofs), _addr(xs), _addr(ys), n, count)
+        if rc != 0:
+            self._raise("kzgamd_kzg_check", rc)
+        return [bool(ok[i]) for i in range(count)]
+
+    def info(self):
+        """(num_g1, num_g2, chunk, lane_form_min): the setup sizes, the chunk length of the scan form of the quotient
+        kernels and the number of lanes (pairs x n) from which the lane form is taken"""
+        self._live()
+        v = [C.c_size_t(0) for _ in range(4)]
+        if lib().kzgamd_kzg_info(self.handle, *[C.byref(x) for x in v]) != 0:
+            raise KzgAmdError("kzgamd_kzg_info failed")
+        return tuple(x.value for x in v)
+
+    def close(self):
+        if self.handle:
+            lib().kzgamd_kzg_free(self.handle)
             self.handle = None
 
     def __enter__(self):

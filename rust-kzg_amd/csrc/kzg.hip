@@ -1,0 +1,636 @@
+// Generic polynomial KZG: the proving and checking calls of the reference's KZGSettings
+// (blst/src/types/kzg_settings.rs:138-277: commit_to_poly, compute_proof_single, compute_proof_multi, check_proof_single,
+// check_proof_multi) for any setup [s^i]G, batched: npoly polynomials x nx points per open call, count tuples per check.
+//
+// A proof is the commitment to the quotient q of p = q (X^n - c) + r, c = x^n, deg r < n.  With h_j = p_j + c h_{j+n}
+// (h_j = 0 for j >= len) the quotient is q_j = h_{j+n} and the remainder r_j = h_j, j < n: n independent first-order
+// recurrences with the SAME multiplier c — one per residue rho = j mod n, the sequence a_t = p_{rho + t n}, t < T =
+// ceil(len / n), run from the top.  Two kernel forms, taken by shape (kzgamd_kzg_info gives the threshold):
+//   lane form     one lane per (pair, rho), serial over t; neighbouring lanes hold neighbouring rho, so every step is a
+//                 coalesced 32-byte-per-lane load and store.  Taken when the call has LANE_FORM_MIN such lanes or more.
+//   chunked scan  one lane per (pair, rho, chunk m of CHUNK consecutive t).  The lane runs its chunk from a zero carry: S_m.
+//                 The true value at the base of chunk m is H_m = S_m + C H_{m+1}, C = c^CHUNK — the same recurrence one
+//                 level up — solved inside a wave by a log-step suffix scan over lanes with the powers C^(2^k), k < 6,
+//                 and across waves through one summary per wave in global memory: k_kzg_chunk<false> writes the S_m
+//                 and the summaries, k_kzg_carry turns the summaries into the true values at the wave bases (the same
+//                 scan once more, a lane per wave, with the powers of C^64), k_kzg_chunk<true> scans the S_m again from
+//                 them and replays every chunk from its true incoming carry, writing q and r.  A sequence of up to 64
+//                 chunks takes the last launch alone, in a group of 1, 2, .. 64 lanes of a wave.
+//                 A dependent multiplication is ~1.1 us on a wave that has its SIMD to itself (measured, profiles/NOTES.md):
+//                 the depth of the three launches — CHUNK + 6, 6 and 6 + CHUNK multiplications — is what they cost.
+// Both write q pair-major in Montgomery form, what msm_enqueue(mont = 1) reads, and r for the evaluations: ys = forward
+// transform of r_j x^j.  Wave-local exchange and global memory between launches only: no workgroup barrier in this file.
+// Everything between the upload of the coefficients and the download of the proofs is enqueued on the handle's one
+// stream; a call holds the handle's lock and synchronises before it returns.
+//
+// check: the G1 side com - [I(s)]G for all tuples on the GPU (inverse transform of the ys, x^-i by one inversion per
+// tuple, one MSM per tuple over the first n setup points, the subtraction); the G2 side and one pairing per tuple on
+// the host (host_pairing.h), as in the reference.
+#include <hip/hip_runtime.h>
+#include <stddef.h>
+#include <stdint.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include <mutex>
+#include <string>
+#include <vector>
+
+#include "../../include/kzg_mi355x.h"
+#include "config.h"
+#include "device_guard.h"
+#include "ff.hip.h"
+#include "fr29.hip.h"
+#include "g1_28.hip.h"
+#include "host_fp64.h"
+#include "host_pairing.h"
+#include "msm_internal.h"
+#include "ntt_internal.h"
+
+using ff::Fr;
+using ff::u32;
+using g1::Xyzz;
+
+namespace {
+
+constexpr int CHUNK = 16;                   // consecutive steps of a sequence per lane of the chunked form
+constexpr size_t LANE_FORM_MIN = 16384;     // lanes (pairs x n) from which the lane form is taken: a wave per CU
+constexpr int PW = 16;                      // per x: c, then C^(2^k), k = 0 .. 11, C = c^CHUNK (C^64 and its powers chain the waves)
+constexpr int NPOW = 12;
+
+__device__ __forceinline__ Fr fr_mul(const Fr& a, const Fr& b) { return fr29::mul_blst(a, b); }
+
+// a^e for a small public exponent
+__device__ __forceinline__ Fr fr_pow(const Fr& a, size_t e) {
+    Fr r = Fr::one(), b = a;
+    while (e) {
+        if (e & 1) r = fr_mul(r, b);
+        e >>= 1;
+        if (e) b = fr_mul(b, b);
+    }
+    return r;
+}
+
+__device__ __forceinline__ Fr shfl_down(const Fr& a, int d) {
+    Fr r;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) r.v[i] = __shfl_down(a.v[i], d, 64);
+    return r;
+}
+
+// per x: pw[0] = c = x^n, pw[1 + k] = (c^CHUNK)^(2^k), k < NPOW
+__global__ void __launch_bounds__(64) k_kzg_pows(Fr* __restrict__ pw, const Fr* __restrict__ xs, size_t n, size_t nx) {
+    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= nx) return;
+    Fr c = xs[t];
+    for (size_t m = 1; m < n; m <<= 1) c = fr_mul(c, c);
+    pw[t * PW] = c;
+    Fr C = fr_pow(c, CHUNK);
+    for (int k = 0; k < NPOW; ++k) {
+        pw[t * PW + 1 + k] = C;
+        C = fr_mul(C, C);
+    }
+}
+
+struct QuotShape {
+    size_t len, n, nx, L;    // L = len - n: the quotient's length (the MSMs' stride); only called with len > n
+    size_t pair0, npairs;    // the pairs of this pass: pair = poly * nx + x index
+    size_t M;                // chunks per sequence, ceil(ceil(len / n) / CHUNK)
+    u32 gw, wv;              // lanes of a wave per sequence (a power of two <= 64), waves per sequence (gw == 64 if > 1)
+};
+
+// the lane form: thread = (pair, rho)
+__global__ void __launch_bounds__(256) k_kzg_lanes(Fr* __restrict__ q, Fr* __restrict__ r, const Fr* __restrict__ polys,
+                                                   const Fr* __restrict__ pw, QuotShape s) {
+    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= s.npairs * s.n) return;
+    const size_t rho = t % s.n, pl = t / s.n, pair = s.pair0 + pl;
+    const Fr* p = polys + (pair / s.nx) * s.len;
+    const Fr c = pw[(pair % s.nx) * PW];
+    Fr* qo = q + pl * s.L;
+    Fr acc = Fr::zero();
+    if (rho < s.len) {
+        for (size_t j = rho + (s.len - 1 - rho) / s.n * s.n;; j -= s.n) {
+            acc = ff::add(p[j], fr_mul(c, acc));
+            if (j < s.n) break;
+            qo[j - s.n] = acc;
+        }
+    }
+    r[pl * s.n + rho] = acc;
+}
+
+// the chunked form: thread = (sequence = (pair, rho), chunk m), gw * wv slots per sequence.
+// REPLAY == false (wv > 1 only): S_m to local[thread], the summary of the wave, sum_d C^d S_{64 w + d}, to sums[seq * wv + w].
+// REPLAY == true: sums holds the true values at the wave bases (k_kzg_carry) and local the S_m when wv > 1 (a sequence
+// within one wave computes them here); q and r are written.
+template <bool REPLAY>
+__global__ void __launch_bounds__(256) k_kzg_chunk(Fr* __restrict__ q, Fr* __restrict__ r, Fr* __restrict__ sums, Fr* __restrict__ local,
+                                                   const Fr* __restrict__ polys, const Fr* __restrict__ pw, QuotShape s) {
+    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const size_t slots = (size_t)s.gw * s.wv;
+    const size_t seq = t / slots, m = t % slots;
+    const bool live = seq < s.npairs * s.n && m < s.M;  // dead lanes carry zeros through the scan: no lane leaves early
+    const size_t rho = live ? seq % s.n : 0, pl = live ? seq / s.n : 0, pair = s.pair0 + pl;
+    const Fr* p = polys + (pair / s.nx) * s.len;
+    const Fr* mypw = pw + (pair % s.nx) * PW;
+    const Fr c = mypw[0];
+    const size_t t0 = m * CHUNK;
+    // the chunk from a zero carry
+    Fr S = Fr::zero();
+    if (REPLAY && s.wv > 1) {
+        S = local[t];
+    } else if (live) {
+        for (int i = CHUNK - 1; i >= 0; --i) {
+            const size_t j = rho + (t0 + i) * s.n;
+            if (j < s.len) S = ff::add(p[j], fr_mul(c, S));
+        }
+    }
+    if (!REPLAY) local[t] = S;
+    const u32 lg = (u32)(m & (s.gw - 1));        // lane within the group
+    const size_t w = m / 64;                      // wave within the sequence (0 when gw < 64)
+    const bool more = REPLAY && live && s.wv > 1 && w + 1 < s.wv;  // a wave of this sequence above this one
+    Fr above = Fr::zero();                        // true value at the base of the next wave
+    if (more) above = sums[seq * s.wv + w + 1];
+    if (more && lg == 63) S = ff::add(S, fr_mul(mypw[1], above));
+    // suffix scan over the group: H_m = sum_{d >= 0} C^d S_{m + d}
+    Fr H = S;
+    for (u32 k = 0; ((u32)1 << k) < s.gw; ++k) {
+        const Fr up = shfl_down(H, 1 << k);
+        if (lg + ((u32)1 << k) < s.gw) H = ff::add(H, fr_mul(mypw[1 + k], up));
+    }
+    if (!REPLAY) {
+        if (live && lg == 0) sums[seq * s.wv + w] = H;
+        return;
+    }
+    Fr acc = shfl_down(H, 1);                     // H_{m+1}: the carry into this chunk
+    if (lg + 1 >= s.gw) acc = above;
+    if (!live) return;
+    // the chunk again, from its true carry
+    Fr* qo = q + pl * s.L;
+    for (int i = CHUNK - 1; i >= 0; --i) {
+        const size_t j = rho + (t0 + i) * s.n;
+        if (j >= s.len) continue;
+        acc = ff::add(p[j], fr_mul(c, acc));
+        if (j >= s.n) qo[j - s.n] = acc;
+        else r[pl * s.n + rho] = acc;
+    }
+}
+
+// summaries of the waves of a sequence -> true values at the wave bases, G_w = W_w + C^64 G_{w+1}: a wave per sequence,
+// a lane per summary, blocks of 64 summaries from the top, each by the suffix scan of k_kzg_chunk with the powers of C^64
+__global__ void __launch_bounds__(64) k_kzg_carry(Fr* __restrict__ sums, const Fr* __restrict__ pw, QuotShape s) {
+    const size_t seq = blockIdx.x;  // < npairs * n
+    const u32 lane = threadIdx.x;
+    const Fr* mypw = pw + ((s.pair0 + seq / s.n) % s.nx) * PW + 7;  // (C^64)^(2^k), k = 0 .. 5
+    Fr* g = sums + seq * s.wv;
+    Fr above = Fr::zero();
+    for (size_t blk = (s.wv + 63) / 64; blk-- > 0;) {
+        const size_t w = blk * 64 + lane;
+        Fr H = w < s.wv ? g[w] : Fr::zero();
+        if (lane == 63) H = ff::add(H, fr_mul(mypw[0], above));
+        for (u32 k = 0; k < 6; ++k) {
+            const Fr up = shfl_down(H, 1 << k);
+            if (lane + ((u32)1 << k) < 64) H = ff::add(H, fr_mul(mypw[k], up));
+        }
+        if (w < s.wv) g[w] = H;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) above.v[i] = __shfl(H.v[i], 0, 64);
+    }
+}
+
+// r_j *= x^j, j < n, for every pair: the forward transform of the result is p(x w^i)
+__global__ void __launch_bounds__(256) k_kzg_twist(Fr* __restrict__ r, const Fr* __restrict__ xs, size_t n, size_t nx, size_t pair0,
+                                                   size_t total) {
+    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= total) return;
+    const size_t j = t % n;
+    if (j == 0) return;
+    r[t] = fr_mul(r[t], fr_pow(xs[(pair0 + t / n) % nx], j));
+}
+// xs[t] = 1 / xs[t]
+__global__ void __launch_bounds__(64) k_kzg_invert(Fr* __restrict__ xs, size_t count) {
+    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t < count) xs[t] = ff::inverse_bgcd(xs[t]);
+}
+// interp[tuple][i] *= (1 / x_tuple)^i
+__global__ void __launch_bounds__(256) k_kzg_unscale(Fr* __restrict__ v, const Fr* __restrict__ xinv, size_t n, size_t total) {
+    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= total) return;
+    const size_t i = t % n;
+    if (i == 0) return;
+    v[t] = fr_mul(v[t], fr_pow(xinv[t / n], i));
+}
+// out = a - b, blst Jacobian points
+__global__ void __launch_bounds__(64) k_kzg_g1_sub(ff::Fp* __restrict__ out, const ff::Fp* __restrict__ a, const ff::Fp* __restrict__ b,
+                                                   size_t count) {
+    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= count) return;
+    auto load = [](const ff::Fp* src) {
+        Xyzz p;
+        if (src[2].is_zero()) {
+            g1::set_inf(p);
+        } else {
+            const fp28::Fe z = fp28::from_blst(src[2]);
+            p.x = fp28::from_blst(src[0]);
+            p.y = fp28::from_blst(src[1]);
+            p.zz = fp28::sqr(z);
+            p.zzz = fp28::mul(p.zz, z);
+        }
+        return p;
+    };
+    Xyzz A = load(a + 3 * t), B = load(b + 3 * t);
+    if (!g1::is_inf(B)) B.y = fp28::neg<8>(B.y);
+    g1::dadd(A, B);
+    g1::to_blst_jacobian(out + 3 * t, A);
+}
+
+struct KzErr {
+    hipError_t e;
+};
+#define KZ_TRY(x)                              \
+    do {                                       \
+        hipError_t _e = (x);                   \
+        if (_e != hipSuccess) throw KzErr{_e}; \
+    } while (0)
+
+struct DevBuf {
+    void* p = nullptr;
+    size_t cap = 0;
+    void ensure(size_t bytes) {
+        if (bytes <= cap) return;
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        cap = 0;
+        KZ_TRY(hipMalloc(&p, bytes));
+        cap = bytes;
+    }
+    void drop() {
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        cap = 0;
+    }
+    template <class T>
+    T* as() const {
+        return (T*)p;
+    }
+};
+
+struct KzgCtx {
+    NttCtx* ntt = nullptr;
+    int device = 0;
+    size_t num_g1 = 0, num_g2 = 0;
+    std::vector<kzgamd::pairing::G2Jac> g2;
+    std::mutex mu;
+    hipStream_t st = nullptr;
+    kzgamd::MsmContext* msm = nullptr;
+    // workspace, grown as calls need it
+    DevBuf polys, xs, pw, q, r, r2, sums, local, out, pts;
+
+    ~KzgCtx() {
+        for (DevBuf* b : {&polys, &xs, &pw, &q, &r, &r2, &sums, &local, &out, &pts}) b->drop();
+        if (msm) kzgamd::msm_destroy(msm);
+        if (st) (void)hipStreamDestroy(st);
+    }
+};
+
+inline unsigned blocks(size_t total, unsigned per = 256) { return (unsigned)((total + per - 1) / per); }
+
+// nbatch MSMs of npoints scalars (Montgomery, stride npoints) over the first setup points, Jacobian out, on the stream
+void msm_on_stream(KzgCtx* kz, void* d_out, const void* d_scalars, size_t npoints, size_t nbatch) {
+    kzgamd::msm_lock(kz->msm);
+    try {
+        kzgamd::msm_enqueue(kz->msm, d_out, d_scalars, npoints, nbatch, 1, kz->st, kzgamd::OUT_JACOBIAN);
+    } catch (...) {
+        kzgamd::msm_unlock(kz->msm);
+        throw KzErr{hipErrorUnknown};
+    }
+    kzgamd::msm_unlock(kz->msm);
+}
+
+// the Jacobian setup points as blst affine points (Montgomery's trick over the Z coordinates; the identity as (0, 0))
+std::vector<ff::Fp> to_affine(const blst_p1* pts, size_t total) {
+    const ff::Fp* jac = reinterpret_cast<const ff::Fp*>(pts);
+    std::vector<ff::Fp> aff(2 * total), pre(total);
+    ff::Fp run = ff::Fp::one();
+    for (size_t i = 0; i < total; ++i) {
+        pre[i] = run;
+        if (!jac[3 * i + 2].is_zero()) run = hfp::mul(run, jac[3 * i + 2]);
+    }
+    ff::Fp inv = ff::inverse_bgcd(run);
+    for (size_t i = total; i-- > 0;) {
+        const ff::Fp* P = &jac[3 * i];
+        if (P[2].is_zero()) {
+            aff[2 * i] = aff[2 * i + 1] = ff::Fp::zero();
+            continue;
+        }
+        const ff::Fp zi = hfp::mul(inv, pre[i]), zi2 = hfp::sqr(zi);
+        inv = hfp::mul(inv, P[2]);
+        aff[2 * i] = hfp::mul(P[0], zi2);
+        aff[2 * i + 1] = hfp::mul(P[1], hfp::mul(zi2, zi));
+    }
+    return aff;
+}
+
+// the quotients and remainders of the pairs [pair0, pair0 + npairs) into kz->q (stride len - n) and kz->r (stride n)
+void enqueue_quotients(KzgCtx* kz, size_t len, size_t n, size_t nx, size_t pair0, size_t npairs) {
+    QuotShape s;
+    s.len = len;
+    s.n = n;
+    s.nx = nx;
+    s.L = len - n;
+    s.pair0 = pair0;
+    s.npairs = npairs;
+    const size_t T = (len + n - 1) / n, seqs = npairs * n;
+    s.M = (T + CHUNK - 1) / CHUNK;
+    s.gw = 1;
+    while (s.gw < 64 && s.gw < s.M) s.gw <<= 1;
+    s.wv = (u32)((s.M + 63) / 64);
+    Fr *q = kz->q.as<Fr>(), *r = kz->r.as<Fr>();
+    const Fr *p = kz->polys.as<Fr>(), *pw = kz->pw.as<Fr>();
+    if (seqs >= LANE_FORM_MIN) {
+        hipLaunchKernelGGL(k_kzg_lanes, dim3(blocks(seqs)), dim3(256), 0, kz->st, q, r, p, pw, s);
+    } else {
+        const size_t threads = seqs * s.gw * s.wv;
+        Fr *sums = nullptr, *local = nullptr;
+        if (s.wv > 1) {
+            kz->sums.ensure(seqs * s.wv * sizeof(Fr));
+            kz->local.ensure((size_t)blocks(threads) * 256 * sizeof(Fr));
+            sums = kz->sums.as<Fr>();
+            local = kz->local.as<Fr>();
+            hipLaunchKernelGGL(k_kzg_chunk<false>, dim3(blocks(threads)), dim3(256), 0, kz->st, q, r, sums, local, p, pw, s);
+            hipLaunchKernelGGL(k_kzg_carry, dim3((unsigned)seqs), dim3(64), 0, kz->st, sums, pw, s);
+        }
+        hipLaunchKernelGGL(k_kzg_chunk<true>, dim3(blocks(threads)), dim3(256), 0, kz->st, q, r, sums, local, p, pw, s);
+    }
+    KZ_TRY(hipGetLastError());
+}
+
+bool g1_affine(const blst_p1* p, ff::Fp& x, ff::Fp& y) {  // returns "is the identity"
+    const ff::Fp* P = reinterpret_cast<const ff::Fp*>(p);
+    if (P[2].is_zero()) return true;
+    const ff::Fp zi = ff::inverse_bgcd(P[2]), zi2 = hfp::sqr(zi);
+    x = hfp::mul(P[0], zi2);
+    y = hfp::mul(P[1], hfp::mul(zi2, zi));
+    return false;
+}
+
+}  // namespace
+
+extern "C" void* kzgamd_kzg_new(void* vntt, const blst_p1* g1_monomial, size_t num_g1, const blst_p2* g2_monomial, size_t num_g2,
+                                const KzgAmdConfig* cfg, int* err) {
+    int dummy;
+    if (!err) err = &dummy;
+    *err = 0;
+    NttCtx* ntt = (NttCtx*)vntt;
+    if (num_g1 == 0) {
+        *err = 1;
+        return nullptr;
+    }
+    if (!ntt || !g1_monomial || (num_g2 && !g2_monomial)) {
+        *err = -1;
+        return nullptr;
+    }
+    kzgamd::Options opt;
+    std::string msg;
+    if (!kzgamd::Options::resolve(opt, cfg, &msg)) {
+        fprintf(stderr, "kzg_mi355x: kzgamd_kzg_new: %s\n", msg.c_str());
+        *err = -2;
+        return nullptr;
+    }
+    opt.device = ntt->device;  // the handle lives where its NTT handle lives
+    auto* kz = new KzgCtx();
+    try {
+        kzgamd::DeviceGuard on_device(ntt->device);
+        KZ_TRY(on_device.err);
+        kz->ntt = ntt;
+        kz->device = ntt->device;
+        kz->num_g1 = num_g1;
+        kz->num_g2 = g2_monomial ? num_g2 : 0;
+        kz->g2.resize(kz->num_g2);
+        if (kz->num_g2) memcpy(kz->g2.data(), g2_monomial, kz->num_g2 * sizeof(blst_p2));
+        KZ_TRY(hipStreamCreateWithFlags(&kz->st, hipStreamNonBlocking));
+        const std::vector<ff::Fp> aff = to_affine(g1_monomial, num_g1);
+        kz->msm = kzgamd::msm_create(aff.data(), num_g1, false, true, false, kzgamd::G1_CHECK, &opt);
+    } catch (const KzErr& e) {
+        *err = -(int)e.e - 100;
+        kzgamd::DeviceGuard on_device(ntt->device);
+        delete kz;
+        return nullptr;
+    } catch (...) {
+        *err = -4;
+        kzgamd::DeviceGuard on_device(ntt->device);
+        delete kz;
+        return nullptr;
+    }
+    return kz;
+}
+
+extern "C" void kzgamd_kzg_free(void* vkz) {
+    KzgCtx* kz = (KzgCtx*)vkz;
+    if (!kz) return;
+    kzgamd::DeviceGuard on_device(kz->device);
+    delete kz;
+}
+
+extern "C" int kzgamd_kzg_info(void* vkz, size_t* num_g1, size_t* num_g2, size_t* chunk, size_t* lane_form_min) {
+    KzgCtx* kz = (KzgCtx*)vkz;
+    if (!kz) return -1;
+    if (num_g1) *num_g1 = kz->num_g1;
+    if (num_g2) *num_g2 = kz->num_g2;
+    if (chunk) *chunk = CHUNK;
+    if (lane_form_min) *lane_form_min = LANE_FORM_MIN;
+    return 0;
+}
+
+extern "C" int kzgamd_kzg_commit(void* vkz, blst_p1* out, const blst_fr* polys, size_t len, size_t npoly) {
+    KzgCtx* kz = (KzgCtx*)vkz;
+    if (!kz) return -1;
+    if (len > kz->num_g1) return 1;
+    if (npoly == 0) return 0;
+    if (!out || (len && !polys)) return -1;
+    if (len == 0) {
+        memset(out, 0, npoly * sizeof(blst_p1));
+        return 0;
+    }
+    std::lock_guard<std::mutex> lk(kz->mu);
+    int rc = 0;
+    try {
+        kzgamd::DeviceGuard on_device(kz->device);
+        KZ_TRY(on_device.err);
+        kz->polys.ensure(npoly * len * sizeof(Fr));
+        kz->out.ensure(npoly * sizeof(blst_p1));
+        try {
+            KZ_TRY(hipMemcpyAsync(kz->polys.p, polys, npoly * len * sizeof(Fr), hipMemcpyHostToDevice, kz->st));
+            msm_on_stream(kz, kz->out.p, kz->polys.p, len, npoly);
+            KZ_TRY(hipMemcpyAsync(out, kz->out.p, npoly * sizeof(blst_p1), hipMemcpyDeviceToHost, kz->st));
+        } catch (...) {
+            (void)hipStreamSynchronize(kz->st);  // a copy into the caller's buffer may be in flight
+            throw;
+        }
+        KZ_TRY(hipStreamSynchronize(kz->st));
+    } catch (const KzErr& e) {
+        rc = -(int)e.e - 100;
+    } catch (...) {
+        rc = -2;
+    }
+    return rc;
+}
+
+extern "C" int kzgamd_kzg_open(void* vkz, blst_p1* proofs, blst_fr* ys, const blst_fr* polys, size_t len, size_t npoly,
+                               const blst_fr* xs, size_t nx, size_t n) {
+    KzgCtx* kz = (KzgCtx*)vkz;
+    if (!kz) return -1;
+    // the reference's checks in the reference's order (kzg_settings.rs:155-158, 198-205, 138-141)
+    if (len == 0) return 2;
+    if (n == 0 || (n & (n - 1))) return 3;
+    if (len > n && len - n > kz->num_g1) return 1;
+    if (ys && n > kz->ntt->W) return 4;
+    const size_t npairs = npoly * nx;
+    if (npairs == 0) return 0;
+    if (!proofs || !polys || !xs) return -1;
+    std::lock_guard<std::mutex> lk(kz->mu);
+    int rc = 0;
+    try {
+        kzgamd::DeviceGuard on_device(kz->device);
+        KZ_TRY(on_device.err);
+        // the workspace of a pass (quotients, remainders, the MSM's digits beside them) stays within a share of the free
+        // HBM: a larger call runs in slices of pairs
+        size_t free_b = 0, total_b = 0;
+        KZ_TRY(hipMemGetInfo(&free_b, &total_b));
+        const size_t per_pair = (len + 2 * n) * sizeof(Fr) + sizeof(blst_p1);
+        size_t per = (free_b + kz->q.cap + kz->r.cap + kz->r2.cap) / 8 / per_pair;
+        if (per == 0) per = 1;
+        if (per > npairs) per = npairs;
+        const size_t L = len > n ? len - n : 0;
+        kz->polys.ensure(npoly * len * sizeof(Fr));
+        kz->xs.ensure(nx * sizeof(Fr));
+        kz->pw.ensure(nx * PW * sizeof(Fr));
+        kz->q.ensure(per * L * sizeof(Fr));
+        kz->r.ensure(per * n * sizeof(Fr));
+        if (ys && n > 1) kz->r2.ensure(per * n * sizeof(Fr));
+        kz->out.ensure(per * sizeof(blst_p1));
+        hipStream_t st = kz->st;
+        try {
+            KZ_TRY(hipMemcpyAsync(kz->polys.p, polys, npoly * len * sizeof(Fr), hipMemcpyHostToDevice, st));
+            KZ_TRY(hipMemcpyAsync(kz->xs.p, xs, nx * sizeof(Fr), hipMemcpyHostToDevice, st));
+            hipLaunchKernelGGL(k_kzg_pows, dim3(blocks(nx, 64)), dim3(64), 0, st, kz->pw.as<Fr>(), kz->xs.as<Fr>(), n, nx);
+            for (size_t done = 0; done < npairs; done += per) {
+                const size_t cnt = npairs - done < per ? npairs - done : per;
+                if (L == 0) {
+                    // len <= n: the reference's zero-length quotient (poly.rs:167-170, 226-229); r = p, zero-extended
+                    KZ_TRY(hipMemsetAsync(kz->out.p, 0, cnt * sizeof(blst_p1), st));
+                    if (ys) {
+                        KZ_TRY(hipMemsetAsync(kz->r.p, 0, cnt * n * sizeof(Fr), st));
+                        for (size_t i = 0; i < cnt; ++i)
+                            KZ_TRY(hipMemcpyAsync(kz->r.as<Fr>() + i * n, kz->polys.as<Fr>() + (done + i) / nx * len, len * sizeof(Fr),
+                                                  hipMemcpyDeviceToDevice, st));
+                    }
+                } else {
+                    enqueue_quotients(kz, len, n, nx, done, cnt);
+                    msm_on_stream(kz, kz->out.p, kz->q.p, L, cnt);
+                }
+                KZ_TRY(hipMemcpyAsync(proofs + done, kz->out.p, cnt * sizeof(blst_p1), hipMemcpyDeviceToHost, st));
+                if (!ys) continue;
+                const Fr* vals = kz->r.as<Fr>();
+                if (n > 1) {
+                    hipLaunchKernelGGL(k_kzg_twist, dim3(blocks(cnt * n)), dim3(256), 0, st, kz->r.as<Fr>(), kz->xs.as<Fr>(), n, nx,
+                                       done, cnt * n);
+                    if (kzgamd_ntt_fr_device(kz->ntt, kz->r2.p, kz->r.p, n, cnt, 0, st) != 0) throw KzErr{hipErrorUnknown};
+                    vals = kz->r2.as<Fr>();
+                }
+                KZ_TRY(hipGetLastError());
+                KZ_TRY(hipMemcpyAsync(ys + done * n, vals, cnt * n * sizeof(Fr), hipMemcpyDeviceToHost, st));
+            }
+        } catch (...) {
+            (void)hipStreamSynchronize(st);  // a copy into the caller's buffer may be in flight
+            throw;
+        }
+        KZ_TRY(hipStreamSynchronize(st));
+    } catch (const KzErr& e) {
+        rc = -(int)e.e - 100;
+    } catch (...) {
+        rc = -2;
+    }
+    return rc;
+}
+
+extern "C" int kzgamd_kzg_check(void* vkz, bool* ok, const blst_p1* commitments, const blst_p1* proofs, const blst_fr* xs,
+                                const blst_fr* ys, size_t n, size_t count) {
+    namespace pr = kzgamd::pairing;
+    KzgCtx* kz = (KzgCtx*)vkz;
+    if (!kz) return -1;
+    if (n == 0 || (n & (n - 1))) return 3;
+    if (n > kz->ntt->W) return 4;
+    if (kz->num_g2 <= n) return 6;
+    if (n > kz->num_g1) return 1;
+    if (count == 0) return 0;
+    if (!ok || !commitments || !proofs || !xs || !ys) return -1;
+    const Fr* hx = reinterpret_cast<const Fr*>(xs);
+    if (n > 1)
+        for (size_t i = 0; i < count; ++i)
+            if (hx[i].is_zero()) return 5;
+    std::vector<blst_p1> lhs(count);
+    int rc = 0;
+    {
+        std::lock_guard<std::mutex> lk(kz->mu);
+        try {
+            kzgamd::DeviceGuard on_device(kz->device);
+            KZ_TRY(on_device.err);
+            kz->r.ensure(count * n * sizeof(Fr));
+            kz->r2.ensure(count * n * sizeof(Fr));
+            kz->xs.ensure(count * sizeof(Fr));
+            kz->out.ensure(count * sizeof(blst_p1));
+            kz->pts.ensure(2 * count * sizeof(blst_p1));
+            hipStream_t st = kz->st;
+            ff::Fp* com = kz->pts.as<ff::Fp>();
+            ff::Fp* dif = com + 3 * count;
+            try {
+                KZ_TRY(hipMemcpyAsync(kz->r.p, ys, count * n * sizeof(Fr), hipMemcpyHostToDevice, st));
+                KZ_TRY(hipMemcpyAsync(com, commitments, count * sizeof(blst_p1), hipMemcpyHostToDevice, st));
+                const Fr* interp = kz->r.as<Fr>();
+                if (n > 1) {
+                    // interp = ifft(ys); interp[i] *= x^-i (kzg_settings.rs:248-258)
+                    KZ_TRY(hipMemcpyAsync(kz->xs.p, xs, count * sizeof(Fr), hipMemcpyHostToDevice, st));
+                    if (kzgamd_ntt_fr_device(kz->ntt, kz->r2.p, kz->r.p, n, count, 1, st) != 0) throw KzErr{hipErrorUnknown};
+                    hipLaunchKernelGGL(k_kzg_invert, dim3(blocks(count, 64)), dim3(64), 0, st, kz->xs.as<Fr>(), count);
+                    hipLaunchKernelGGL(k_kzg_unscale, dim3(blocks(count * n)), dim3(256), 0, st, kz->r2.as<Fr>(), kz->xs.as<Fr>(), n,
+                                       count * n);
+                    interp = kz->r2.as<Fr>();
+                }
+                msm_on_stream(kz, kz->out.p, interp, n, count);
+                hipLaunchKernelGGL(k_kzg_g1_sub, dim3(blocks(count, 64)), dim3(64), 0, st, dif, (const ff::Fp*)com,
+                                   (const ff::Fp*)kz->out.p, count);
+                KZ_TRY(hipGetLastError());
+                KZ_TRY(hipMemcpyAsync(lhs.data(), dif, count * sizeof(blst_p1), hipMemcpyDeviceToHost, st));
+            } catch (...) {
+                (void)hipStreamSynchronize(st);
+                throw;
+            }
+            KZ_TRY(hipStreamSynchronize(st));
+        } catch (const KzErr& e) {
+            rc = -(int)e.e - 100;
+        } catch (...) {
+            rc = -2;
+        }
+    }
+    if (rc) return rc;
+    // the G2 side and the pairings, on the host like the reference's:  e(lhs, G2) == e(proof, [s^n]G2 - [x^n]G2)
+    const pr::G2Jac gen = pr::g2_generator();
+    const std::shared_ptr<const pr::LineTable> tgen = pr::prepared_lines(gen);
+    for (size_t i = 0; i < count; ++i) {
+        Fr xn = hx[i];
+        for (size_t m = 1; m < n; m <<= 1) xn = ff::mul(xn, xn);
+        xn = ff::from_mont(xn);
+        const pr::G2Jac rhs2 = pr::g2_add(kz->g2[n], pr::g2_neg(pr::g2_mul(gen, xn.v)));
+        const pr::LineTable trhs = pr::g2_line_table(pr::g2_to_affine(rhs2));
+        ff::Fp px[2], py[2];
+        bool inf[2];
+        inf[0] = g1_affine(&lhs[i], px[0], py[0]);
+        inf[1] = g1_affine(&proofs[i], px[1], py[1]);
+        if (!inf[0]) py[0] = hfp::neg(py[0]);  // e(-lhs, G2) e(proof, rhs2) == 1
+        const pr::LineTable* tabs[2] = {tgen.get(), &trhs};
+        ok[i] = pr::f12_is_one(pr::final_exponentiation(pr::miller_loop_multi(tabs, px, py, inf, 2)));
+    }
+    return 0;
+}

@@ -7,17 +7,17 @@ use alloc::string::{String, ToString};
 use alloc::sync::Arc;
 use alloc::vec::Vec;
 
-use blst::blst_p1_affine;
-use kzg::{FFTFr, FFTSettings, Fr, G1Affine, G1Mul, G2Mul, KZGSettings, Poly, FFTG1, G1, G2};
-use rust_kzg_blst::kzg_proofs::pairings_verify;
+use blst::{blst_fr, blst_p1, blst_p1_affine, blst_p2};
+use kzg::{FFTSettings, G1Affine, KZGSettings, FFTG1, G1};
 use rust_kzg_blst::types::fp::FsFp;
 use rust_kzg_blst::types::fr::FsFr;
 use rust_kzg_blst::types::g2::FsG2;
 use rust_kzg_blst::types::poly::FsPoly;
 use rust_kzg_mi355x_sys as sys;
+use rust_kzg_mi355x_sys::GpuKzg;
 
 use crate::fft_settings::MiFFTSettings;
-use crate::g1::{g1_linear_combination, MiG1, MiG1Affine, MiG1ProjAddAffine, MiPrecomputation};
+use crate::g1::{MiG1, MiG1Affine, MiG1ProjAddAffine, MiPrecomputation};
 
 #[derive(Debug, Clone, Default)]
 pub struct MiKZGSettings {
@@ -34,7 +34,15 @@ pub struct MiKZGSettings {
     /// whether the FK20 matrix table was attached; `false` = it did not fit its budget (or the device refused) and
     /// `g1_lincomb_batch` runs row by row — correct, two orders of magnitude slower; callers that care can look
     pub matrix_table_attached: bool,
+    /// the polynomial-level calls (`commit_to_poly`, `compute_proof_*`, `check_proof_*`) on the GPU: `kzgamd_kzg_new` over
+    /// `g1_values_monomial` / `g2_values_monomial` and the NTT handle of `fs`.  `None` only for `Default::default()` (a
+    /// host placeholder, as elsewhere in this crate: using it is an error, never a CPU fallback)
+    pub poly_kzg: Option<Arc<GpuKzg>>,
 }
+
+/// HBM the fixed-base table over `g1_values_monomial` of the polynomial-level handle may take (see below: several
+/// settings objects live side by side in the rust-kzg suites).
+pub const MONOMIAL_TABLE_BUDGET_BYTES: u64 = 8 << 30;
 
 /// HBM each of the two fixed-base tables of ONE settings object may take.  The library's default (160 GB per table,
 /// capped by what is free) is right for a process that owns a GPU and one settings object; the rust-kzg test and bench
@@ -81,7 +89,30 @@ fn prepare(points: &[MiG1], matrix: &[Vec<MiG1>], lagrange_budget: u64, matrix_b
     (Some(Arc::new(MiPrecomputation::from_ptr(handle))), attached)
 }
 
+fn fr_slice(v: &[FsFr]) -> &[blst_fr] {
+    unsafe { core::slice::from_raw_parts(v.as_ptr() as *const blst_fr, v.len()) }
+}
+
 impl MiKZGSettings {
+    fn device(&self) -> Result<&GpuKzg, String> {
+        self.poly_kzg.as_deref().ok_or_else(|| String::from("MiKZGSettings::default() has no device handle; use new()"))
+    }
+
+    /// `compute_proof_single` / `compute_proof_multi`: the batched call (`kzgamd_kzg_open`) with a batch of one — quotient
+    /// and commitment in one device pass, nothing of the polynomial touched on the host
+    fn open_one(&self, p: &FsPoly, x: &FsFr, n: usize) -> Result<MiG1, String> {
+        let (proofs, _) = self.device()?.open(fr_slice(&p.coeffs), p.coeffs.len(), 1, fr_slice(core::slice::from_ref(x)), n, false)?;
+        Ok(MiG1::from_blst(proofs[0]))
+    }
+
+    /// `check_proof_single` / `check_proof_multi`: interpolation, its commitment and the subtraction on the GPU, the
+    /// pairing on the host inside the library (`kzgamd_kzg_check`)
+    fn check_one(&self, com: &MiG1, proof: &MiG1, x: &FsFr, ys: &[FsFr], n: usize) -> Result<bool, String> {
+        let ok = self.device()?.check(core::slice::from_ref(&com.0 .0), core::slice::from_ref(&proof.0 .0), fr_slice(core::slice::from_ref(x)),
+                                      fr_slice(ys), n)?;
+        Ok(ok[0])
+    }
+
     /// Rebuilds the two device tables with other HBM budgets (bytes per table; 0 = the library's default of 160 GB
     /// capped by the free HBM — for a process with ONE settings object on a GPU of its own).  The old tables are
     /// released first if this object is their last owner (otherwise when the last clone that shares them goes away).
@@ -132,7 +163,18 @@ impl KZGSettings<FsFr, MiG1, FsG2, MiFFTSettings, FsPoly, FsFp, MiG1Affine, MiG1
         }
         let (precomputation, matrix_table_attached) =
             prepare(g1_lagrange_brp, &x_ext_fft_columns, LAGRANGE_TABLE_BUDGET_BYTES, MATRIX_TABLE_BUDGET_BYTES);
+        let poly_kzg = match fft_settings.gpu.clone() {
+            Some(ntt) => {
+                let mono = unsafe { core::slice::from_raw_parts(g1_monomial.as_ptr() as *const blst_p1, g1_monomial.len()) };
+                let g2 = unsafe { core::slice::from_raw_parts(g2_monomial.as_ptr() as *const blst_p2, g2_monomial.len()) };
+                let mut cfg = sys::KzgAmdConfig::default();
+                cfg.table_budget_bytes = MONOMIAL_TABLE_BUDGET_BYTES;
+                Some(Arc::new(GpuKzg::new(ntt, mono, g2, Some(&cfg))?))
+            }
+            None => None,
+        };
         Ok(Self {
+            poly_kzg,
             g1_values_monomial: g1_monomial.to_vec(),
             g1_values_lagrange_brp: g1_lagrange_brp.to_vec(),
             g2_values_monomial: g2_monomial.to_vec(),
@@ -145,67 +187,30 @@ impl KZGSettings<FsFr, MiG1, FsG2, MiFFTSettings, FsPoly, FsFp, MiG1Affine, MiG1
     }
 
     fn commit_to_poly(&self, poly: &FsPoly) -> Result<MiG1, String> {
-        if poly.coeffs.len() > self.g1_values_monomial.len() {
-            return Err(String::from("Polynomial is longer than secret g1"));
-        }
-        let mut out = MiG1::default();
-        g1_linear_combination(&mut out, &self.g1_values_monomial, &poly.coeffs, poly.coeffs.len(), None);
-        Ok(out)
+        let out = self.device()?.commit(fr_slice(&poly.coeffs), poly.coeffs.len(), 1)?;
+        Ok(MiG1::from_blst(out[0]))
     }
 
     fn compute_proof_single(&self, p: &FsPoly, x: &FsFr) -> Result<MiG1, String> {
-        if p.coeffs.is_empty() {
-            return Err(String::from("Polynomial must not be empty"));
-        }
-        // synthetic division by (X - x), highest coefficient first
-        let mut q: Vec<FsFr> = p.coeffs[1..].to_vec();
-        for i in (1..q.len()).rev() {
-            let carry = q[i].mul(x);
-            q[i - 1] = q[i - 1].add(&carry);
-        }
-        self.commit_to_poly(&FsPoly { coeffs: q })
+        self.open_one(p, x, 1)
     }
 
     fn check_proof_single(&self, com: &MiG1, proof: &MiG1, x: &FsFr, y: &FsFr) -> Result<bool, String> {
-        // e(com - [y]G1, G2) == e(proof, [s]G2 - [x]G2); the pairing is CPU code in every backend
-        let s_minus_x = self.g2_values_monomial[1].sub(&FsG2::generator().mul(x));
-        let com_minus_y = com.sub(&MiG1::generator().mul(y));
-        Ok(pairings_verify(&com_minus_y.0, &FsG2::generator(), &proof.0, &s_minus_x))
+        self.check_one(com, proof, x, core::slice::from_ref(y), 1)
     }
 
     fn compute_proof_multi(&self, p: &FsPoly, x0: &FsFr, n: usize) -> Result<MiG1, String> {
-        if p.coeffs.is_empty() {
-            return Err(String::from("Polynomial must not be empty"));
-        }
-        if !n.is_power_of_two() {
-            return Err(String::from("n must be a power of two"));
-        }
-        // divisor X^n - x0^n, quotient by the blst backend's polynomial division, commitment on the GPU
-        let mut divisor = FsPoly { coeffs: alloc::vec![FsFr::zero(); n + 1] };
-        divisor.coeffs[0] = x0.pow(n).negate();
-        divisor.coeffs[n] = FsFr::one();
-        let mut dividend = p.clone();
-        let q = dividend.div(&divisor)?;
-        self.commit_to_poly(&q)
+        self.open_one(p, x0, n)
     }
 
     fn check_proof_multi(&self, com: &MiG1, proof: &MiG1, x: &FsFr, ys: &[FsFr], n: usize) -> Result<bool, String> {
         if !n.is_power_of_two() {
             return Err(String::from("n is not a power of two"));
         }
-        // interpolation polynomial of ys on the coset x * <w_n>: inverse NTT (GPU), then unscale by x^-i
-        let mut interp = FsPoly { coeffs: self.fs.fft_fr(ys, true)? };
-        let inv_x = x.inverse();
-        let mut pw = inv_x;
-        for c in interp.coeffs.iter_mut().skip(1) {
-            *c = c.mul(&pw);
-            pw = pw.mul(&inv_x);
+        if ys.len() != n {
+            return Err(String::from("A list with power-of-two length expected"));
         }
-        let xn2 = FsG2::generator().mul(&x.pow(n));
-        let xn_minus_yn = self.g2_values_monomial[n].sub(&xn2);
-        let is1 = self.commit_to_poly(&interp)?;
-        let commit_minus_interp = com.sub(&is1);
-        Ok(pairings_verify(&commit_minus_interp.0, &FsG2::generator(), &proof.0, &xn_minus_yn))
+        self.check_one(com, proof, x, ys, n)
     }
 
     fn get_roots_of_unity_at(&self, i: usize) -> FsFr {

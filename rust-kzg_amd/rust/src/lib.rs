@@ -6,7 +6,7 @@
 //!   * `GpuNtt::fft_fr` / `das_fft_extension` / `fft_g1`  <->  blst/src/fft_fr.rs:156-165,
 //!     blst/src/data_availability_sampling.rs:78-100, blst/src/fft_g1.rs:54-83
 //!   * `g1_sum`  —  combine step of one MSM split over several GPUs
-use blst::{blst_fr, blst_p1, blst_p1_affine};
+use blst::{blst_fr, blst_p1, blst_p1_affine, blst_p2};
 use core::ffi::{c_char, c_int, c_void};
 
 #[repr(C)]
@@ -63,6 +63,17 @@ extern "C" {
     fn kzgamd_fk20_da(fk: *mut c_void, out: *mut blst_p1, polys: *const blst_fr, n: usize, npoly: usize,
                       optimized: c_int) -> c_int;
     fn kzgamd_fk20_info(fk: *mut c_void, n2: *mut usize, chunk_len: *mut usize, form: *mut c_int) -> c_int;
+
+    fn kzgamd_kzg_new(ntt: *mut c_void, g1_monomial: *const blst_p1, num_g1: usize, g2_monomial: *const blst_p2, num_g2: usize,
+                      cfg: *const KzgAmdConfig, err: *mut c_int) -> *mut c_void;
+    fn kzgamd_kzg_free(kz: *mut c_void);
+    fn kzgamd_kzg_info(kz: *mut c_void, num_g1: *mut usize, num_g2: *mut usize, chunk: *mut usize,
+                       lane_form_min: *mut usize) -> c_int;
+    fn kzgamd_kzg_commit(kz: *mut c_void, out: *mut blst_p1, polys: *const blst_fr, len: usize, npoly: usize) -> c_int;
+    fn kzgamd_kzg_open(kz: *mut c_void, proofs: *mut blst_p1, ys: *mut blst_fr, polys: *const blst_fr, len: usize,
+                       npoly: usize, xs: *const blst_fr, nx: usize, n: usize) -> c_int;
+    fn kzgamd_kzg_check(kz: *mut c_void, ok: *mut bool, commitments: *const blst_p1, proofs: *const blst_p1,
+                        xs: *const blst_fr, ys: *const blst_fr, n: usize, count: usize) -> c_int;
 }
 
 fn check(err: RustError, what: &str) -> Result<(), String> {
@@ -363,6 +374,111 @@ impl GpuFk20 {
 impl Drop for GpuFk20 {
     fn drop(&mut self) {
         unsafe { kzgamd_fk20_free(self.ctx) }
+    }
+}
+
+/// Generic polynomial KZG handle (`kzgamd_kzg_new`): the proving and checking calls of the reference's `KZGSettings`
+/// (blst/src/types/kzg_settings.rs:138-277) over a `GpuNtt` and a monomial setup, batched.  Holds the NTT handle alive:
+/// the C handle keeps it by pointer and must be freed first (field order = drop order).
+pub struct GpuKzg {
+    ctx: *mut c_void,
+    _ntt: std::sync::Arc<GpuNtt>,
+}
+unsafe impl Send for GpuKzg {}
+unsafe impl Sync for GpuKzg {}
+
+impl core::fmt::Debug for GpuKzg {
+    fn fmt(&self, f: &mut core::fmt::Formatter<'_>) -> core::fmt::Result {
+        let (num_g1, num_g2, _, _) = self.info();
+        write!(f, "GpuKzg {{ num_g1: {num_g1}, num_g2: {num_g2} }}")
+    }
+}
+
+impl GpuKzg {
+    /// `g2_monomial` may be empty: a handle that proves but does not check.
+    pub fn new(ntt: std::sync::Arc<GpuNtt>, g1_monomial: &[blst_p1], g2_monomial: &[blst_p2],
+               cfg: Option<&KzgAmdConfig>) -> Result<Self, String> {
+        let mut err: c_int = 0;
+        let cfg_ptr = cfg.map_or(core::ptr::null(), |c| c as *const KzgAmdConfig);
+        let g2_ptr = if g2_monomial.is_empty() { core::ptr::null() } else { g2_monomial.as_ptr() };
+        let ctx = unsafe {
+            kzgamd_kzg_new(ntt.ctx, g1_monomial.as_ptr(), g1_monomial.len(), g2_ptr, g2_monomial.len(), cfg_ptr, &mut err)
+        };
+        if ctx.is_null() {
+            return Err(match err {
+                1 => String::from("the setup has no G1 points"),
+                e => format!("kzgamd_kzg_new failed: {e}"),
+            });
+        }
+        Ok(Self { ctx, _ntt: ntt })
+    }
+
+    /// `commit_to_poly` for `npoly` polynomials of `len` coefficients each (contiguous).
+    pub fn commit(&self, polys: &[blst_fr], len: usize, npoly: usize) -> Result<Vec<blst_p1>, String> {
+        if polys.len() != len * npoly {
+            return Err(String::from("polys must hold npoly * len coefficients"));
+        }
+        let mut out = vec![blst_p1::default(); npoly];
+        match unsafe { kzgamd_kzg_commit(self.ctx, out.as_mut_ptr(), polys.as_ptr(), len, npoly) } {
+            0 => Ok(out),
+            1 => Err(String::from("Polynomial is longer than secret g1")),
+            e => Err(format!("GPU KZG commit failed: {e}")),
+        }
+    }
+
+    /// `compute_proof_single` (n = 1) / `compute_proof_multi` for every (polynomial, x) pair: npoly * xs.len() proofs,
+    /// and with `want_ys` the npoly * xs.len() * n values p(x w^i).
+    pub fn open(&self, polys: &[blst_fr], len: usize, npoly: usize, xs: &[blst_fr], n: usize,
+                want_ys: bool) -> Result<(Vec<blst_p1>, Vec<blst_fr>), String> {
+        if polys.len() != len * npoly {
+            return Err(String::from("polys must hold npoly * len coefficients"));
+        }
+        let pairs = npoly * xs.len();
+        let mut proofs = vec![blst_p1::default(); pairs];
+        let mut ys = vec![blst_fr::default(); if want_ys { pairs * n } else { 0 }];
+        let ys_ptr = if want_ys { ys.as_mut_ptr() } else { core::ptr::null_mut() };
+        match unsafe { kzgamd_kzg_open(self.ctx, proofs.as_mut_ptr(), ys_ptr, polys.as_ptr(), len, npoly, xs.as_ptr(), xs.len(), n) } {
+            0 => Ok((proofs, ys)),
+            1 => Err(String::from("Polynomial is longer than secret g1")),
+            2 => Err(String::from("Polynomial must not be empty")),
+            3 => Err(String::from("n must be a power of two")),
+            4 => Err(String::from("Supplied list is longer than the available max width")),
+            e => Err(format!("GPU KZG open failed: {e}")),
+        }
+    }
+
+    /// `check_proof_single` (n = 1) / `check_proof_multi` for `xs.len()` tuples: one verdict per tuple.
+    pub fn check(&self, commitments: &[blst_p1], proofs: &[blst_p1], xs: &[blst_fr], ys: &[blst_fr],
+                 n: usize) -> Result<Vec<bool>, String> {
+        let count = xs.len();
+        if commitments.len() != count || proofs.len() != count || ys.len() != count * n {
+            return Err(String::from("commitments, proofs, xs and ys must describe the same number of tuples"));
+        }
+        let mut ok = vec![false; count];
+        match unsafe {
+            kzgamd_kzg_check(self.ctx, ok.as_mut_ptr(), commitments.as_ptr(), proofs.as_ptr(), xs.as_ptr(), ys.as_ptr(), n, count)
+        } {
+            0 => Ok(ok),
+            1 => Err(String::from("Polynomial is longer than secret g1")),
+            3 => Err(String::from("n is not a power of two")),
+            4 => Err(String::from("Supplied list is longer than the available max width")),
+            5 => Err(String::from("x must not be zero")),
+            6 => Err(String::from("the setup has too few G2 points")),
+            e => Err(format!("GPU KZG check failed: {e}")),
+        }
+    }
+
+    /// (num_g1, num_g2, chunk, lane_form_min)
+    pub fn info(&self) -> (usize, usize, usize, usize) {
+        let (mut a, mut b, mut c, mut d) = (0usize, 0usize, 0usize, 0usize);
+        unsafe { kzgamd_kzg_info(self.ctx, &mut a, &mut b, &mut c, &mut d) };
+        (a, b, c, d)
+    }
+}
+
+impl Drop for GpuKzg {
+    fn drop(&mut self) {
+        unsafe { kzgamd_kzg_free(self.ctx) }
     }
 }
 
