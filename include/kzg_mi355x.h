@@ -263,6 +263,48 @@ int kzgamd_kzg_open(void *kz, blst_p1 *proofs, blst_fr *ys, const blst_fr *polys
                     const blst_fr *xs, size_t nx, size_t n);
 int kzgamd_kzg_check(void *kz, bool *ok, const blst_p1 *commitments, const blst_p1 *proofs, const blst_fr *xs,
                      const blst_fr *ys, size_t n, size_t count);
+/* Batched polynomial arithmetic, the reference's Poly<Fr> and FFTSettingsPoly (blst/src/types/poly.rs) on the GPU
+ * (rust-kzg_amd/csrc/poly.hip).  Conventions of kzgamd_kzg_*: scalars are Montgomery blst_fr in host buffers; batches
+ * are contiguous, npoly independent problems of the same shape per call; the handle is thread-safe (calls on one handle
+ * take turns; calls on `ntt` may run beside them).  Codes: 0 ok, positive = the reference's error conditions as listed
+ * per call, -1 NULL argument (or a form outside 0..2), other negatives = device error.  Every result is a field element
+ * with one value — a truncated product, the first coefficients of a power-series inverse, a quotient by a divisor whose
+ * highest coefficient is non-zero — so results equal the reference's element for element, whichever route runs.
+ *
+ * kzgamd_poly_new keeps `ntt` by pointer and uses it in every call: free the poly handle FIRST, the NTT handle after
+ * it.  *err (may be NULL): 0 ok, -1 NULL argument, -2 malformed configuration, or a device error.  kzgamd_poly_free
+ * gives every byte of HBM back.  kzgamd_poly_info: the max width of `ntt`, the coefficients a lane of eval takes, the
+ * multiplications per lane up to which form 0 of mul takes the direct product, the coefficients of an inverse that
+ * come from the one-launch recurrence before Newton steps begin; any pointer may be NULL. */
+void *kzgamd_poly_new(void *ntt, const KzgAmdConfig *cfg, int *err);
+void kzgamd_poly_free(void *ph);
+int kzgamd_poly_info(void *ph, size_t *max_width, size_t *eval_chunk, size_t *mul_direct_max, size_t *inv_direct_max);
+/* ys[b * nx + k] = p_b(x_k) (Poly::eval, poly.rs:42-62).  len = 0: zeros.  x = 0 gives coefficient 0.  npoly = 0 or
+ * nx = 0: ok, nothing written. */
+int kzgamd_poly_eval(void *ph, blst_fr *ys, const blst_fr *polys, size_t len, size_t npoly, const blst_fr *xs, size_t nx);
+/* out[b * len + i] = in[b * len + i] * 5^-(i+1) (inverse = 0: Poly::scale, poly.rs:64-73) or * 5^(i+1) (inverse = 1:
+ * unscale, :75-83).  NOTE the exponent i + 1, not i: the reference multiplies before it uses the power.  out may be in. */
+int kzgamd_poly_scale(void *ph, blst_fr *out, const blst_fr *in, size_t len, size_t npoly, int inverse);
+/* out[b * out_len + i] = coefficient i of a_b * b_b, zero beyond la + lb - 2 (mul_direct :252-277, mul_fft :340-396,
+ * mul :398-405).  form 0: chosen by shape, 1: direct (a lane per output coefficient), 2: by transforms (a product of
+ * two constants runs none).  All forms give the same elements.  la = 0 or lb = 0: out_len zeros (the reference returns
+ * an empty polynomial there).  out_len = 0 or npoly = 0: ok, nothing written.  4: the transform form needs a transform
+ * longer than the handle's max width (nothing written). */
+int kzgamd_poly_mul(void *ph, blst_fr *out, const blst_fr *a, size_t la, const blst_fr *b, size_t lb, size_t out_len,
+                    size_t npoly, int form);
+/* out[b * out_len + i] = coefficient i of 1 / b_b as a power series (Poly::inverse, :86-149).  1: out_len == 0,
+ * 2: lb == 0, 3: a polynomial of the batch has b[0] == 0 (outputs unspecified), 4: as above. */
+int kzgamd_poly_inverse(void *ph, blst_fr *out, const blst_fr *b, size_t lb, size_t out_len, size_t npoly);
+/* q[b * (la - lb + 1) + i] = coefficient i of the quotient of a_b by b_b (div :151-158, long_div :160-214, fast_div
+ * :216-250: one result whichever the reference would take).  1: lb == 0 ("Can't divide by zero"), 2: a divisor's
+ * highest coefficient is zero (outputs unspecified), 4: as above.  la < lb: ok, nothing written (the reference's
+ * zero-length quotient). */
+int kzgamd_poly_div(void *ph, blst_fr *q, const blst_fr *a, size_t la, const blst_fr *b, size_t lb, size_t npoly);
+/* host-only, no GPU: the longest transform a call of this shape enqueues in this build (0: none).  op 0 mul (form 2),
+ * 1 inverse (la ignored), 2 div (out_len ignored).  A call succeeds exactly when the handle's max width is at least
+ * this.  Never more than next_pow2(min(la, out_len) + min(lb, out_len) - 1) for mul and next_pow2(2 L - 1) for inverse
+ * (L = out_len) and div (L = la - lb + 1): the reference's own lengths (poly.rs:341, :109). */
+size_t kzgamd_poly_transform_len(int op, size_t la, size_t lb, size_t out_len);
 /* The tile plan the NTT kernel runs for (kind, T) — host-only, no GPU needed (rust-kzg_amd/csrc/ntt_plan.h):
  * kind 0 = whole transform of 2^T <= 4096 points, 1 = first pass of a longer one, 2 = later pass; rounds[4*r..] =
  * {first stage, stages, barrier after, element bit}; tab[(r*1024 + thread)*4..] = {idxA, idxB, lds(idxA), lds(idxB)}.

@@ -67,6 +67,8 @@ EXPORTS = [
     "fft_g1", "kzgamd_fft_g1_batch", "kzgamd_g1_sum",
     "kzgamd_fk20_new", "kzgamd_fk20_free", "kzgamd_fk20_da", "kzgamd_fk20_info",
     "kzgamd_kzg_new", "kzgamd_kzg_free", "kzgamd_kzg_info", "kzgamd_kzg_commit", "kzgamd_kzg_open", "kzgamd_kzg_check",
+    "kzgamd_poly_new", "kzgamd_poly_free", "kzgamd_poly_info", "kzgamd_poly_eval", "kzgamd_poly_scale", "kzgamd_poly_mul",
+    "kzgamd_poly_inverse", "kzgamd_poly_div", "kzgamd_poly_transform_len",
     "load_trusted_setup", "load_trusted_setup_file", "free_trusted_setup", "blob_to_kzg_commitment",
     "compute_kzg_proof", "compute_blob_kzg_proof", "kzgamd_compute_blob_kzg_proof_batch", "compute_challenge",
     "bytes_to_kzg_commitment", "bytes_from_bls_field", "compute_cells_and_kzg_proofs",
@@ -231,6 +233,24 @@ def lib():
     L.kzgamd_kzg_open.argtypes = [vp, vp, vp, vp, sz, sz, vp, sz, sz]
     L.kzgamd_kzg_check.restype = C.c_int
     L.kzgamd_kzg_check.argtypes = [vp, vp, vp, vp, vp, vp, sz, sz]
+    L.kzgamd_poly_new.restype = vp
+    L.kzgamd_poly_new.argtypes = [vp, cp, C.POINTER(C.c_int)]
+    L.kzgamd_poly_free.restype = None
+    L.kzgamd_poly_free.argtypes = [vp]
+    L.kzgamd_poly_info.restype = C.c_int
+    L.kzgamd_poly_info.argtypes = [vp, C.POINTER(sz), C.POINTER(sz), C.POINTER(sz), C.POINTER(sz)]
+    L.kzgamd_poly_eval.restype = C.c_int
+    L.kzgamd_poly_eval.argtypes = [vp, vp, vp, sz, sz, vp, sz]
+    L.kzgamd_poly_scale.restype = C.c_int
+    L.kzgamd_poly_scale.argtypes = [vp, vp, vp, sz, sz, C.c_int]
+    L.kzgamd_poly_mul.restype = C.c_int
+    L.kzgamd_poly_mul.argtypes = [vp, vp, vp, sz, vp, sz, sz, sz, C.c_int]
+    L.kzgamd_poly_inverse.restype = C.c_int
+    L.kzgamd_poly_inverse.argtypes = [vp, vp, vp, sz, sz, sz]
+    L.kzgamd_poly_div.restype = C.c_int
+    L.kzgamd_poly_div.argtypes = [vp, vp, vp, sz, vp, sz, sz]
+    L.kzgamd_poly_transform_len.restype = sz
+    L.kzgamd_poly_transform_len.argtypes = [C.c_int, sz, sz, sz]
     L.kzgamd_ntt_roots.restype = C.c_int
     L.kzgamd_ntt_roots.argtypes = [vp, vp, vp, vp]
     sp = C.POINTER(CKZGSettings)
@@ -838,6 +858,119 @@ class PolyKZGSettings:
     def close(self):
         if self.handle:
             lib().kzgamd_kzg_free(self.handle)
+            self.handle = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+POLY_ERRORS = {
+    "inverse": {1: "Can't produce a zero-length result", 2: "Can't inverse a zero-length poly",
+                3: "First coefficient of polynomial mustn't be zero"},
+    "div": {1: "Can't divide by zero", 2: "Highest coefficient must be non-zero"},
+}
+
+
+class PolySettings:
+    """The reference's Poly<Fr> and FFTSettingsPoly (blst/src/types/poly.rs) over an FFTSettings handle, batched: every
+    call takes npoly polynomials of one shape, contiguous, as Montgomery blst_fr.  Errors carry the reference's messages
+    and the code (`.code`).  Keeps the FFTSettings object alive; close() (or leaving the `with` block) frees the GPU state."""
+
+    def __init__(self, fs, config=None):
+        self.fs = fs
+        self.handle = None
+        err = C.c_int(0)
+        self.handle = lib().kzgamd_poly_new(fs.handle, _cfgp(config), C.byref(err))
+        self.err = err.value
+        if not self.handle:
+            raise self._error("kzgamd_poly_new", err.value, "kzgamd_poly_new failed: %d (no GPU, NULL argument or bad configuration)" % err.value)
+
+    @staticmethod
+    def _error(what, rc, msg=None):
+        if msg is None and rc == 4:
+            msg = "Supplied list is longer than the available max width"
+        e = KzgAmdError(msg or "%s: %d" % (what, rc))
+        e.code = rc
+        return e
+
+    def _live(self):
+        if not self.handle:
+            raise KzgAmdError("PolySettings is closed")
+
+    def eval(self, polys, length, npoly, xs, nx):
+        """Poly::eval of every polynomial at every x.  Returns (BlstFr * (npoly * nx)): ys[b * nx + k] = p_b(x_k)."""
+        self._live()
+        ys = (BlstFr * max(1, npoly * nx))()
+        rc = lib().kzgamd_poly_eval(self.handle, ys, _addr(polys) if npoly * length else None, length, npoly,
+                                    _addr(xs) if nx else None, nx)
+        if rc != 0:
+            raise self._error("kzgamd_poly_eval", rc)
+        return ys
+
+    def scale(self, polys, length, npoly=1, inverse=False):
+        """Poly::scale (coefficient i times 5^-(i+1)) or, inverse=True, Poly::unscale.  Returns (BlstFr * (npoly * length))."""
+        self._live()
+        out = (BlstFr * max(1, npoly * length))()
+        rc = lib().kzgamd_poly_scale(self.handle, out, _addr(polys) if npoly * length else None, length, npoly, 1 if inverse else 0)
+        if rc != 0:
+            raise self._error("kzgamd_poly_scale", rc)
+        return out
+
+    def mul(self, a, la, b, lb, out_len, npoly=1, form=0):
+        """The first out_len coefficients of a_b * b_b (Poly::mul; form 1: mul_direct, 2: mul_fft).  Returns
+        (BlstFr * (npoly * out_len))."""
+        self._live()
+        out = (BlstFr * max(1, npoly * out_len))()
+        rc = lib().kzgamd_poly_mul(self.handle, out, _addr(a) if npoly * la else None, la, _addr(b) if npoly * lb else None, lb,
+                                   out_len, npoly, form)
+        if rc != 0:
+            raise self._error("kzgamd_poly_mul", rc)
+        return out
+
+    def inverse(self, b, lb, out_len, npoly=1):
+        """Poly::inverse: the first out_len coefficients of 1 / b_b.  Returns (BlstFr * (npoly * out_len))."""
+        self._live()
+        out = (BlstFr * max(1, npoly * out_len))()
+        rc = lib().kzgamd_poly_inverse(self.handle, out, _addr(b) if npoly * lb else None, lb, out_len, npoly)
+        if rc != 0:
+            raise self._error("kzgamd_poly_inverse", rc, POLY_ERRORS["inverse"].get(rc))
+        return out
+
+    def div(self, a, la, b, lb, npoly=1):
+        """Poly::div: the quotients of a_b by b_b.  Returns (BlstFr * (npoly * (la - lb + 1))), of length 0 when la < lb."""
+        self._live()
+        qlen = la - lb + 1 if la >= lb else 0
+        out = (BlstFr * (npoly * qlen))()
+        rc = lib().kzgamd_poly_div(self.handle, out, _addr(a) if npoly * la else None, la, _addr(b) if npoly * lb else None, lb, npoly)
+        if rc != 0:
+            raise self._error("kzgamd_poly_div", rc, POLY_ERRORS["div"].get(rc))
+        return out
+
+    def info(self):
+        """(max_width, eval_chunk, mul_direct_max, inv_direct_max): see kzgamd_poly_info"""
+        self._live()
+        v = [C.c_size_t(0) for _ in range(4)]
+        if lib().kzgamd_poly_info(self.handle, *[C.byref(x) for x in v]) != 0:
+            raise KzgAmdError("kzgamd_poly_info failed")
+        return tuple(x.value for x in v)
+
+    @staticmethod
+    def transform_len(op, la, lb, out_len):
+        """the longest transform a call of this shape enqueues (0: none); op "mul" (form 2), "inverse" or "div".  No GPU."""
+        return lib().kzgamd_poly_transform_len({"mul": 0, "inverse": 1, "div": 2}[op], la, lb, out_len)
+
+    def close(self):
+        if self.handle:
+            lib().kzgamd_poly_free(self.handle)
             self.handle = None
 
     def __enter__(self):

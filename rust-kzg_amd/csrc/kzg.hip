@@ -42,6 +42,7 @@
 #include "device_guard.h"
 #include "ff.hip.h"
 #include "fr29.hip.h"
+#include "frscan.hip.h"
 #include "g1_28.hip.h"
 #include "host_fp64.h"
 #include "host_pairing.h"
@@ -54,44 +55,8 @@ using g1::Xyzz;
 
 namespace {
 
-constexpr int CHUNK = 16;                   // consecutive steps of a sequence per lane of the chunked form
+// CHUNK, PW, NPOW, fr_mul, fr_pow, shfl_down, scan_suffix and k_kzg_pows: frscan.hip.h, shared with poly.hip
 constexpr size_t LANE_FORM_MIN = 16384;     // lanes (pairs x n) from which the lane form is taken: a wave per CU
-constexpr int PW = 16;                      // per x: c, then C^(2^k), k = 0 .. 11, C = c^CHUNK (C^64 and its powers chain the waves)
-constexpr int NPOW = 12;
-
-__device__ __forceinline__ Fr fr_mul(const Fr& a, const Fr& b) { return fr29::mul_blst(a, b); }
-
-// a^e for a small public exponent
-__device__ __forceinline__ Fr fr_pow(const Fr& a, size_t e) {
-    Fr r = Fr::one(), b = a;
-    while (e) {
-        if (e & 1) r = fr_mul(r, b);
-        e >>= 1;
-        if (e) b = fr_mul(b, b);
-    }
-    return r;
-}
-
-__device__ __forceinline__ Fr shfl_down(const Fr& a, int d) {
-    Fr r;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) r.v[i] = __shfl_down(a.v[i], d, 64);
-    return r;
-}
-
-// per x: pw[0] = c = x^n, pw[1 + k] = (c^CHUNK)^(2^k), k < NPOW
-__global__ void __launch_bounds__(64) k_kzg_pows(Fr* __restrict__ pw, const Fr* __restrict__ xs, size_t n, size_t nx) {
-    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= nx) return;
-    Fr c = xs[t];
-    for (size_t m = 1; m < n; m <<= 1) c = fr_mul(c, c);
-    pw[t * PW] = c;
-    Fr C = fr_pow(c, CHUNK);
-    for (int k = 0; k < NPOW; ++k) {
-        pw[t * PW + 1 + k] = C;
-        C = fr_mul(C, C);
-    }
-}
 
 struct QuotShape {
     size_t len, n, nx, L;    // L = len - n: the quotient's length (the MSMs' stride); only called with len > n
@@ -154,11 +119,7 @@ __global__ void __launch_bounds__(256) k_kzg_chunk(Fr* __restrict__ q, Fr* __res
     if (more) above = sums[seq * s.wv + w + 1];
     if (more && lg == 63) S = ff::add(S, fr_mul(mypw[1], above));
     // suffix scan over the group: H_m = sum_{d >= 0} C^d S_{m + d}
-    Fr H = S;
-    for (u32 k = 0; ((u32)1 << k) < s.gw; ++k) {
-        const Fr up = shfl_down(H, 1 << k);
-        if (lg + ((u32)1 << k) < s.gw) H = ff::add(H, fr_mul(mypw[1 + k], up));
-    }
+    const Fr H = scan_suffix(S, lg, s.gw, mypw + 1);
     if (!REPLAY) {
         if (live && lg == 0) sums[seq * s.wv + w] = H;
         return;
@@ -189,10 +150,7 @@ __global__ void __launch_bounds__(64) k_kzg_carry(Fr* __restrict__ sums, const F
         const size_t w = blk * 64 + lane;
         Fr H = w < s.wv ? g[w] : Fr::zero();
         if (lane == 63) H = ff::add(H, fr_mul(mypw[0], above));
-        for (u32 k = 0; k < 6; ++k) {
-            const Fr up = shfl_down(H, 1 << k);
-            if (lane + ((u32)1 << k) < 64) H = ff::add(H, fr_mul(mypw[k], up));
-        }
+        H = scan_suffix(H, lane, 64, mypw);
         if (w < s.wv) g[w] = H;
 #pragma unroll
         for (int i = 0; i < 8; ++i) above.v[i] = __shfl(H.v[i], 0, 64);

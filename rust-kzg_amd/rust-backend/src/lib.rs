@@ -9,6 +9,7 @@
 //! | [`fft_settings::MiFFTSettings`] | `FsFFTSettings` | `FFTFr::fft_fr`, `FFTG1::fft_g1`, `DASExtension::das_fft_extension` |
 //! | [`fk20::MiFK20SingleSettings`], [`fk20::MiFK20MultiSettings`] | — (device handle) | `FK20SingleSettings` / `FK20MultiSettings::data_availability[_optimized]` (-> `kzgamd_fk20_da`) |
 //! | [`kzg_settings::MiKZGSettings`] | — (own fields)  | `KZGSettings::new` (builds the device table), `commit_to_poly`, `compute_proof_single` |
+//! | [`poly::MiPolyExt`] on `MiFFTSettings` | — (device handle per call) | `FFTSettingsPoly::poly_mul_fft` with settings, `poly_mul` / `poly_inverse` / `poly_div` / `poly_eval_many` (-> `kzgamd_poly_*`) |
 //!
 //! Mirrors blst/src/types/{g1,fft_settings,kzg_settings}.rs method for method; every other method delegates to
 //! the wrapped blst type.  Not compiled in the build image: see Cargo.toml.
@@ -20,10 +21,12 @@ pub mod fft_settings;
 pub mod fk20;
 pub mod g1;
 pub mod kzg_settings;
+pub mod poly;
 
 pub use backend::MiBackend;
 pub use fft_settings::MiFFTSettings;
 pub use fk20::{MiFK20MultiSettings, MiFK20SingleSettings};
 pub use g1::MiG1;
 pub use kzg_settings::MiKZGSettings;
+pub use poly::MiPolyExt;
 pub use rust_kzg_blst::types::{fp::FsFp, fr::FsFr, g2::FsG2, poly::FsPoly};

@@ -74,6 +74,22 @@ extern "C" {
                        npoly: usize, xs: *const blst_fr, nx: usize, n: usize) -> c_int;
     fn kzgamd_kzg_check(kz: *mut c_void, ok: *mut bool, commitments: *const blst_p1, proofs: *const blst_p1,
                         xs: *const blst_fr, ys: *const blst_fr, n: usize, count: usize) -> c_int;
+
+    fn kzgamd_poly_new(ntt: *mut c_void, cfg: *const KzgAmdConfig, err: *mut c_int) -> *mut c_void;
+    fn kzgamd_poly_free(ph: *mut c_void);
+    fn kzgamd_poly_info(ph: *mut c_void, max_width: *mut usize, eval_chunk: *mut usize, mul_direct_max: *mut usize,
+                        inv_direct_max: *mut usize) -> c_int;
+    fn kzgamd_poly_eval(ph: *mut c_void, ys: *mut blst_fr, polys: *const blst_fr, len: usize, npoly: usize,
+                        xs: *const blst_fr, nx: usize) -> c_int;
+    fn kzgamd_poly_scale(ph: *mut c_void, out: *mut blst_fr, input: *const blst_fr, len: usize, npoly: usize,
+                         inverse: c_int) -> c_int;
+    fn kzgamd_poly_mul(ph: *mut c_void, out: *mut blst_fr, a: *const blst_fr, la: usize, b: *const blst_fr, lb: usize,
+                       out_len: usize, npoly: usize, form: c_int) -> c_int;
+    fn kzgamd_poly_inverse(ph: *mut c_void, out: *mut blst_fr, b: *const blst_fr, lb: usize, out_len: usize,
+                           npoly: usize) -> c_int;
+    fn kzgamd_poly_div(ph: *mut c_void, q: *mut blst_fr, a: *const blst_fr, la: usize, b: *const blst_fr, lb: usize,
+                       npoly: usize) -> c_int;
+    fn kzgamd_poly_transform_len(op: c_int, la: usize, lb: usize, out_len: usize) -> usize;
 }
 
 fn check(err: RustError, what: &str) -> Result<(), String> {
@@ -479,6 +495,135 @@ impl GpuKzg {
 impl Drop for GpuKzg {
     fn drop(&mut self) {
         unsafe { kzgamd_kzg_free(self.ctx) }
+    }
+}
+
+/// Batched polynomial arithmetic handle (`kzgamd_poly_new`): the reference's `Poly<Fr>` and `FFTSettingsPoly`
+/// (blst/src/types/poly.rs) over a `GpuNtt` — eval, scale / unscale, mul, inverse, div for `npoly` polynomials of one
+/// shape per call (contiguous, Montgomery).  Holds the NTT handle alive: the C handle keeps it by pointer and must be
+/// freed first (field order = drop order).  Errors carry the reference's messages.
+pub struct GpuPoly {
+    ctx: *mut c_void,
+    _ntt: std::sync::Arc<GpuNtt>,
+}
+unsafe impl Send for GpuPoly {}
+unsafe impl Sync for GpuPoly {} // calls on one handle take turns inside the library
+
+impl core::fmt::Debug for GpuPoly {
+    fn fmt(&self, f: &mut core::fmt::Formatter<'_>) -> core::fmt::Result {
+        write!(f, "GpuPoly {{ max_width: {} }}", self.info().0)
+    }
+}
+
+/// Which product `GpuPoly::mul` runs: all give the same elements.
+#[derive(Debug, Clone, Copy, PartialEq, Eq)]
+pub enum PolyMulForm {
+    Auto = 0,
+    Direct = 1,
+    Transform = 2,
+}
+
+const POLY_TOO_WIDE: &str = "Supplied list is longer than the available max width";
+
+impl GpuPoly {
+    pub fn new(ntt: std::sync::Arc<GpuNtt>, cfg: Option<&KzgAmdConfig>) -> Result<Self, String> {
+        let mut err: c_int = 0;
+        let cfg_ptr = cfg.map_or(core::ptr::null(), |c| c as *const KzgAmdConfig);
+        let ctx = unsafe { kzgamd_poly_new(ntt.ctx, cfg_ptr, &mut err) };
+        if ctx.is_null() {
+            return Err(format!("kzgamd_poly_new failed: {err}"));
+        }
+        Ok(Self { ctx, _ntt: ntt })
+    }
+
+    /// `Poly::eval` of every polynomial at every x: ys[b * xs.len() + k] = p_b(x_k).
+    pub fn eval(&self, polys: &[blst_fr], len: usize, npoly: usize, xs: &[blst_fr]) -> Result<Vec<blst_fr>, String> {
+        if polys.len() != len * npoly {
+            return Err(String::from("polys must hold npoly * len coefficients"));
+        }
+        let mut ys = vec![blst_fr::default(); npoly * xs.len()];
+        match unsafe { kzgamd_poly_eval(self.ctx, ys.as_mut_ptr(), polys.as_ptr(), len, npoly, xs.as_ptr(), xs.len()) } {
+            0 => Ok(ys),
+            e => Err(format!("GPU poly eval failed: {e}")),
+        }
+    }
+
+    /// `Poly::scale` (coefficient i times 5^-(i+1)) or, with `inverse`, `Poly::unscale`.
+    pub fn scale(&self, polys: &[blst_fr], len: usize, npoly: usize, inverse: bool) -> Result<Vec<blst_fr>, String> {
+        if polys.len() != len * npoly {
+            return Err(String::from("polys must hold npoly * len coefficients"));
+        }
+        let mut out = vec![blst_fr::default(); polys.len()];
+        match unsafe { kzgamd_poly_scale(self.ctx, out.as_mut_ptr(), polys.as_ptr(), len, npoly, inverse as c_int) } {
+            0 => Ok(out),
+            e => Err(format!("GPU poly scale failed: {e}")),
+        }
+    }
+
+    /// The first `out_len` coefficients of a_b * b_b (`Poly::mul`, `mul_direct`, `mul_fft`).
+    pub fn mul(&self, a: &[blst_fr], la: usize, b: &[blst_fr], lb: usize, out_len: usize, npoly: usize,
+               form: PolyMulForm) -> Result<Vec<blst_fr>, String> {
+        if a.len() != la * npoly || b.len() != lb * npoly {
+            return Err(String::from("a and b must hold npoly * la and npoly * lb coefficients"));
+        }
+        let mut out = vec![blst_fr::default(); npoly * out_len];
+        match unsafe {
+            kzgamd_poly_mul(self.ctx, out.as_mut_ptr(), a.as_ptr(), la, b.as_ptr(), lb, out_len, npoly, form as c_int)
+        } {
+            0 => Ok(out),
+            4 => Err(String::from(POLY_TOO_WIDE)),
+            e => Err(format!("GPU poly mul failed: {e}")),
+        }
+    }
+
+    /// `Poly::inverse`: the first `out_len` coefficients of 1 / b_b as a power series.
+    pub fn inverse(&self, b: &[blst_fr], lb: usize, out_len: usize, npoly: usize) -> Result<Vec<blst_fr>, String> {
+        if b.len() != lb * npoly {
+            return Err(String::from("b must hold npoly * lb coefficients"));
+        }
+        let mut out = vec![blst_fr::default(); npoly * out_len];
+        match unsafe { kzgamd_poly_inverse(self.ctx, out.as_mut_ptr(), b.as_ptr(), lb, out_len, npoly) } {
+            0 => Ok(out),
+            1 => Err(String::from("Can't produce a zero-length result")),
+            2 => Err(String::from("Can't inverse a zero-length poly")),
+            3 => Err(String::from("First coefficient of polynomial mustn't be zero")),
+            4 => Err(String::from(POLY_TOO_WIDE)),
+            e => Err(format!("GPU poly inverse failed: {e}")),
+        }
+    }
+
+    /// `Poly::div`: npoly quotients of la - lb + 1 coefficients each (none when la < lb).
+    pub fn div(&self, a: &[blst_fr], la: usize, b: &[blst_fr], lb: usize, npoly: usize) -> Result<Vec<blst_fr>, String> {
+        if a.len() != la * npoly || b.len() != lb * npoly {
+            return Err(String::from("a and b must hold npoly * la and npoly * lb coefficients"));
+        }
+        let qlen = if la >= lb { la - lb + 1 } else { 0 };
+        let mut q = vec![blst_fr::default(); npoly * qlen];
+        match unsafe { kzgamd_poly_div(self.ctx, q.as_mut_ptr(), a.as_ptr(), la, b.as_ptr(), lb, npoly) } {
+            0 => Ok(q),
+            1 => Err(String::from("Can't divide by zero")),
+            2 => Err(String::from("Highest coefficient must be non-zero")),
+            4 => Err(String::from(POLY_TOO_WIDE)),
+            e => Err(format!("GPU poly div failed: {e}")),
+        }
+    }
+
+    /// (max_width, eval_chunk, mul_direct_max, inv_direct_max)
+    pub fn info(&self) -> (usize, usize, usize, usize) {
+        let (mut a, mut b, mut c, mut d) = (0usize, 0usize, 0usize, 0usize);
+        unsafe { kzgamd_poly_info(self.ctx, &mut a, &mut b, &mut c, &mut d) };
+        (a, b, c, d)
+    }
+
+    /// The longest transform a call of this shape enqueues (0: none); op 0 mul by transforms, 1 inverse, 2 div.  Host-only.
+    pub fn transform_len(op: i32, la: usize, lb: usize, out_len: usize) -> usize {
+        unsafe { kzgamd_poly_transform_len(op as c_int, la, lb, out_len) }
+    }
+}
+
+impl Drop for GpuPoly {
+    fn drop(&mut self) {
+        unsafe { kzgamd_poly_free(self.ctx) }
     }
 }
 
