@@ -71,6 +71,28 @@ FF_HD constexpr u32 pad_l(int i) {
     return K == 2 ? t2[i] : K == 4 ? t4[i] : K == 8 ? t8[i] : K == 16 ? t16[i] : t32[i];
 }
 
+// K*p with B units borrowed from the limb above into each of the limbs 0..12: limb 0 is (K*p)_0 + B*2^28, limbs 1..12
+// are (K*p)_i + B*2^28 - B >= B*(2^28 - 1), the top limb is (K*p)_13 - B.  B normalized values can be subtracted from
+// it limb-wise without a limb going negative (pad_l<K> is the B = 1 case as a table).
+struct PadW {
+    u32 v[L];
+};
+template <int K, int B>
+FF_HD constexpr PadW padw() {
+    PadW r{};
+    u64 c = 0;
+    for (int i = 0; i < L; ++i) {
+        c += (u64)K * pl(i);
+        r.v[i] = i < L - 1 ? ((u32)c & MASK) : (u32)c;
+        c >>= 28;
+    }
+    for (int i = 0; i < L - 1; ++i) {
+        r.v[i] += (u32)B << 28;
+        r.v[i + 1] -= (u32)B;
+    }
+    return r;
+}
+
 FF_HD Fe zero() {
     Fe r;
 #pragma unroll
@@ -135,6 +157,39 @@ FF_HD Fe neg(const Fe& a) {
     Fe r;
 #pragma unroll
     for (int i = 0; i < L; ++i) r.v[i] = pad_l<K>(i) - a.v[i];
+    norm(r);
+    return r;
+}
+
+// K*p - y + s (m = 0) or K*p - y - s (m = 0xffffffff) without a carry pass: the sign of s is a mask, (s ^ m) - m.
+// s, y normalized; K = 16: s < 2p, y < 6p; K = 8: s < p, y <= 2p.
+//   limbs 0..12: the pad limb is in [2^29 - 2, 2^28 + 2^29), so the result is in [0, 2^30 - 2]: the minus case takes
+//                two normalized limbs off >= 2^29 - 2, the plus case adds one to < 2^28 + 2^29
+//   top limb:    (16p)_13 - 2 = 0x1a010f against y_13 + s_13 <= 0x9c066 + 0x34022, (8p)_13 - 2 = 0xd0086 against
+//                0x34022 + 0x1a011: never negative, below 2^21
+//   value:       in (8p, 18p) for K = 16, in (5p, 9p) for K = 8
+// A legal operand of sqr (a column is at most 14 * 2^60 + 14 * 2^56 + a carry < 2^64; 18p * 18p < 2^392 * p = 2520 p^2),
+// and of mul / mul2_inline against a normalized operand (14 * 2^58 per column).
+template <int K>
+FF_HD Fe sub_signed_lazy(const Fe& s, const Fe& y, u32 m) {
+    static_assert(K == 8 || K == 16, "pad multiple");
+    constexpr PadW pw = padw<K, 2>();
+    Fe r;
+#pragma unroll
+    for (int i = 0; i < L; ++i) r.v[i] = pw.v[i] - y.v[i] + ((s.v[i] ^ m) - m);
+    return r;
+}
+
+// a + 8p - 2b - c with ONE carry pass (sub<8>(a, addn(add(b, b), c)) takes two).  a, b, c normalized, a arbitrary,
+// b, c < 2p.
+//   limbs 0..12: the pad limb is >= 3 * 2^28 - 3 >= 2 b_i + c_i; the sum is below 5 * 2^28, carries are at most 5
+//   top limb:    (8p)_13 - 3 = 0xd0085 against 2 b_13 + c_13 <= 3 * 0x34022: never negative
+//   value:       a + 8p - 2b - c in (a + 2p, a + 8p]; output normalized
+FF_HD Fe sub_2b_c(const Fe& a, const Fe& b, const Fe& c) {
+    constexpr PadW pw = padw<8, 3>();
+    Fe r;
+#pragma unroll
+    for (int i = 0; i < L; ++i) r.v[i] = a.v[i] + pw.v[i] - ((b.v[i] << 1) + c.v[i]);
     norm(r);
     return r;
 }

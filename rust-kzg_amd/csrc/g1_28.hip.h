@@ -116,6 +116,80 @@ FF_HD void madd(Xyzz& acc, const Fe& x2, const Fe& y2) {
     acc.zzz = mul(acc.zzz, ppp);
 }
 
+// ---- the addition of k_fbw_accum: a lane's chain of table points ----
+// What the chain's accumulator holds is kept in a register beside it, so that no addition tests ZZ for all-zero and
+// the first addition of a chain does not multiply by ZZ = ZZZ = 1:
+//   CHAIN_EMPTY   infinity (all-zero limbs)
+//   CHAIN_AFFINE  one table point: x canonical, y canonical or 2p - y, ZZ = ZZZ = one()
+//   CHAIN_XYZZ    X < 10p, Y < 6p, ZZ, ZZZ < 2p, normalized, not infinity
+constexpr ff::u32 CHAIN_EMPTY = 0, CHAIN_AFFINE = 1, CHAIN_XYZZ = 2;
+
+// acc += (x2, y2) for m = 0, acc -= (x2, y2) for m = 0xffffffff; (x2, y2) a table point (canonical, not infinity).
+// madd-2008-s on CHAIN_XYZZ, mmadd-2008-s on CHAIN_AFFINE (P = x2 - X1, R = +-y2 - Y1, ZZ3 = PP, ZZZ3 = PPP: four
+// products fewer), with two changes to madd above:
+//   - the sign goes into R, not into y2: S2 = y2 * ZZZ1 from the stored y, R = 16p - Y1 +- S2 (fp28::sub_signed_lazy:
+//     limbs < 2^30, value < 18p; 8p - Y1 +- y2 < 9p on CHAIN_AFFINE) — no negation and carry pass of y2 in front of
+//     the addition;
+//   - X3 = R^2 + 8p - 2Q - PPP in one expression with one carry pass (fp28::sub_2b_c), < 10p as in madd.
+// P = U2 + 16p - X1 (sub_lazy<16>, U2 < 2p, X1 < 10p; x2 + 4p - X1 with X1 < p on CHAIN_AFFINE): limbs < 2^28 + 2^29,
+// value < 18p.  Products: PP = P^2 and R^2 take <= 324 p^2, Q = X1 * PP <= 20 p^2, all below 2^392 * p = 2520 p^2.
+// Y3 = R*(Q + 16p - X3) + (8p - Y1)*PPP as in madd: R < 2^30 against a normalized limb, 8p - Y1 < 2^29 against a
+// normalized limb, the quotient digits against p: columns <= 14 * (4 + 2 + 1) * 2^56 = 98 * 2^56 < 2^63 (mul2_inline's
+// rule); value <= 18p * 18p + 8p * 2p = 340 p^2, so Y3 < 2p.
+// Exceptional cases as madd: equal points -> dbl_affine, opposite points -> infinity (CHAIN_EMPTY).
+FF_HD void chain_add(Xyzz& acc, ff::u32& st, const Fe& x2, const Fe& y2, ff::u32 m) {
+    using namespace fp28;
+    if (st == CHAIN_EMPTY) {
+        acc.x = x2;
+        acc.y = m ? neg<2>(y2) : y2;
+        acc.zz = one();
+        acc.zzz = one();
+        st = CHAIN_AFFINE;
+        return;
+    }
+    const bool affine = st == CHAIN_AFFINE;
+    // (the pads of the two states differ on purpose: with the same ones the compiler hoists 16p - Y1 out of both
+    // branches and R costs four instructions per limb instead of three)
+    Fe p, r;
+    if (affine) {
+        p = sub_lazy<4>(x2, acc.x);
+        r = sub_signed_lazy<8>(y2, acc.y, m);
+    } else {
+        p = sub_lazy<16>(mul(x2, acc.zz), acc.x);
+        r = sub_signed_lazy<16>(mul(y2, acc.zzz), acc.y, m);
+    }
+    if (is_zero_mod_p(p)) {
+        if (is_zero_mod_p(r)) {
+            dbl_affine(acc, x2, m ? neg<2>(y2) : y2);
+            st = CHAIN_XYZZ;
+        } else {
+            // set_inf with the stores in the order EVERY path of this function ends on (x, y, zz, zzz): the compiler
+            // merges the stores of paths that join, and where their orders differ it merges them into stores through
+            // a selected address, which keeps the accumulator in scratch memory
+            acc.x = zero();
+            acc.y = zero();
+            acc.zz = zero();
+            acc.zzz = zero();
+            st = CHAIN_EMPTY;
+        }
+        return;
+    }
+    Fe pp = sqr(p);
+    Fe ppp = mul(p, pp);
+    Fe q = mul(acc.x, pp);
+    Fe x3 = sub_2b_c(sqr(r), q, ppp);
+    Fe y3 = mul2_inline(r, sub<16>(q, x3), sub_lazy<8>(zero(), acc.y), ppp);
+    acc.x = x3;
+    acc.y = y3;
+    if (!affine) {
+        pp = mul(acc.zz, pp);
+        ppp = mul(acc.zzz, ppp);
+    }
+    acc.zz = pp;
+    acc.zzz = ppp;
+    st = CHAIN_XYZZ;
+}
+
 // acc += b   (add-2008-s) for b != acc; returns true and leaves acc alone when the two are the same point — the caller
 // doubles.  Kernels that run their additions as ONE inlined site inside a loop (k_tile_sums) keep the doubling, which
 // never runs on random data, as one site of its own instead of one per addition.

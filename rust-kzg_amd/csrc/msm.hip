@@ -1681,6 +1681,7 @@ __global__ void __launch_bounds__(256) k_fbw_accum(DigitParams P, const u32* __r
     if (GLV) l >>= 1;
     Xyzz acc;
     g1::set_inf(acc);
+    u32 st = g1::CHAIN_EMPTY;  // what acc holds (g1::chain_add): nothing, one table point, a sum
     const u32 half = 1u << (P.c - 1);
     const int sh = P.c - 1;
     const size_t seg0 = P.nseg ? (b % P.nseg) * P.n : 0;  // first table base of this MSM
@@ -1702,9 +1703,7 @@ __global__ void __launch_bounds__(256) k_fbw_accum(DigitParams P, const u32* __r
                     if (e == FBW_SKIP) continue;
                     const WidePt pk = wide[(((size_t)(w4 + q) * P.row_stride + seg0 + i) << sh) + (e & 0x7fffffffu)];
                     if (pk.pad[0]) continue;  // multiple of a base at infinity
-                    fp28::Fe x = pk.x, y = pk.y;
-                    if (e >> 31) y = fp28::neg<2>(y);
-                    g1::madd(acc, x, y);
+                    g1::chain_add(acc, st, pk.x, pk.y, 0u - (e >> 31));
                 }
             }
         } else {
@@ -1723,13 +1722,11 @@ __global__ void __launch_bounds__(256) k_fbw_accum(DigitParams P, const u32* __r
                 if (d == 0) continue;
                 const WidePt pk = wide[(((size_t)w * P.row_stride + seg0 + i) << sh) + (d - 1)];
                 if (pk.pad[0]) continue;  // multiple of a base at infinity
-                fp28::Fe x = pk.x, y = pk.y;
-                if (neg) y = fp28::neg<2>(y);
-                g1::madd(acc, x, y);
+                g1::chain_add(acc, st, pk.x, pk.y, 0u - neg);
             }
         }
     }
-    if (GLV && part && !g1::is_inf(acc)) {
+    if (GLV && part && st != g1::CHAIN_EMPTY) {
         acc.x = fp28::mul(acc.x, beta28());                     // psi(X, Y, ZZ, ZZZ) = (beta X, -Y, ZZ, ZZZ)
         acc.y = fp28::mul(fp28::neg<8>(acc.y), fp28::one());    // -Y, back under the 2p bound
     }
