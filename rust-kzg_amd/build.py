@@ -11,6 +11,16 @@ HEADERS = ["ff.hip.h", "fp28.hip.h", "g1_28.hip.h", "g1_io.hip.h", "msm_internal
            os.path.join("..", "..", "include", "kzg_mi355x.h")]
 
 
+# the compiler and the flags every device translation unit of the product is compiled with; the test-only device harness
+# (tests/device_checks/) takes them from here, so that it exercises the headers as the library compiles them
+HIPCC_DEFAULT = "/opt/rocm/bin/hipcc"
+COMPILE_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17"]
+
+
+def hipcc_path():
+    return os.environ.get("HIPCC", HIPCC_DEFAULT)
+
+
 # what the last build() / build_exact() / build_prefixed() of this process did, per library file name: "reused (content stamp
 # matches the sources)" or "compiled: <sources>; linked" — __graft_entry__.build() prints it, so that a build record says
 # whether hipcc ran
@@ -113,7 +123,7 @@ def _stamp_matches(lib, defines):
 def _compile_and_link(lib, tag, defines, force, verbose):
     """Objects <source><tag>.o (parallel hipcc, rebuilt by their .d files) -> lib; then the content stamp."""
     srcs = [s for s in SOURCES if os.path.exists(os.path.join(CSRC, s))]
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    hipcc = hipcc_path()
     want = _content_hash(defines)  # before compiling: an edit during the compilation makes the stamp stale, as it should
     objs = []
     procs = []
@@ -122,7 +132,7 @@ def _compile_and_link(lib, tag, defines, force, verbose):
         objs.append(o)
         if not force and not _obj_stale(os.path.join(CSRC, s), o):
             continue
-        cmd = [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"] + defines + ["-MD", "-MF", o[:-2] + ".d", "-c", os.path.join(CSRC, s), "-o", o]
+        cmd = [hipcc] + COMPILE_FLAGS + ["-fPIC"] + defines + ["-MD", "-MF", o[:-2] + ".d", "-c", os.path.join(CSRC, s), "-o", o]
         if verbose:
             print(" ".join(cmd))
         procs.append((s, subprocess.Popen(cmd, cwd=CSRC)))

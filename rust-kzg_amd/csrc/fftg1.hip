@@ -82,13 +82,18 @@ __global__ void __launch_bounds__(256) k_g1_load(Xyzz* __restrict__ out, const f
     out[t] = p;
 }
 
-// device-resident form: XYZZ in natural order -> bit-reversed order of each transform
+// device-resident form: XYZZ in natural order -> bit-reversed order of each transform.  The input may have been stored by
+// the limb-parallel folds of msm.hip (the OUT_XYZZ sums of a wide-table MSM: X, Y < 18p), and the single-lane stage
+// kernels negate and double what they load (fp28::neg<8>, g1::dbl: Y <= 8p): this copy is the boundary, X and Y leave it
+// below 2p (two multiplications per point in front of ~170 point operations per butterfly).
 __global__ void __launch_bounds__(256) k_g1_brp_xyzz(Xyzz* __restrict__ out, const Xyzz* __restrict__ in, u32 n, int logn,
                                                      size_t total) {
     const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= total) return;
     const size_t xf = t / n;
-    out[t] = in[xf * n + brev((u32)(t % n), logn)];
+    Xyzz p = in[xf * n + brev((u32)(t % n), logn)];
+    g1::reduce_xy(p);
+    out[t] = p;
 }
 
 // ---------------------------------------------------------------- the chain kernels: 1, 2 or 4 lanes per half-butterfly

@@ -7,6 +7,11 @@
 //
 // Value bounds carried between calls (see fp28.hip.h): X < 10p, Y < 6p, ZZ, ZZZ < 2p (dbl and dadd also take Y <= 8p:
 // a negated input; madd does not).
+// A point the limb-parallel code stored (g1w.hip.h: X, Y < 18p, exactly normalized) may be passed wherever X and Y only
+// feed multiplications: as b of dadd / dadd_unequal, as acc of dadd / dadd_unequal when b is a different point (equal
+// points end in dbl: Y <= 8p), to dbl_k and to to_blst_jacobian.  dbl, madd, chain_add and a negation of Y (fp28::neg<8>)
+// need the bounds above: reduce_xy first.  (DESIGN.md has the table of producers and consumers; tests/lane_model.py,
+// boundary_cases, pins each consumer at X, Y just under 18p.)
 #pragma once
 #include "fp28.hip.h"
 
@@ -48,6 +53,14 @@ FF_HD void set_affine(Xyzz& p, const Fe& x, const Fe& y) {
     p.y = y;
     p.zzz = fp28::one();
     p.zz = fp28::one();
+}
+
+// X, Y of a point the limb-parallel code stored (g1w.hip.h lets them grow to 18p) back under 2p, for the routines below
+// that negate or double what they load: a multiplication by one each, value unchanged; infinity stays all-zero
+FF_HD void reduce_xy(Xyzz& p) {
+    const Fe o = fp28::one();
+    p.x = fp28::mul(p.x, o);
+    p.y = fp28::mul(p.y, o);
 }
 
 // 2 * (x2, y2)  (mdbl-2008-s-1)
