@@ -631,8 +631,8 @@ C_KZG_RET guarded(F&& f) {
         f();
         return C_KZG_OK;
     } catch (const CkErr& e) {
-        static const bool debug = getenv("KZGAMD_DEBUG") != nullptr;
-        if (debug) fprintf(stderr, "kzg_mi355x: %s\n", e.what.c_str());
+        // read when a call fails, not once per process: a caller (or a test) can turn the texts on for one call
+        if (getenv("KZGAMD_DEBUG") != nullptr) fprintf(stderr, "kzg_mi355x: %s\n", e.what.c_str());
         return e.rc == C_KZG_MALLOC ? C_KZG_MALLOC : C_KZG_BADARGS;  // the reference maps every failure to BadArgs
     } catch (const std::bad_alloc&) {
         return C_KZG_MALLOC;

@@ -4,8 +4,8 @@
 //   KZGAMD_TUNING       "key=value;key=value": the same string a caller puts in KzgAmdConfig.tuning (measurement tools)
 //   KZGAMD_FBW_MAX_GB   table budget per fixed-base table, when the caller passed none
 //   KZGAMD_VERBOSE      say on stderr what shape a prepared handle ended up with
-//   KZGAMD_DEBUG        say on stderr why a c-kzg entry point returned C_KZG_BADARGS
-// Order of precedence: defaults < environment < KzgAmdConfig.  Values are read ONCE, when a handle is created.
+//   KZGAMD_DEBUG        say on stderr why a c-kzg entry point returned C_KZG_BADARGS (looked up when a call fails)
+// Order of precedence: defaults < environment < KzgAmdConfig.  The first three are read ONCE, when a handle is created.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>

@@ -621,7 +621,6 @@ def _g1_encodings(L, O, rnd):
             for sign in (0, 0x20):
                 enc.append(bytes([0x80 | sign | (x >> 376)]) + (x & ((1 << 376) - 1)).to_bytes(47, "big"))
             outside += 1
-    valid = len(enc)
     good = enc[5]
     bad = [
         bytes([good[0] & 0x7F]) + good[1:],                 # compression flag missing
@@ -636,33 +635,21 @@ def _g1_encodings(L, O, rnd):
         rhs = (pow(x, 3, O.P) + 4) % O.P
         if pow(rhs, (O.P - 1) // 2, O.P) != 1:
             bad.append(bytes([0x80]) + x.to_bytes(47, "big"))
-    enc += bad
+    # tests/g1_encodings.py on top: low-order and torsion points, every flag combination, the range edges
+    import g1_encodings
+
+    cat = g1_encodings.catalogue()
+    enc += [b for _, b, cls in cat if cls != 1]
+    valid = len(enc)
+    enc += bad + [b for _, b, cls in cat if cls == 1]
     return enc, valid
 
 
-def test_host_g1_serialisation_and_subgroup_test_against_the_oracle(tmp_path, oracle):
-    """csrc/host_g1.h (the host side of bytes_to_kzg_commitment, compute_challenge's commitment, commitment checks of
-    small proof batches, the Horner tail of variable-base host calls): uncompress / compress / batch compress, the
-    Jacobian doubling and addition with their exceptional cases, and the endomorphism subgroup test, against the oracle
-    on points of G1, curve points outside G1 and every class of invalid encoding (FsG1::from_bytes,
-    blst/src/types/g1.rs:65-87)."""
-    import random
+def build_g1check(tmp_path):
+    """the stand-alone program over csrc/host_g1.h: per line of compressed hex on stdin `bad` or `ok <in G1> <compressed
+    again>`, then the doublings and sums of the decoded points through the batch compression"""
     import shutil
     import subprocess
-
-    import oracle_ffi as O
-
-    L = oracle.lib()
-    rnd = random.Random(404)
-    g = O.G1()
-    L.og1_generator(C.byref(g))
-
-    def comp(p):
-        buf = C.create_string_buffer(48)
-        L.og1_compress(buf, C.byref(p))
-        return buf.raw
-
-    enc, valid = _g1_encodings(L, O, rnd)
 
     cxx = shutil.which("g++") or shutil.which("clang++") or "/opt/rocm/lib/llvm/bin/clang++"
     src = tmp_path / "g1check.cpp"
@@ -710,6 +697,34 @@ int main() {
 ''')
     exe = tmp_path / "g1check"
     subprocess.check_call([cxx, "-O2", "-std=c++17", "-I", os.path.join(ROOT, "rust-kzg_amd", "csrc"), str(src), "-o", str(exe)])
+    return exe
+
+
+def test_host_g1_serialisation_and_subgroup_test_against_the_oracle(tmp_path, oracle):
+    """csrc/host_g1.h (the host side of bytes_to_kzg_commitment, compute_challenge's commitment, commitment checks of
+    small proof batches, the Horner tail of variable-base host calls): uncompress / compress / batch compress, the
+    Jacobian doubling and addition with their exceptional cases, and the endomorphism subgroup test, against the oracle
+    on points of G1, curve points outside G1 and every class of invalid encoding (FsG1::from_bytes,
+    blst/src/types/g1.rs:65-87)."""
+    import random
+    import shutil
+    import subprocess
+
+    import oracle_ffi as O
+
+    L = oracle.lib()
+    rnd = random.Random(404)
+    g = O.G1()
+    L.og1_generator(C.byref(g))
+
+    def comp(p):
+        buf = C.create_string_buffer(48)
+        L.og1_compress(buf, C.byref(p))
+        return buf.raw
+
+    enc, valid = _g1_encodings(L, O, rnd)
+
+    exe = build_g1check(tmp_path)
     out = subprocess.run([str(exe)], input="\n".join(e.hex() for e in enc) + "\n", capture_output=True, text=True, check=True).stdout.split("\n")
     heads, sums = [ln for ln in out if ln and not ln.startswith("c ")], [ln[2:] for ln in out if ln.startswith("c ")]
     assert len(heads) == len(enc)
@@ -728,7 +743,10 @@ int main() {
         assert int(in_g1) == L.og1_in_subgroup(C.byref(p)), (i, e.hex())
         assert again == e.hex() == comp(p).hex(), i
         pts.append(p)
-    assert sum(1 for ln in heads if ln.startswith("ok 0")) == 12  # the six outside points, both signs
+    import g1_encodings
+
+    # the six outside points, both signs, and the catalogue's
+    assert sum(1 for ln in heads if ln.startswith("ok 0")) == 12 + len(g1_encodings.by_class(2))
     assert len(sums) == 5 * len(pts)
     for i, a in enumerate(pts):
         b = pts[(i + 1) % len(pts)]
@@ -1224,19 +1242,12 @@ int main() {
         assert got == want, line.split()[0] + " " + line.split()[-1]
 
 
-def test_device_g1_serialisation_code_against_the_oracle_on_the_host(tmp_path, oracle):
-    """g1_io.hip.h — what k_uncompress / k_decode_check_g1 and the compressed output mode of the MSM's last kernel run per
-    point — compiled for the host: the same encodings as the host_g1.h test (valid, outside G1, every invalid class) are
-    accepted or refused as the oracle does, accepted ones compress back to themselves, and a point with non-trivial
-    ZZ / ZZZ (its double) compresses to the oracle's bytes (the inversion behind it included)."""
-    import random
+def build_g1io(tmp_path):
+    """the stand-alone program over csrc/g1_io.hip.h compiled for the host: per line of compressed hex on stdin `bad` or
+    `ok <compressed again> <its double, compressed> <affpt_in_g1>`"""
     import shutil
     import subprocess
 
-    import oracle_ffi as O
-
-    L = oracle.lib()
-    enc, valid = _g1_encodings(L, O, random.Random(404))
     cxx = shutil.which("g++") or shutil.which("clang++") or "/opt/rocm/lib/llvm/bin/clang++"
     src = tmp_path / "g1io.cpp"
     src.write_text(r'''
@@ -1261,20 +1272,37 @@ int main() {
         hex(c);
         printf(" ");
         hex(c2);
-        printf("\n");
+        printf(" %d\n", g1io::affpt_in_g1(a) ? 1 : 0);
     }
     return 0;
 }
 ''')
     exe = tmp_path / "g1io"
     subprocess.check_call([cxx, "-O1", "-std=c++17", "-I", os.path.join(ROOT, "rust-kzg_amd", "csrc"), str(src), "-o", str(exe)])
+    return exe
+
+
+def test_device_g1_serialisation_code_against_the_oracle_on_the_host(tmp_path, oracle):
+    """g1_io.hip.h — what k_uncompress / k_decode_check_g1 and the compressed output mode of the MSM's last kernel run per
+    point — compiled for the host: the same encodings as the host_g1.h test (valid, outside G1, every invalid class) are
+    accepted or refused as the oracle does, accepted ones compress back to themselves, and a point with non-trivial
+    ZZ / ZZZ (its double) compresses to the oracle's bytes (the inversion behind it included)."""
+    import random
+    import shutil
+    import subprocess
+
+    import oracle_ffi as O
+
+    L = oracle.lib()
+    enc, valid = _g1_encodings(L, O, random.Random(404))
+    exe = build_g1io(tmp_path)
     out = subprocess.run([str(exe)], input="\n".join(e.hex() for e in enc) + "\n", capture_output=True, text=True, check=True).stdout.strip().split("\n")
     assert len(out) == len(enc)
     for i, (e, ln) in enumerate(zip(enc, out)):
         assert (ln != "bad") == (i < valid), (i, e.hex(), ln)
         if ln == "bad":
             continue
-        _, again, doubled = ln.split()
+        _, again, doubled, in_g1 = ln.split()
         assert again == e.hex(), i
         a, p, d = O.G1Affine(), O.G1(), O.G1()
         assert L.og1_uncompress(C.byref(a), e)
@@ -1284,3 +1312,4 @@ int main() {
         buf = C.create_string_buffer(48)
         L.og1_compress(buf, C.byref(d))
         assert doubled == buf.raw.hex(), i
+        assert int(in_g1) == L.og1_in_subgroup(C.byref(p)), (i, e.hex())  # affpt_in_g1, the single-lane membership test
