@@ -305,6 +305,48 @@ int kzgamd_poly_div(void *ph, blst_fr *q, const blst_fr *a, size_t la, const bls
  * this.  Never more than next_pow2(min(la, out_len) + min(lb, out_len) - 1) for mul and next_pow2(2 L - 1) for inverse
  * (L = out_len) and div (L = la - lb + 1): the reference's own lengths (poly.rs:341, :109). */
 size_t kzgamd_poly_transform_len(int op, size_t la, size_t lb, size_t out_len);
+/* Zero polynomials and sample recovery, the reference's ZeroPoly and PolyRecover (kzg/src/lib.rs:433-463, 535-545;
+ * blst/src/zero_poly.rs, blst/src/recovery.rs) on the poly handle (rust-kzg_amd/csrc/zeropoly.hip), with the conventions
+ * of kzgamd_poly_*.  Positive codes are tested in the order listed; on a positive code nothing is written.  Every output
+ * is a field element with one value — a monic product of linear factors, its transform, a pointwise quotient whose
+ * divisor is never zero (5 is not a 2^k-th root of unity) — so results equal the reference's element for element.
+ * roots[] below is the handle's roots_of_unity table (kzgamd_ntt_roots), max_width + 1 entries.
+ *
+ * kzgamd_poly_zero_partial: out[0 .. nidx] = the nidx + 1 coefficients of prod_k (X - roots[idxs[k] * stride]), lowest
+ * first (do_zero_poly_mul_partial, for any nidx; repeated indices allowed).  1: nidx == 0, 2: some idxs[k] * stride >
+ * max_width, 4: the product needs a transform longer than the max width. */
+int kzgamd_poly_zero_partial(void *ph, blst_fr *out, const uint64_t *idxs, size_t nidx, size_t stride);
+/* out = the sum(lens[k] - 1) + 1 coefficients of the product of npartial polynomials stored back to back in `partials`
+ * (reduce_partials; any coefficients, monic or not).  1: domain_size is not a power of two, 2: npartial == 0,
+ * 5: some lens[k] == 0, 3: out degree + 1 > domain_size, 4: domain_size > max width. */
+int kzgamd_poly_reduce_partials(void *ph, blst_fr *out, size_t domain_size, const blst_fr *partials, const size_t *lens,
+                                size_t npartial);
+/* zero_poly_via_multiplication for nprob index lists in one call: problem b has missing[offsets[b] .. offsets[b+1]).
+ * zero_poly[b * domain_size ..] = prod (X - w^idx), zero-padded to domain_size, w = roots[max_width / domain_size];
+ * zero_eval[b * domain_size ..] = its forward transform.  Either output may be NULL.  1: a list has >= domain_size
+ * entries, 2: domain_size > max width, 3: domain_size is not a power of two (0 included), 5: an index >= domain_size.
+ * An empty list gives the empty product (zero_poly = 1, 0, 0, ...; zero_eval all ones); nprob = 0: ok, nothing
+ * written.  form 0: chosen by shape, 1: direct (a lane per domain point multiplies out Z(w^t); one inverse transform),
+ * 2: product tree (a wave per 64 roots, then one batched pair of transforms per level).  All forms give the same
+ * elements. */
+int kzgamd_poly_zero_poly(void *ph, blst_fr *zero_eval, blst_fr *zero_poly, size_t domain_size, const uint64_t *missing,
+                          const size_t *offsets /* nprob + 1 */, size_t nprob, int form);
+/* nprob sample vectors of n elements; present[b * n + i] == 0 marks a missing sample, whose value is never used.
+ * coeffs != 0: recover_poly_coeffs_from_samples, coeffs == 0: recover_poly_from_samples.  Defined for any sample
+ * values: with Z the zero polynomial of the missing set, E the samples with zeros in the gaps and s_k(p) the map
+ * coefficient i -> p_i k^i (exponent i, NOT the i + 1 of kzgamd_poly_scale), the coefficient form is
+ * s_5(ifft(fft(s_1/5(ifft(E . fft Z))) / fft(s_1/5(Z)))).  1: n is not a power of two (0 included), 2: a vector has more
+ * than n / 2 missing, 3: n > max width.  No missing sample: ifft(samples), or the samples.  Any n up to the max width. */
+int kzgamd_poly_recover(void *ph, blst_fr *out, const blst_fr *samples, const uint8_t *present, size_t n, size_t nprob,
+                        int coeffs);
+/* the roots a wave of the leaf kernel takes, and the largest list of a call for which form 0 of kzgamd_poly_zero_poly
+ * (and kzgamd_poly_recover) takes the direct form (0 in this build: the tree measured level or ahead at every size, the
+ * direct form is form 1 only); any pointer may be NULL */
+int kzgamd_poly_zero_info(void *ph, size_t *leaf_roots, size_t *direct_max);
+/* host-only, no GPU: the levels the tree form runs for `count` roots, levels[3 * l ..] = {polynomials entering the
+ * level, coefficients of each below its leading 1 (the last may have fewer), transform length}.  Returns the number of
+ * levels, ceil(log2(ceil(count / leaf_roots))), at most 32.  The longest transform is never more than next_pow2(count + 1). */
+size_t kzgamd_poly_zero_plan(size_t count, size_t *levels /* 32 x 3 */);
 /* The tile plan the NTT kernel runs for (kind, T) — host-only, no GPU needed (rust-kzg_amd/csrc/ntt_plan.h):
  * kind 0 = whole transform of 2^T <= 4096 points, 1 = first pass of a longer one, 2 = later pass; rounds[4*r..] =
  * {first stage, stages, barrier after, element bit}; tab[(r*1024 + thread)*4..] = {idxA, idxB, lds(idxA), lds(idxB)}.

@@ -69,6 +69,8 @@ EXPORTS = [
     "kzgamd_kzg_new", "kzgamd_kzg_free", "kzgamd_kzg_info", "kzgamd_kzg_commit", "kzgamd_kzg_open", "kzgamd_kzg_check",
     "kzgamd_poly_new", "kzgamd_poly_free", "kzgamd_poly_info", "kzgamd_poly_eval", "kzgamd_poly_scale", "kzgamd_poly_mul",
     "kzgamd_poly_inverse", "kzgamd_poly_div", "kzgamd_poly_transform_len",
+    "kzgamd_poly_zero_partial", "kzgamd_poly_reduce_partials", "kzgamd_poly_zero_poly", "kzgamd_poly_recover",
+    "kzgamd_poly_zero_info", "kzgamd_poly_zero_plan",
     "load_trusted_setup", "load_trusted_setup_file", "free_trusted_setup", "blob_to_kzg_commitment",
     "compute_kzg_proof", "compute_blob_kzg_proof", "kzgamd_compute_blob_kzg_proof_batch", "compute_challenge",
     "bytes_to_kzg_commitment", "bytes_from_bls_field", "compute_cells_and_kzg_proofs",
@@ -251,6 +253,18 @@ def lib():
     L.kzgamd_poly_div.argtypes = [vp, vp, vp, sz, vp, sz, sz]
     L.kzgamd_poly_transform_len.restype = sz
     L.kzgamd_poly_transform_len.argtypes = [C.c_int, sz, sz, sz]
+    L.kzgamd_poly_zero_partial.restype = C.c_int
+    L.kzgamd_poly_zero_partial.argtypes = [vp, vp, C.POINTER(C.c_uint64), sz, sz]
+    L.kzgamd_poly_reduce_partials.restype = C.c_int
+    L.kzgamd_poly_reduce_partials.argtypes = [vp, vp, sz, vp, C.POINTER(sz), sz]
+    L.kzgamd_poly_zero_poly.restype = C.c_int
+    L.kzgamd_poly_zero_poly.argtypes = [vp, vp, vp, sz, C.POINTER(C.c_uint64), C.POINTER(sz), sz, C.c_int]
+    L.kzgamd_poly_recover.restype = C.c_int
+    L.kzgamd_poly_recover.argtypes = [vp, vp, vp, C.POINTER(C.c_uint8), sz, sz, C.c_int]
+    L.kzgamd_poly_zero_info.restype = C.c_int
+    L.kzgamd_poly_zero_info.argtypes = [vp, C.POINTER(sz), C.POINTER(sz)]
+    L.kzgamd_poly_zero_plan.restype = sz
+    L.kzgamd_poly_zero_plan.argtypes = [sz, C.POINTER(sz)]
     L.kzgamd_ntt_roots.restype = C.c_int
     L.kzgamd_ntt_roots.argtypes = [vp, vp, vp, vp]
     sp = C.POINTER(CKZGSettings)
@@ -877,6 +891,15 @@ POLY_ERRORS = {
     "inverse": {1: "Can't produce a zero-length result", 2: "Can't inverse a zero-length poly",
                 3: "First coefficient of polynomial mustn't be zero"},
     "div": {1: "Can't divide by zero", 2: "Highest coefficient must be non-zero"},
+    # blst/src/zero_poly.rs, blst/src/recovery.rs; where the reference panics the message says what it trips over
+    "zero_partial": {1: "idx array must not be empty", 2: "index out of bounds: idx * stride exceeds max_width"},
+    "reduce_partials": {1: "Expected domain size to be a power of 2", 2: "partials must not be empty",
+                        3: "Out degree is longer than possible polynomial size in domain",
+                        4: "Domain size greater than fft_settings.max_width", 5: "attempt to subtract with overflow: empty partial"},
+    "zero_poly": {1: "Missing idxs greater than domain size", 2: "Domain size greater than fft_settings.max_width",
+                  3: "Domain size must be a power of 2", 5: "index out of bounds: missing idx exceeds domain size"},
+    "recover": {1: "Samples must have a length that is a power of two", 2: "Impossible to recover, too many shards are missing",
+                3: "Supplied list is longer than the available max width"},
 }
 
 
@@ -962,6 +985,76 @@ class PolySettings:
         if lib().kzgamd_poly_info(self.handle, *[C.byref(x) for x in v]) != 0:
             raise KzgAmdError("kzgamd_poly_info failed")
         return tuple(x.value for x in v)
+
+    def zero_partial(self, idxs, stride=1):
+        """do_zero_poly_mul_partial for any number of indices: the len(idxs) + 1 coefficients of
+        prod (X - roots[idx * stride]).  Returns (BlstFr * (len(idxs) + 1))."""
+        self._live()
+        n = len(idxs)
+        arr = (C.c_uint64 * max(1, n))(*idxs)
+        out = (BlstFr * (n + 1))()
+        rc = lib().kzgamd_poly_zero_partial(self.handle, out, arr, n, stride)
+        if rc != 0:
+            raise self._error("kzgamd_poly_zero_partial", rc, POLY_ERRORS["zero_partial"].get(rc))
+        return out
+
+    def reduce_partials(self, domain_size, partials, lens):
+        """reduce_partials: the product of len(lens) polynomials stored back to back in `partials` (blst_fr, Montgomery).
+        Returns (BlstFr * (sum(lens) - len(lens) + 1))."""
+        self._live()
+        m = len(lens)
+        larr = (C.c_size_t * max(1, m))(*lens)
+        out = (BlstFr * max(1, sum(lens) - m + 1))()
+        rc = lib().kzgamd_poly_reduce_partials(self.handle, out, domain_size, _addr(partials) if sum(lens) else None, larr, m)
+        if rc != 0:
+            raise self._error("kzgamd_poly_reduce_partials", rc, POLY_ERRORS["reduce_partials"].get(rc))
+        return out
+
+    def zero_poly(self, domain_size, missing_lists, form=0, want_eval=True, want_poly=True):
+        """zero_poly_via_multiplication for every index list of missing_lists in one call.  Returns (zero_eval, zero_poly),
+        each (BlstFr * (len(missing_lists) * domain_size)) or None when not wanted.  An empty list gives the empty
+        product (the reference returns two empty vectors there)."""
+        self._live()
+        nprob = len(missing_lists)
+        flat = [i for lst in missing_lists for i in lst]
+        offs = [0]
+        for lst in missing_lists:
+            offs.append(offs[-1] + len(lst))
+        marr = (C.c_uint64 * max(1, len(flat)))(*flat)
+        oarr = (C.c_size_t * (nprob + 1))(*offs)
+        ze = (BlstFr * max(1, nprob * domain_size))() if want_eval else None
+        zp = (BlstFr * max(1, nprob * domain_size))() if want_poly else None
+        rc = lib().kzgamd_poly_zero_poly(self.handle, ze, zp, domain_size, marr, oarr, nprob, form)
+        if rc != 0:
+            raise self._error("kzgamd_poly_zero_poly", rc, POLY_ERRORS["zero_poly"].get(rc))
+        return ze, zp
+
+    def recover(self, samples, present, n, nprob=1, coeffs=False):
+        """recover_poly_from_samples (coeffs=True: recover_poly_coeffs_from_samples) for nprob vectors of n samples
+        (blst_fr, Montgomery); present: nprob * n bytes, 0 marks a missing sample, whose value is never used.
+        Returns (BlstFr * (nprob * n))."""
+        self._live()
+        mask = (C.c_uint8 * max(1, nprob * n)).from_buffer_copy(bytes(present) if nprob * n else b"\0")
+        out = (BlstFr * max(1, nprob * n))()
+        rc = lib().kzgamd_poly_recover(self.handle, out, _addr(samples) if nprob * n else None, mask, n, nprob, 1 if coeffs else 0)
+        if rc != 0:
+            raise self._error("kzgamd_poly_recover", rc, POLY_ERRORS["recover"].get(rc))
+        return out
+
+    def zero_info(self):
+        """(leaf_roots, direct_max): see kzgamd_poly_zero_info"""
+        self._live()
+        v = [C.c_size_t(0) for _ in range(2)]
+        if lib().kzgamd_poly_zero_info(self.handle, *[C.byref(x) for x in v]) != 0:
+            raise KzgAmdError("kzgamd_poly_zero_info failed")
+        return tuple(x.value for x in v)
+
+    @staticmethod
+    def zero_plan(count):
+        """the levels the tree form runs for `count` roots: [(polynomials entering, coefficients each, transform length)].  No GPU."""
+        lv = (C.c_size_t * 96)()
+        k = lib().kzgamd_poly_zero_plan(count, lv)
+        return [(lv[3 * i], lv[3 * i + 1], lv[3 * i + 2]) for i in range(k)]
 
     @staticmethod
     def transform_len(op, la, lb, out_len):

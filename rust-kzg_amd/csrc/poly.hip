@@ -49,9 +49,11 @@
 #include "fr29.hip.h"
 #include "frscan.hip.h"
 #include "ntt_internal.h"
+#include "poly_internal.h"
 
 using ff::Fr;
 using ff::u32;
+using namespace kzgamd_poly;
 
 namespace {
 
@@ -66,19 +68,6 @@ struct Operand {
 };
 __device__ __forceinline__ Fr op_at(const Operand& o, size_t poly, size_t i) {
     return o.p[poly * o.stride + (o.flip ? o.len - 1 - i : i)];
-}
-
-__device__ __forceinline__ Fr shfl_xor(const Fr& a, int m) {
-    Fr r;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) r.v[i] = __shfl_xor(a.v[i], m, 64);
-    return r;
-}
-__device__ __forceinline__ Fr shfl_idx(const Fr& a, int lane) {
-    Fr r;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) r.v[i] = __shfl(a.v[i], lane, 64);
-    return r;
 }
 
 struct EvalShape {
@@ -230,60 +219,6 @@ __global__ void __launch_bounds__(256) k_poly_mul_const(Fr* __restrict__ q, cons
     if (t < total) q[t] = fr_mul(a[t], inv[t / la]);
 }
 
-struct PolyErr {
-    hipError_t e;
-};
-#define PL_TRY(x)                                \
-    do {                                         \
-        hipError_t _e = (x);                     \
-        if (_e != hipSuccess) throw PolyErr{_e}; \
-    } while (0)
-
-struct DevBuf {
-    void* p = nullptr;
-    size_t cap = 0;
-    void ensure(size_t bytes) {
-        if (bytes <= cap) return;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-        PL_TRY(hipMalloc(&p, bytes));
-        cap = bytes;
-    }
-    void drop() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-    }
-    template <class T>
-    T* as() const {
-        return (T*)p;
-    }
-};
-
-struct PolyCtx {
-    NttCtx* ntt = nullptr;
-    int device = 0;
-    std::mutex mu;
-    hipStream_t st = nullptr;
-    // workspace, grown as calls need it: operands, inverse, result, the two transform buffers, eval's points and sums
-    DevBuf a, b, c, out, f, g, xs, pw, sums, flag;
-
-    std::vector<DevBuf*> bufs() { return {&a, &b, &c, &out, &f, &g, &xs, &pw, &sums, &flag}; }
-    ~PolyCtx() {
-        for (DevBuf* d : bufs()) d->drop();
-        if (st) (void)hipStreamDestroy(st);
-    }
-};
-
-inline unsigned blocks(size_t total, unsigned per = 256) { return (unsigned)((total + per - 1) / per); }
-inline size_t next_pow2(size_t v) {
-    size_t n = 1;
-    while (n < v) n <<= 1;
-    return n;
-}
-inline size_t min_sz(size_t a, size_t b) { return a < b ? a : b; }
-
 // the transform a product by transforms runs; 0: none (an empty operand or output, or a product of two constants)
 size_t mul_transform_len(size_t la, size_t lb, size_t out_len) {
     if (!la || !lb || !out_len) return 0;
@@ -336,10 +271,6 @@ size_t div_transform_len(size_t la, size_t lb) {
     return n;
 }
 
-void ntt_on_stream(PolyCtx* pc, Fr* out, const Fr* in, size_t n, size_t nbatch, int inverse) {
-    if (kzgamd_ntt_fr_device(pc->ntt, out, in, n, nbatch, inverse, pc->st) != 0) throw PolyErr{hipErrorUnknown};
-}
-
 // out[poly out_len + i] = coefficient i of a_poly b_poly (pc->f and pc->g hold 2 npoly N elements when not direct)
 void enqueue_mul(PolyCtx* pc, Fr* out, size_t out_len, int out_flip, const Operand& a, const Operand& b, size_t npoly, int form) {
     hipStream_t st = pc->st;
@@ -375,46 +306,6 @@ void enqueue_inverse(PolyCtx* pc, Fr* c, const Operand& b, size_t L, size_t npol
         hipLaunchKernelGGL(k_poly_cut, dim3(blocks(npoly * s.n1)), dim3(256), 0, st, c, L, s.n1, 0, (const Fr*)g, s.N, npoly * s.n1);
     }
     PL_TRY(hipGetLastError());
-}
-
-// polynomials per slice: the workspace of a slice stays within a share of the free HBM
-size_t slice_of(PolyCtx* pc, size_t npoly, size_t bytes_per_poly) {
-    size_t free_b = 0, total_b = 0, held = 0;
-    PL_TRY(hipMemGetInfo(&free_b, &total_b));
-    for (DevBuf* d : pc->bufs()) held += d->cap;
-    size_t per = (free_b + held) / 8 / (bytes_per_poly ? bytes_per_poly : 1);
-    if (per == 0) per = 1;
-    return per < npoly ? per : npoly;
-}
-
-// one call on the handle: its lock, its GPU, everything `body` enqueues, one synchronisation
-template <class F>
-int run_call(PolyCtx* pc, F&& body) {
-    std::lock_guard<std::mutex> lk(pc->mu);
-    int rc = 0;
-    try {
-        kzgamd::DeviceGuard on_device(pc->device);
-        PL_TRY(on_device.err);
-        try {
-            body();
-        } catch (...) {
-            (void)hipStreamSynchronize(pc->st);  // a copy into the caller's buffer may be in flight
-            throw;
-        }
-        PL_TRY(hipStreamSynchronize(pc->st));
-    } catch (const PolyErr& e) {
-        rc = -(int)e.e - 100;
-    } catch (...) {
-        rc = -2;
-    }
-    return rc;
-}
-
-void upload(PolyCtx* pc, void* dst, const void* src, size_t bytes) {
-    PL_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, pc->st));
-}
-void download(PolyCtx* pc, void* dst, const void* src, size_t bytes) {
-    PL_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, pc->st));
 }
 
 }  // namespace

@@ -10,6 +10,7 @@
 //! | [`fk20::MiFK20SingleSettings`], [`fk20::MiFK20MultiSettings`] | — (device handle) | `FK20SingleSettings` / `FK20MultiSettings::data_availability[_optimized]` (-> `kzgamd_fk20_da`) |
 //! | [`kzg_settings::MiKZGSettings`] | — (own fields)  | `KZGSettings::new` (builds the device table), `commit_to_poly`, `compute_proof_single` |
 //! | [`poly::MiPolyExt`] on `MiFFTSettings` | — (device handle per call) | `FFTSettingsPoly::poly_mul_fft` with settings, `poly_mul` / `poly_inverse` / `poly_div` / `poly_eval_many` (-> `kzgamd_poly_*`) |
+//! | [`zero_poly`] on `MiFFTSettings`, [`recover`] on `FsPoly` | — (device handle per call) | `ZeroPoly::do_zero_poly_mul_partial` / `reduce_partials` / `zero_poly_via_multiplication`, `PolyRecover::recover_poly[_coeffs]_from_samples` (-> `kzgamd_poly_zero_*`, `kzgamd_poly_recover`) |
 //!
 //! Mirrors blst/src/types/{g1,fft_settings,kzg_settings}.rs method for method; every other method delegates to
 //! the wrapped blst type.  Not compiled in the build image: see Cargo.toml.
@@ -22,6 +23,8 @@ pub mod fk20;
 pub mod g1;
 pub mod kzg_settings;
 pub mod poly;
+pub mod recover;
+pub mod zero_poly;
 
 pub use backend::MiBackend;
 pub use fft_settings::MiFFTSettings;

@@ -90,6 +90,15 @@ extern "C" {
     fn kzgamd_poly_div(ph: *mut c_void, q: *mut blst_fr, a: *const blst_fr, la: usize, b: *const blst_fr, lb: usize,
                        npoly: usize) -> c_int;
     fn kzgamd_poly_transform_len(op: c_int, la: usize, lb: usize, out_len: usize) -> usize;
+    fn kzgamd_poly_zero_partial(ph: *mut c_void, out: *mut blst_fr, idxs: *const u64, nidx: usize, stride: usize) -> c_int;
+    fn kzgamd_poly_reduce_partials(ph: *mut c_void, out: *mut blst_fr, domain_size: usize, partials: *const blst_fr,
+                                   lens: *const usize, npartial: usize) -> c_int;
+    fn kzgamd_poly_zero_poly(ph: *mut c_void, zero_eval: *mut blst_fr, zero_poly: *mut blst_fr, domain_size: usize,
+                             missing: *const u64, offsets: *const usize, nprob: usize, form: c_int) -> c_int;
+    fn kzgamd_poly_recover(ph: *mut c_void, out: *mut blst_fr, samples: *const blst_fr, present: *const u8, n: usize,
+                           nprob: usize, coeffs: c_int) -> c_int;
+    fn kzgamd_poly_zero_info(ph: *mut c_void, leaf_roots: *mut usize, direct_max: *mut usize) -> c_int;
+    fn kzgamd_poly_zero_plan(count: usize, levels: *mut usize) -> usize;
 }
 
 fn check(err: RustError, what: &str) -> Result<(), String> {
@@ -613,6 +622,93 @@ impl GpuPoly {
         let (mut a, mut b, mut c, mut d) = (0usize, 0usize, 0usize, 0usize);
         unsafe { kzgamd_poly_info(self.ctx, &mut a, &mut b, &mut c, &mut d) };
         (a, b, c, d)
+    }
+
+    /// `do_zero_poly_mul_partial` for any number of indices: the idxs.len() + 1 coefficients of
+    /// prod (X - roots[idx * stride]), lowest first.
+    pub fn zero_partial(&self, idxs: &[u64], stride: usize) -> Result<Vec<blst_fr>, String> {
+        let mut out = vec![blst_fr::default(); idxs.len() + 1];
+        match unsafe { kzgamd_poly_zero_partial(self.ctx, out.as_mut_ptr(), idxs.as_ptr(), idxs.len(), stride) } {
+            0 => Ok(out),
+            1 => Err(String::from("idx array must not be empty")),
+            2 => Err(String::from("index out of bounds: idx * stride exceeds max_width")),
+            4 => Err(String::from(POLY_TOO_WIDE)),
+            e => Err(format!("GPU zero_partial failed: {e}")),
+        }
+    }
+
+    /// `reduce_partials`: the product of lens.len() polynomials stored back to back in `partials`.
+    pub fn reduce_partials(&self, domain_size: usize, partials: &[blst_fr], lens: &[usize]) -> Result<Vec<blst_fr>, String> {
+        if partials.len() != lens.iter().sum::<usize>() {
+            return Err(String::from("partials must hold the coefficients lens adds up to"));
+        }
+        let out_len = lens.iter().map(|l| l.saturating_sub(1)).sum::<usize>() + 1;
+        let mut out = vec![blst_fr::default(); out_len];
+        match unsafe {
+            kzgamd_poly_reduce_partials(self.ctx, out.as_mut_ptr(), domain_size, partials.as_ptr(), lens.as_ptr(), lens.len())
+        } {
+            0 => Ok(out),
+            1 => Err(String::from("Expected domain size to be a power of 2")),
+            2 => Err(String::from("partials must not be empty")),
+            3 => Err(String::from("Out degree is longer than possible polynomial size in domain")),
+            4 => Err(String::from("Domain size greater than fft_settings.max_width")),
+            5 => Err(String::from("attempt to subtract with overflow: empty partial")),
+            e => Err(format!("GPU reduce_partials failed: {e}")),
+        }
+    }
+
+    /// `zero_poly_via_multiplication` for offsets.len() - 1 index lists in one call (list b is
+    /// missing[offsets[b] .. offsets[b + 1]]): (zero_eval, zero_poly), domain_size elements per list each.  An empty
+    /// list gives the empty product: the caller that wants the reference's two empty vectors returns them itself.
+    pub fn zero_poly(&self, domain_size: usize, missing: &[u64], offsets: &[usize], form: PolyMulForm)
+                     -> Result<(Vec<blst_fr>, Vec<blst_fr>), String> {
+        if offsets.is_empty() || *offsets.last().unwrap() != missing.len() {
+            return Err(String::from("offsets must hold nprob + 1 positions ending at missing.len()"));
+        }
+        let nprob = offsets.len() - 1;
+        let mut ze = vec![blst_fr::default(); nprob * domain_size];
+        let mut zp = vec![blst_fr::default(); nprob * domain_size];
+        match unsafe {
+            kzgamd_poly_zero_poly(self.ctx, ze.as_mut_ptr(), zp.as_mut_ptr(), domain_size, missing.as_ptr(), offsets.as_ptr(),
+                                  nprob, form as c_int)
+        } {
+            0 => Ok((ze, zp)),
+            1 => Err(String::from("Missing idxs greater than domain size")),
+            2 => Err(String::from("Domain size greater than fft_settings.max_width")),
+            3 => Err(String::from("Domain size must be a power of 2")),
+            5 => Err(String::from("index out of bounds: missing idx exceeds domain size")),
+            e => Err(format!("GPU zero_poly failed: {e}")),
+        }
+    }
+
+    /// `recover_poly_from_samples` (`coeffs`: `recover_poly_coeffs_from_samples`) for `nprob` vectors of `n` samples;
+    /// present[b * n + i] == 0 marks a missing sample, whose value is never used.
+    pub fn recover(&self, samples: &[blst_fr], present: &[u8], n: usize, nprob: usize, coeffs: bool) -> Result<Vec<blst_fr>, String> {
+        if samples.len() != n * nprob || present.len() != n * nprob {
+            return Err(String::from("samples and present must hold nprob * n entries"));
+        }
+        let mut out = vec![blst_fr::default(); n * nprob];
+        match unsafe { kzgamd_poly_recover(self.ctx, out.as_mut_ptr(), samples.as_ptr(), present.as_ptr(), n, nprob, coeffs as c_int) } {
+            0 => Ok(out),
+            1 => Err(String::from("Samples must have a length that is a power of two")),
+            2 => Err(String::from("Impossible to recover, too many shards are missing")),
+            3 => Err(String::from(POLY_TOO_WIDE)),
+            e => Err(format!("GPU recover failed: {e}")),
+        }
+    }
+
+    /// (roots a wave of the leaf kernel takes, the longest list for which form 0 takes the direct form)
+    pub fn zero_info(&self) -> (usize, usize) {
+        let (mut a, mut b) = (0usize, 0usize);
+        unsafe { kzgamd_poly_zero_info(self.ctx, &mut a, &mut b) };
+        (a, b)
+    }
+
+    /// The levels the tree form runs for `count` roots: (polynomials entering, coefficients each, transform length).  Host-only.
+    pub fn zero_plan(count: usize) -> Vec<(usize, usize, usize)> {
+        let mut lv = [0usize; 96];
+        let k = unsafe { kzgamd_poly_zero_plan(count, lv.as_mut_ptr()) };
+        (0..k).map(|i| (lv[3 * i], lv[3 * i + 1], lv[3 * i + 2])).collect()
     }
 
     /// The longest transform a call of this shape enqueues (0: none); op 0 mul by transforms, 1 inverse, 2 div.  Host-only.
