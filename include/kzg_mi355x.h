@@ -252,6 +252,38 @@ int kzgamd_fk20_info(void *fk, size_t *n2, size_t *chunk_len, int *form);
  * 5 x == 0 in a tuple with n > 1 — the reference feeds inverse(0) into its arithmetic there (:253-261), which has no
  * meaningful result; negatives as above.  count = 0: ok, nothing written.
  *
+ * kzgamd_kzg_check_batch: the same count tuples under ONE pairing.  With weights rho_t = r^t (rho_0 = 1), I_t the
+ * interpolation polynomial of tuple t as above and A = sum_t rho_t I_t (n coefficients):
+ *   L = sum rho_t com_t + sum rho_t x_t^n proof_t - [A(s)]G,   P = sum rho_t proof_t,   *ok = e(L, G2) == e(P, [s^n]G2)
+ * — kzgamd_kzg_check's equation with [x_t^n]G2 moved to the G1 side, summed with the weights.  If every tuple is valid
+ * the batch passes for every r; if one is not, and every point is in G1, it passes for at most count - 1 values of r.  So
+ * the points are tested (on the curve and in G1, on the GPU) and r must not be known before the inputs are:
+ *   r == NULL: r = kzgamd_kzg_batch_challenge of the inputs;
+ *   r != NULL: used as given, for callers with a transcript of their own (and for tests).  Such an r MUST be fixed
+ *     after every input of the call is: an r the prover can anticipate lets errors of different tuples cancel (r = 1 adds
+ *     the tuples up unweighted, r = 0 checks tuple 0 alone).
+ * Everything but the hash and one pairing against line tables kept per handle and n runs on the GPU: the points to affine
+ * form with one inversion per lane and both tests, the weights, A from one batched inverse transform, [A(s)]G, one
+ * two-row MSM over the 2 count points.  Codes: kzgamd_kzg_check's, in its order (3, 4, 6, 1, 5), then 7 a commitment
+ * or proof is not on the curve or not in G1; -1 NULL argument, other negatives = device error.  On a positive code
+ * nothing is written.  count = 0: ok, *ok = true (ok is still required; the input pointers are not looked at).  Point
+ * coordinates are taken mod p (a non-canonical limb pattern >= p is the element it reduces to); the identity is Z = 0
+ * with all-zero limbs, whatever X and Y hold.  The derived challenge is hashed before the handle's lock is taken, the
+ * pairing runs after it is released.  ok_each (may be NULL): when the batch passes every entry is true;
+ * when it fails the entries are kzgamd_kzg_check's for the same tuples (count pairings).
+ *
+ * kzgamd_kzg_check_batch_g1: L and P (out[0], out[1], Jacobian) of the same inputs and the same r, no pairing — for
+ * callers that pair themselves, like kzgamd_verify_kzg_proof_batch_g1.  Needs no G2 setup: code 6 does not apply.
+ * count = 0: two identities (out is still required).
+ *
+ * kzgamd_kzg_batch_challenge (host only, no GPU): r = hash_to_bls_field(SHA-256(D)) — the digest as a big-endian
+ * integer mod the group order, as compute_challenge reduces its digest — with D = "KZGAMD_CHKBATCH1" (16 bytes) |
+ * u64_be(n) | u64_be(count) | the count x 144 commitment bytes | the count x 144 proof bytes | the count x 32 bytes of
+ * xs | the count x n x 32 bytes of ys, all AS PASSED: the caller's in-memory bytes, not a canonical encoding (no
+ * inversion, and the hash runs on the host while the GPU works).  Two Jacobian forms of one point therefore give two
+ * challenges — each as good as the other, but a verifier that must reproduce r has to hash the same bytes.  0 ok, -1
+ * NULL argument.
+ *
  * kzgamd_kzg_info: the setup sizes, the chunk length of the scan form and the number of lanes (pairs x n) from which
  * the lane form is taken; any pointer may be NULL. */
 void *kzgamd_kzg_new(void *ntt, const blst_p1 *g1_monomial, size_t num_g1, const blst_p2 *g2_monomial, size_t num_g2,
@@ -263,6 +295,12 @@ int kzgamd_kzg_open(void *kz, blst_p1 *proofs, blst_fr *ys, const blst_fr *polys
                     const blst_fr *xs, size_t nx, size_t n);
 int kzgamd_kzg_check(void *kz, bool *ok, const blst_p1 *commitments, const blst_p1 *proofs, const blst_fr *xs,
                      const blst_fr *ys, size_t n, size_t count);
+int kzgamd_kzg_check_batch(void *kz, bool *ok, bool *ok_each, const blst_p1 *commitments, const blst_p1 *proofs,
+                           const blst_fr *xs, const blst_fr *ys, size_t n, size_t count, const blst_fr *r);
+int kzgamd_kzg_check_batch_g1(void *kz, blst_p1 out[2], const blst_p1 *commitments, const blst_p1 *proofs,
+                              const blst_fr *xs, const blst_fr *ys, size_t n, size_t count, const blst_fr *r);
+int kzgamd_kzg_batch_challenge(blst_fr *r_out, const blst_p1 *commitments, const blst_p1 *proofs, const blst_fr *xs,
+                               const blst_fr *ys, size_t n, size_t count);
 /* Batched polynomial arithmetic, the reference's Poly<Fr> and FFTSettingsPoly (blst/src/types/poly.rs) on the GPU
  * (rust-kzg_amd/csrc/poly.hip).  Conventions of kzgamd_kzg_*: scalars are Montgomery blst_fr in host buffers; batches
  * are contiguous, npoly independent problems of the same shape per call; the handle is thread-safe (calls on one handle

@@ -67,6 +67,7 @@ EXPORTS = [
     "fft_g1", "kzgamd_fft_g1_batch", "kzgamd_g1_sum",
     "kzgamd_fk20_new", "kzgamd_fk20_free", "kzgamd_fk20_da", "kzgamd_fk20_info",
     "kzgamd_kzg_new", "kzgamd_kzg_free", "kzgamd_kzg_info", "kzgamd_kzg_commit", "kzgamd_kzg_open", "kzgamd_kzg_check",
+    "kzgamd_kzg_check_batch", "kzgamd_kzg_check_batch_g1", "kzgamd_kzg_batch_challenge",
     "kzgamd_poly_new", "kzgamd_poly_free", "kzgamd_poly_info", "kzgamd_poly_eval", "kzgamd_poly_scale", "kzgamd_poly_mul",
     "kzgamd_poly_inverse", "kzgamd_poly_div", "kzgamd_poly_transform_len",
     "kzgamd_poly_zero_partial", "kzgamd_poly_reduce_partials", "kzgamd_poly_zero_poly", "kzgamd_poly_recover",
@@ -235,6 +236,12 @@ def lib():
     L.kzgamd_kzg_open.argtypes = [vp, vp, vp, vp, sz, sz, vp, sz, sz]
     L.kzgamd_kzg_check.restype = C.c_int
     L.kzgamd_kzg_check.argtypes = [vp, vp, vp, vp, vp, vp, sz, sz]
+    L.kzgamd_kzg_check_batch.restype = C.c_int
+    L.kzgamd_kzg_check_batch.argtypes = [vp, vp, vp, vp, vp, vp, vp, sz, sz, vp]
+    L.kzgamd_kzg_check_batch_g1.restype = C.c_int
+    L.kzgamd_kzg_check_batch_g1.argtypes = [vp, vp, vp, vp, vp, vp, sz, sz, vp]
+    L.kzgamd_kzg_batch_challenge.restype = C.c_int
+    L.kzgamd_kzg_batch_challenge.argtypes = [vp, vp, vp, vp, vp, sz, sz]
     L.kzgamd_poly_new.restype = vp
     L.kzgamd_poly_new.argtypes = [vp, cp, C.POINTER(C.c_int)]
     L.kzgamd_poly_free.restype = None
@@ -801,7 +808,26 @@ KZG_ERRORS = {
     4: "Supplied list is longer than the available max width",
     5: "x must not be zero: the interpolation on the coset divides by it",
     6: "the setup has too few G2 points",
+    7: "a commitment or proof is not on the curve or not in G1",
 }
+
+
+def _one_fr(r):
+    """NULL, or the address of one BlstFr (a BlstFr or any buffer of 32 bytes)"""
+    if r is None:
+        return None
+    return C.cast(C.pointer(r), C.c_void_p) if isinstance(r, C.Structure) else _addr(r)
+
+
+def batch_challenge(commitments, proofs, xs, ys, n=1, count=1):
+    """The weight base r of PolyKZGSettings.check_batch(r=None): hash_to_bls_field(SHA-256("KZGAMD_CHKBATCH1" | u64_be(n) |
+    u64_be(count) | commitments | proofs | xs | ys)) over the buffers' bytes as passed.  Host only.  Returns a BlstFr."""
+    out = BlstFr()
+    rc = lib().kzgamd_kzg_batch_challenge(C.byref(out), _addr(commitments) if count else None, _addr(proofs) if count else None,
+                                          _addr(xs) if count else None, _addr(ys) if count * n else None, n, count)
+    if rc != 0:
+        raise KzgAmdError("kzgamd_kzg_batch_challenge: %d" % rc)
+    return out
 
 
 class PolyKZGSettings:
@@ -859,6 +885,29 @@ class PolyKZGSettings:
         if rc != 0:
             self._raise("kzgamd_kzg_check", rc)
         return [bool(ok[i]) for i in range(count)]
+
+    def check_batch(self, commitments, proofs, xs, ys, n=1, count=1, r=None, each=False):
+        """All `count` tuples under one pairing, weighted by the powers of r (None: batch_challenge of the inputs; a
+        caller's own r must be fixed after the inputs are).  Returns the verdict, or (verdict, list of count booleans)
+        with each=True — all true when the batch passes, check()'s when it fails."""
+        self._live()
+        ok = C.c_bool(False)
+        per = (C.c_bool * max(1, count))() if each else None
+        rc = lib().kzgamd_kzg_check_batch(self.handle, C.byref(ok), per, _addr(commitments), _addr(proofs), _addr(xs), _addr(ys),
+                                          n, count, _one_fr(r))
+        if rc != 0:
+            self._raise("kzgamd_kzg_check_batch", rc)
+        return (ok.value, [bool(per[i]) for i in range(count)]) if each else ok.value
+
+    def check_batch_g1(self, commitments, proofs, xs, ys, n=1, count=1, r=None):
+        """The two G1 sides of check_batch, no pairing: (BlstP1 * 2) = L, P with e(L, G2) == e(P, [s^n]G2) the verdict."""
+        self._live()
+        out = (BlstP1 * 2)()
+        rc = lib().kzgamd_kzg_check_batch_g1(self.handle, out, _addr(commitments), _addr(proofs), _addr(xs), _addr(ys), n, count,
+                                             _one_fr(r))
+        if rc != 0:
+            self._raise("kzgamd_kzg_check_batch_g1", rc)
+        return out
 
     def info(self):
         """(num_g1, num_g2, chunk, lane_form_min): the setup sizes, the chunk length of the scan form of the quotient

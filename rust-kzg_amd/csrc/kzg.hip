@@ -26,6 +26,17 @@
 // check: the G1 side com - [I(s)]G for all tuples on the GPU (inverse transform of the ys, x^-i by one inversion per
 // tuple, one MSM per tuple over the first n setup points, the subtraction); the G2 side and one pairing per tuple on
 // the host (host_pairing.h), as in the reference.
+//
+// check_batch: any number of tuples under ONE pairing.  With weights rho_t = r^t,
+//     L = sum rho_t C_t + sum rho_t x_t^n pi_t - [A(s)]G,  A = sum rho_t I_t,   P = sum rho_t pi_t,   ok = e(L, G2) == e(P, [s^n]G2).
+// GPU: the 2 count Jacobian points to affine slots with the curve equation tested (k_kzg_points: Montgomery's trick, one
+// inversion per lane) and the r-torsion test on each (k_kzg_in_g1), failures counted in two status words the host reads
+// once; the weights and the two scalar rows over [proofs | commitments] (k_kzg_batch_scalars); A from one batched inverse
+// transform (k_kzg_batch_agg: a lane per tuple walks x^-i, wave shuffles sum over the tuples; k_kzg_batch_fold adds the
+// waves); [A(s)]G on the setup's MSM handle, one two-row variable-base MSM over the checked points, one
+// subtraction, one download.  Host: the SHA-256 of the challenge before the handle's lock is taken (a hash of megabytes
+// at large counts must not hold up the handle's other callers), one pairing check after it is released, against the line
+// tables of G2 (pairing::prepared_lines) and of [s^n]G2, kept per handle and n.
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
@@ -33,6 +44,8 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <map>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -44,13 +57,16 @@
 #include "fr29.hip.h"
 #include "frscan.hip.h"
 #include "g1_28.hip.h"
+#include "g1_io.hip.h"
 #include "host_fp64.h"
 #include "host_pairing.h"
 #include "msm_internal.h"
 #include "ntt_internal.h"
+#include "sha256.h"
 
 using ff::Fr;
 using ff::u32;
+using g1::AffPt;
 using g1::Xyzz;
 
 namespace {
@@ -203,6 +219,107 @@ __global__ void __launch_bounds__(64) k_kzg_g1_sub(ff::Fp* __restrict__ out, con
     g1::to_blst_jacobian(out + 3 * t, A);
 }
 
+// ---- check_batch ----
+constexpr int PT_CHUNK = 8;        // points per lane of k_kzg_points: one inversion per PT_CHUNK points
+constexpr int AGG_WAVE = 64;       // tuples per block of k_kzg_batch_agg: one wave
+
+// blst Jacobian points -> the affine slots of the variable-base engine (identity: flag and (0, 0)), a lane per PT_CHUNK
+// consecutive points with one inversion of the product of their Z (pref: a slot per point for the running products).
+// The curve equation is tested on what the lane has just computed, y^2 == x^3 + 4 with x = X / Z^2, y = Y / Z^3 — which
+// is Y^2 == X^3 + 4 Z^6 for Z != 0; a point that fails becomes the identity and counts in status[0].
+// The identity is Z with all-zero limbs, whatever X and Y hold (blst's convention).  Coordinates are taken mod p: a
+// non-canonical one (>= p) is the element it reduces to.  The one exception fails safe: a Z that is 0 mod p with non-zero
+// limbs (Z = p) zeroes the lane's running product, the inverse of 0 comes back 0, and all PT_CHUNK points of the lane fail
+// the curve test — the call returns 7, as it would for that point alone.
+__global__ void __launch_bounds__(64) k_kzg_points(AffPt* __restrict__ out, const ff::Fp* __restrict__ jac, fp28::Fe* __restrict__ pref,
+                                                   size_t total, int* __restrict__ status) {
+    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const size_t lo = t * PT_CHUNK;
+    if (lo >= total) return;
+    const size_t hi = lo + PT_CHUNK < total ? lo + PT_CHUNK : total;
+    fp28::Fe run = fp28::one();
+    for (size_t k = lo; k < hi; ++k) {
+        pref[k] = run;
+        if (!jac[3 * k + 2].is_zero()) run = fp28::mul(run, fp28::from_blst(jac[3 * k + 2]));
+    }
+    fp28::Fe inv = g1io::inverse(run);
+    fp28::Fe b4;
+#pragma unroll
+    for (int i = 0; i < 14; ++i) b4.v[i] = g1io::b4_392_l(i);
+    int bad = 0;
+    for (size_t k = hi; k-- > lo;) {
+        AffPt o;
+        o.flags = 1;
+        o.pad[0] = o.pad[1] = o.pad[2] = 0;
+        o.x = fp28::zero();
+        o.y = fp28::zero();
+        if (!jac[3 * k + 2].is_zero()) {
+            const fp28::Fe z = fp28::from_blst(jac[3 * k + 2]);
+            const fp28::Fe zi = fp28::mul(inv, pref[k]), zi2 = fp28::sqr(zi);
+            inv = fp28::mul(inv, z);
+            const fp28::Fe x = fp28::mul(fp28::from_blst(jac[3 * k]), zi2);
+            const fp28::Fe y = fp28::mul(fp28::from_blst(jac[3 * k + 1]), fp28::mul(zi2, zi));
+            const fp28::Fe rhs = fp28::addn(fp28::mul(fp28::sqr(x), x), b4);  // x^3 + 4, < 4p
+            if (fp28::is_zero_mod_p(fp28::sub<8>(fp28::sqr(y), rhs))) {
+                o.flags = 0;
+                o.x = fp28::canon(x);
+                o.y = fp28::canon(y);
+            } else {
+                ++bad;
+            }
+        }
+        out[k] = o;
+    }
+    if (bad) atomicAdd(status, bad);
+}
+// the r-torsion test of every slot (g1_io.hip.h: phi(P) == -[x^2]P, what k_bases_in_g1 runs on a handle's bases): status[1]
+__global__ void __launch_bounds__(64) k_kzg_in_g1(const AffPt* __restrict__ pts, size_t total, int* __restrict__ status) {
+    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= total) return;
+    if (!g1io::affpt_in_g1(pts[t])) atomicAdd(status + 1, 1);
+}
+// per tuple: rho_t = r^t, and the two scalar rows over [proofs | commitments] (np = 2 count columns):
+// row P = rho_t | 0, row L = rho_t x_t^n | rho_t
+__global__ void __launch_bounds__(64) k_kzg_batch_scalars(Fr* __restrict__ rho, Fr* __restrict__ rows, const Fr* __restrict__ r,
+                                                          const Fr* __restrict__ xs, size_t n, size_t count) {
+    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= count) return;
+    const Fr w = fr_pow(*r, t);
+    Fr xn = xs[t];
+    for (size_t m = 1; m < n; m <<= 1) xn = fr_mul(xn, xn);
+    rho[t] = w;
+    rows[t] = w;
+    rows[count + t] = Fr::zero();
+    rows[2 * count + t] = fr_mul(w, xn);
+    rows[3 * count + t] = w;
+}
+// part[wave][i] = sum over the 64 tuples t of the wave of rho_t x_t^-i v_t[i], i < n: a lane per tuple walks rho_t x_t^-i
+// along i, the sum over t by shuffles; a block is one wave, so nothing here needs a workgroup barrier (k_kzg_batch_fold
+// adds the waves).  xinv == nullptr (n = 1): no walk.  Field addition is exact: the order of the sum does not matter.
+__global__ void __launch_bounds__(AGG_WAVE) k_kzg_batch_agg(Fr* __restrict__ part, const Fr* __restrict__ v, const Fr* __restrict__ rho,
+                                                            const Fr* __restrict__ xinv, size_t n, size_t count) {
+    const size_t t = (size_t)blockIdx.x * AGG_WAVE + threadIdx.x;
+    const bool live = t < count;  // dead lanes add zeros: no lane leaves before the shuffles
+    Fr pw = live ? rho[t] : Fr::zero();
+    const Fr step = live && xinv ? xinv[t] : Fr::zero();
+    const Fr* mine = v + (live ? t : 0) * n;
+    Fr* out = part + (size_t)blockIdx.x * n;
+    for (size_t i = 0; i < n; ++i) {
+        Fr term = live ? fr_mul(pw, mine[i]) : Fr::zero();
+        if (i + 1 < n) pw = fr_mul(pw, step);
+        for (int d = 32; d > 0; d >>= 1) term = ff::add(term, shfl_down(term, d));
+        if (threadIdx.x == 0) out[i] = term;
+    }
+}
+// A_i = sum over the waves of part[wave][i]
+__global__ void __launch_bounds__(256) k_kzg_batch_fold(Fr* __restrict__ agg, const Fr* __restrict__ part, size_t n, size_t nblocks) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    Fr s = part[i];
+    for (size_t b = 1; b < nblocks; ++b) s = ff::add(s, part[b * n + i]);
+    agg[i] = s;
+}
+
 struct KzErr {
     hipError_t e;
 };
@@ -242,11 +359,19 @@ struct KzgCtx {
     std::mutex mu;
     hipStream_t st = nullptr;
     kzgamd::MsmContext* msm = nullptr;
+    // check_batch: the variable-base handle over a call's checked points (created by the first call, given new points by
+    // every later one), and the line table of [s^n]G2 per n (G2's own comes from pairing::prepared_lines)
+    kzgamd::Options opt;
+    kzgamd::MsmContext* vmsm = nullptr;
+    std::map<size_t, std::shared_ptr<const kzgamd::pairing::LineTable>> lines;
     // workspace, grown as calls need it
     DevBuf polys, xs, pw, q, r, r2, sums, local, out, pts;
+    DevBuf aff, pref, stat, xinv, rho, rows, part, agg;
 
     ~KzgCtx() {
-        for (DevBuf* b : {&polys, &xs, &pw, &q, &r, &r2, &sums, &local, &out, &pts}) b->drop();
+        for (DevBuf* b : {&polys, &xs, &pw, &q, &r, &r2, &sums, &local, &out, &pts, &aff, &pref, &stat, &xinv, &rho, &rows, &part, &agg})
+            b->drop();
+        if (vmsm) kzgamd::msm_destroy(vmsm);
         if (msm) kzgamd::msm_destroy(msm);
         if (st) (void)hipStreamDestroy(st);
     }
@@ -363,6 +488,7 @@ extern "C" void* kzgamd_kzg_new(void* vntt, const blst_p1* g1_monomial, size_t n
         KZ_TRY(on_device.err);
         kz->ntt = ntt;
         kz->device = ntt->device;
+        kz->opt = opt;
         kz->num_g1 = num_g1;
         kz->num_g2 = g2_monomial ? num_g2 : 0;
         kz->g2.resize(kz->num_g2);
@@ -513,10 +639,12 @@ extern "C" int kzgamd_kzg_open(void* vkz, blst_p1* proofs, blst_fr* ys, const bl
     return rc;
 }
 
-extern "C" int kzgamd_kzg_check(void* vkz, bool* ok, const blst_p1* commitments, const blst_p1* proofs, const blst_fr* xs,
-                                const blst_fr* ys, size_t n, size_t count) {
+namespace {
+
+// kzgamd_kzg_check: one pairing per tuple (also what check_batch fills ok_each with when a batch fails)
+int check_each(KzgCtx* kz, bool* ok, const blst_p1* commitments, const blst_p1* proofs, const blst_fr* xs, const blst_fr* ys, size_t n,
+               size_t count) {
     namespace pr = kzgamd::pairing;
-    KzgCtx* kz = (KzgCtx*)vkz;
     if (!kz) return -1;
     if (n == 0 || (n & (n - 1))) return 3;
     if (n > kz->ntt->W) return 4;
@@ -590,5 +718,213 @@ extern "C" int kzgamd_kzg_check(void* vkz, bool* ok, const blst_p1* commitments,
         const pr::LineTable* tabs[2] = {tgen.get(), &trhs};
         ok[i] = pr::f12_is_one(pr::final_exponentiation(pr::miller_loop_multi(tabs, px, py, inf, 2)));
     }
+    return 0;
+}
+
+// D = "KZGAMD_CHKBATCH1" | u64_be(n) | u64_be(count) | commitments | proofs | xs | ys, the caller's bytes;
+// r = the SHA-256 of D as a big-endian integer mod the group order (hash_to_bls_field), Montgomery form
+Fr batch_challenge(const blst_p1* commitments, const blst_p1* proofs, const blst_fr* xs, const blst_fr* ys, size_t n, size_t count) {
+    kzgamd::Sha256 h;
+    uint8_t head[32];
+    memcpy(head, "KZGAMD_CHKBATCH1", 16);
+    for (int i = 0; i < 8; ++i) {
+        head[16 + 7 - i] = (uint8_t)((uint64_t)n >> (8 * i));
+        head[24 + 7 - i] = (uint8_t)((uint64_t)count >> (8 * i));
+    }
+    h.update(head, 32);
+    if (count) {
+        h.update((const uint8_t*)commitments, count * sizeof(blst_p1));
+        h.update((const uint8_t*)proofs, count * sizeof(blst_p1));
+        h.update((const uint8_t*)xs, count * sizeof(blst_fr));
+        if (n) h.update((const uint8_t*)ys, count * n * sizeof(blst_fr));
+    }
+    uint8_t digest[32];
+    h.finish(digest);
+    Fr v;
+    for (int i = 0; i < 8; ++i) {
+        const uint8_t* q = digest + (7 - i) * 4;
+        v.v[i] = ((u32)q[0] << 24) | ((u32)q[1] << 16) | ((u32)q[2] << 8) | (u32)q[3];
+    }
+    return ff::mul(v, Fr::r2());
+}
+
+// the argument checks the batched calls share, kzgamd_kzg_check's codes in its order; 0 = go on
+int batch_args(KzgCtx* kz, bool need_g2, const void* out, const blst_p1* commitments, const blst_p1* proofs, const blst_fr* xs,
+               const blst_fr* ys, size_t n, size_t count) {
+    if (n == 0 || (n & (n - 1))) return 3;
+    if (n > kz->ntt->W) return 4;
+    if (need_g2 && kz->num_g2 <= n) return 6;
+    if (n > kz->num_g1) return 1;
+    if (!out) return -1;  // written even when count == 0
+    if (count == 0) return 0;
+    if (!commitments || !proofs || !xs || !ys) return -1;
+    const Fr* hx = reinterpret_cast<const Fr*>(xs);
+    if (n > 1)
+        for (size_t i = 0; i < count; ++i)
+            if (hx[i].is_zero()) return 5;
+    return 0;
+}
+
+// L and P of the batch into lp[0], lp[1] (count > 0, arguments checked).  0 ok, 7 a point off the curve or outside G1,
+// negative = device error.  r: the weight base (the caller's, or the challenge hashed before the lock was taken).
+// tab_n != nullptr: also look up (or build) the line table of [s^n]G2, under the same lock.
+int batch_g1(KzgCtx* kz, blst_p1 lp[2], const blst_p1* commitments, const blst_p1* proofs, const blst_fr* xs, const blst_fr* ys,
+             size_t n, size_t count, const Fr& r, std::shared_ptr<const kzgamd::pairing::LineTable>* tab_n) {
+    namespace pr = kzgamd::pairing;
+    const size_t np = 2 * count, nblocks = blocks(count, AGG_WAVE);
+    int rc = 0;
+    std::lock_guard<std::mutex> lk(kz->mu);
+    try {
+        kzgamd::DeviceGuard on_device(kz->device);
+        KZ_TRY(on_device.err);
+        kz->pts.ensure(np * sizeof(blst_p1));
+        kz->aff.ensure(np * sizeof(AffPt));
+        kz->pref.ensure(np * sizeof(fp28::Fe));
+        kz->stat.ensure(2 * sizeof(int));
+        kz->r.ensure(count * n * sizeof(Fr));
+        if (n > 1) kz->r2.ensure(count * n * sizeof(Fr));
+        kz->xs.ensure((count + 1) * sizeof(Fr));  // the x of every tuple, then r
+        if (n > 1) kz->xinv.ensure(count * sizeof(Fr));
+        kz->rho.ensure(count * sizeof(Fr));
+        kz->rows.ensure(2 * np * sizeof(Fr));
+        kz->part.ensure(nblocks * n * sizeof(Fr));
+        kz->agg.ensure(n * sizeof(Fr));
+        kz->out.ensure(4 * sizeof(blst_p1));  // L | P | row L | [A(s)]G
+        hipStream_t st = kz->st;
+        ff::Fp* jac = kz->pts.as<ff::Fp>();
+        AffPt* aff = kz->aff.as<AffPt>();
+        int* stat = kz->stat.as<int>();
+        Fr* dx = kz->xs.as<Fr>();
+        ff::Fp* out = kz->out.as<ff::Fp>();
+        int hstat[2] = {1, 1};
+        try {
+            // points: [proofs | commitments] -> affine slots, on the curve, in G1
+            KZ_TRY(hipMemcpyAsync(jac, proofs, count * sizeof(blst_p1), hipMemcpyHostToDevice, st));
+            KZ_TRY(hipMemcpyAsync(jac + 3 * count, commitments, count * sizeof(blst_p1), hipMemcpyHostToDevice, st));
+            KZ_TRY(hipMemsetAsync(stat, 0, 2 * sizeof(int), st));
+            hipLaunchKernelGGL(k_kzg_points, dim3(blocks(blocks(np, PT_CHUNK), 64)), dim3(64), 0, st, aff, (const ff::Fp*)jac,
+                               kz->pref.as<fp28::Fe>(), np, stat);
+            hipLaunchKernelGGL(k_kzg_in_g1, dim3(blocks(np, 64)), dim3(64), 0, st, (const AffPt*)aff, np, stat);
+            // values: the inverse transforms and x^-1
+            KZ_TRY(hipMemcpyAsync(kz->r.p, ys, count * n * sizeof(Fr), hipMemcpyHostToDevice, st));
+            KZ_TRY(hipMemcpyAsync(dx, xs, count * sizeof(Fr), hipMemcpyHostToDevice, st));
+            const Fr* vals = kz->r.as<Fr>();
+            if (n > 1) {
+                if (kzgamd_ntt_fr_device(kz->ntt, kz->r2.p, kz->r.p, n, count, 1, st) != 0) throw KzErr{hipErrorUnknown};
+                KZ_TRY(hipMemcpyAsync(kz->xinv.p, dx, count * sizeof(Fr), hipMemcpyDeviceToDevice, st));
+                hipLaunchKernelGGL(k_kzg_invert, dim3(blocks(count, 64)), dim3(64), 0, st, kz->xinv.as<Fr>(), count);
+                vals = kz->r2.as<Fr>();
+            }
+            KZ_TRY(hipGetLastError());
+            KZ_TRY(hipMemcpyAsync(hstat, stat, 2 * sizeof(int), hipMemcpyDeviceToHost, st));
+            KZ_TRY(hipStreamSynchronize(st));
+            if (hstat[0] || hstat[1]) return 7;
+            // the checked points become the bases of the variable-base handle (all in G1: the GLV split holds)
+            if (!kz->vmsm) kz->vmsm = kzgamd::msm_create(aff, np, true, false, true, kzgamd::G1_TRUSTED, &kz->opt);
+            else kzgamd::msm_reset_points(kz->vmsm, aff, np);
+            KZ_TRY(hipMemcpyAsync(dx + count, &r, sizeof(Fr), hipMemcpyHostToDevice, st));
+            hipLaunchKernelGGL(k_kzg_batch_scalars, dim3(blocks(count, 64)), dim3(64), 0, st, kz->rho.as<Fr>(), kz->rows.as<Fr>(),
+                               (const Fr*)(dx + count), (const Fr*)dx, n, count);
+            Fr* part = nblocks > 1 ? kz->part.as<Fr>() : kz->agg.as<Fr>();
+            hipLaunchKernelGGL(k_kzg_batch_agg, dim3((unsigned)nblocks), dim3(AGG_WAVE), 0, st, part, vals, (const Fr*)kz->rho.as<Fr>(),
+                               n > 1 ? (const Fr*)kz->xinv.as<Fr>() : (const Fr*)nullptr, n, count);
+            if (nblocks > 1)
+                hipLaunchKernelGGL(k_kzg_batch_fold, dim3(blocks(n)), dim3(256), 0, st, kz->agg.as<Fr>(), (const Fr*)part, n, nblocks);
+            KZ_TRY(hipGetLastError());
+            msm_on_stream(kz, out + 9, kz->agg.p, n, 1);  // [A(s)]G
+            kzgamd::msm_lock(kz->vmsm);
+            try {
+                kzgamd::msm_enqueue(kz->vmsm, out + 3, kz->rows.p, np, 2, 1, st, kzgamd::OUT_JACOBIAN);  // P, row L
+            } catch (...) {
+                kzgamd::msm_unlock(kz->vmsm);
+                throw KzErr{hipErrorUnknown};
+            }
+            kzgamd::msm_unlock(kz->vmsm);
+            hipLaunchKernelGGL(k_kzg_g1_sub, dim3(1), dim3(64), 0, st, out, (const ff::Fp*)(out + 6), (const ff::Fp*)(out + 9), (size_t)1);
+            KZ_TRY(hipGetLastError());
+            KZ_TRY(hipMemcpyAsync(lp, out, 2 * sizeof(blst_p1), hipMemcpyDeviceToHost, st));
+        } catch (...) {
+            (void)hipStreamSynchronize(st);
+            throw;
+        }
+        KZ_TRY(hipStreamSynchronize(st));
+        if (tab_n) {
+            auto it = kz->lines.find(n);
+            if (it == kz->lines.end())
+                it = kz->lines.emplace(n, std::make_shared<const pr::LineTable>(pr::g2_line_table(pr::g2_to_affine(kz->g2[n])))).first;
+            *tab_n = it->second;
+        }
+    } catch (const KzErr& e) {
+        rc = -(int)e.e - 100;
+    } catch (...) {
+        rc = -2;
+    }
+    return rc;
+}
+
+}  // namespace
+
+extern "C" int kzgamd_kzg_check(void* vkz, bool* ok, const blst_p1* commitments, const blst_p1* proofs, const blst_fr* xs,
+                                const blst_fr* ys, size_t n, size_t count) {
+    return check_each((KzgCtx*)vkz, ok, commitments, proofs, xs, ys, n, count);
+}
+
+extern "C" int kzgamd_kzg_batch_challenge(blst_fr* r_out, const blst_p1* commitments, const blst_p1* proofs, const blst_fr* xs,
+                                          const blst_fr* ys, size_t n, size_t count) {
+    if (!r_out || (count && (!commitments || !proofs || !xs || (n && !ys)))) return -1;
+    const Fr r = batch_challenge(commitments, proofs, xs, ys, n, count);
+    memcpy(r_out, &r, sizeof r);
+    return 0;
+}
+
+extern "C" int kzgamd_kzg_check_batch_g1(void* vkz, blst_p1 out[2], const blst_p1* commitments, const blst_p1* proofs,
+                                         const blst_fr* xs, const blst_fr* ys, size_t n, size_t count, const blst_fr* r) {
+    KzgCtx* kz = (KzgCtx*)vkz;
+    if (!kz) return -1;
+    if (const int rc = batch_args(kz, false, out, commitments, proofs, xs, ys, n, count)) return rc;
+    if (count == 0) {
+        memset(out, 0, 2 * sizeof(blst_p1));
+        return 0;
+    }
+    // the hash of 2 count points and count (n + 1) scalars runs BEFORE the handle's lock is taken: other callers of the
+    // handle are not held up by it
+    const Fr w = r ? *reinterpret_cast<const Fr*>(r) : batch_challenge(commitments, proofs, xs, ys, n, count);
+    blst_p1 lp[2];
+    const int rc = batch_g1(kz, lp, commitments, proofs, xs, ys, n, count, w, nullptr);
+    if (rc == 0) memcpy(out, lp, sizeof lp);
+    return rc;
+}
+
+extern "C" int kzgamd_kzg_check_batch(void* vkz, bool* ok, bool* ok_each, const blst_p1* commitments, const blst_p1* proofs,
+                                      const blst_fr* xs, const blst_fr* ys, size_t n, size_t count, const blst_fr* r) {
+    namespace pr = kzgamd::pairing;
+    KzgCtx* kz = (KzgCtx*)vkz;
+    if (!kz) return -1;
+    if (const int rc = batch_args(kz, true, ok, commitments, proofs, xs, ys, n, count)) return rc;
+    if (count == 0) {
+        *ok = true;
+        return 0;
+    }
+    const Fr w = r ? *reinterpret_cast<const Fr*>(r) : batch_challenge(commitments, proofs, xs, ys, n, count);  // before the lock
+    blst_p1 lp[2];
+    std::shared_ptr<const pr::LineTable> tab_n;
+    if (const int rc = batch_g1(kz, lp, commitments, proofs, xs, ys, n, count, w, &tab_n)) return rc;
+    const std::shared_ptr<const pr::LineTable> tab_gen = pr::prepared_lines(pr::g2_generator());
+    // one pairing check, outside the handle's lock:  e(-L, G2) e(P, [s^n]G2) == 1
+    ff::Fp px[2], py[2];
+    bool inf[2];
+    inf[0] = g1_affine(&lp[0], px[0], py[0]);
+    inf[1] = g1_affine(&lp[1], px[1], py[1]);
+    if (!inf[0]) py[0] = hfp::neg(py[0]);
+    const pr::LineTable* tabs[2] = {tab_gen.get(), tab_n.get()};
+    const bool pass = pr::f12_is_one(pr::final_exponentiation(pr::miller_loop_multi(tabs, px, py, inf, 2)));
+    if (ok_each) {
+        if (pass) {
+            for (size_t i = 0; i < count; ++i) ok_each[i] = true;
+        } else if (const int rc = check_each(kz, ok_each, commitments, proofs, xs, ys, n, count)) {
+            return rc;
+        }
+    }
+    *ok = pass;
     return 0;
 }

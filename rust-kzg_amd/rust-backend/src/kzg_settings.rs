@@ -11,6 +11,7 @@ use blst::{blst_fr, blst_p1, blst_p1_affine, blst_p2};
 use kzg::{FFTSettings, G1Affine, KZGSettings, FFTG1, G1};
 use rust_kzg_blst::types::fp::FsFp;
 use rust_kzg_blst::types::fr::FsFr;
+use rust_kzg_blst::types::g1::FsG1;
 use rust_kzg_blst::types::g2::FsG2;
 use rust_kzg_blst::types::poly::FsPoly;
 use rust_kzg_mi355x_sys as sys;
@@ -89,6 +90,18 @@ fn prepare(points: &[MiG1], matrix: &[Vec<MiG1>], lagrange_budget: u64, matrix_b
     (Some(Arc::new(MiPrecomputation::from_ptr(handle))), attached)
 }
 
+// FsG1 is a one-field tuple struct over blst_p1 (`pub struct FsG1(pub blst_p1)`, what `MiG1::from_blst` builds and
+// `.0 .0` reads): the view below is only sound while the two have the same layout, so that is checked at compile time
+const _: () = assert!(core::mem::size_of::<FsG1>() == core::mem::size_of::<blst_p1>()
+    && core::mem::align_of::<FsG1>() == core::mem::align_of::<blst_p1>());
+
+/// `&[MiG1]` as the `blst_p1` array the C ABI takes: MiG1 -> FsG1 by `MiG1::slice_as_fs` (repr(transparent)), FsG1 ->
+/// blst_p1 by the layout asserted above
+fn p1_slice(v: &[MiG1]) -> &[blst_p1] {
+    let fs: &[FsG1] = MiG1::slice_as_fs(v);
+    unsafe { core::slice::from_raw_parts(fs.as_ptr() as *const blst_p1, fs.len()) }
+}
+
 fn fr_slice(v: &[FsFr]) -> &[blst_fr] {
     unsafe { core::slice::from_raw_parts(v.as_ptr() as *const blst_fr, v.len()) }
 }
@@ -111,6 +124,24 @@ impl MiKZGSettings {
         let ok = self.device()?.check(core::slice::from_ref(&com.0 .0), core::slice::from_ref(&proof.0 .0), fr_slice(core::slice::from_ref(x)),
                                       fr_slice(ys), n)?;
         Ok(ok[0])
+    }
+
+    /// Any number of `check_proof_single` (n = 1) / `check_proof_multi` statements under ONE pairing
+    /// (`kzgamd_kzg_check_batch`): tuple t is (`commitments[t]`, `proofs[t]`, `xs[t]`, `ys[t * n..(t + 1) * n]`).  The
+    /// tuples are weighted by the powers of a challenge the library hashes from the inputs; the points are tested for
+    /// the curve and for G1 on the device.  An addition over the reference's trait, for callers that check many
+    /// samples at once: `Ok(true)` exactly when every tuple would pass `check_proof_multi`, up to the soundness of the
+    /// random weights.
+    pub fn check_proofs_batch(&self, commitments: &[MiG1], proofs: &[MiG1], xs: &[FsFr], ys: &[FsFr], n: usize) -> Result<bool, String> {
+        if !n.is_power_of_two() {
+            return Err(String::from("n is not a power of two"));
+        }
+        if commitments.len() != xs.len() || proofs.len() != xs.len() || ys.len() != xs.len() * n {
+            return Err(String::from("commitments, proofs, xs and ys must describe the same number of tuples"));
+        }
+        let (com, prf) = (p1_slice(commitments), p1_slice(proofs));
+        let (ok, _) = self.device()?.check_batch(com, prf, fr_slice(xs), fr_slice(ys), n, None, false)?;
+        Ok(ok)
     }
 
     /// Rebuilds the two device tables with other HBM budgets (bytes per table; 0 = the library's default of 160 GB

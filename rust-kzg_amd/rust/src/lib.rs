@@ -74,6 +74,13 @@ extern "C" {
                        npoly: usize, xs: *const blst_fr, nx: usize, n: usize) -> c_int;
     fn kzgamd_kzg_check(kz: *mut c_void, ok: *mut bool, commitments: *const blst_p1, proofs: *const blst_p1,
                         xs: *const blst_fr, ys: *const blst_fr, n: usize, count: usize) -> c_int;
+    fn kzgamd_kzg_check_batch(kz: *mut c_void, ok: *mut bool, ok_each: *mut bool, commitments: *const blst_p1,
+                              proofs: *const blst_p1, xs: *const blst_fr, ys: *const blst_fr, n: usize, count: usize,
+                              r: *const blst_fr) -> c_int;
+    fn kzgamd_kzg_check_batch_g1(kz: *mut c_void, out: *mut blst_p1, commitments: *const blst_p1, proofs: *const blst_p1,
+                                 xs: *const blst_fr, ys: *const blst_fr, n: usize, count: usize, r: *const blst_fr) -> c_int;
+    fn kzgamd_kzg_batch_challenge(r_out: *mut blst_fr, commitments: *const blst_p1, proofs: *const blst_p1,
+                                  xs: *const blst_fr, ys: *const blst_fr, n: usize, count: usize) -> c_int;
 
     fn kzgamd_poly_new(ntt: *mut c_void, cfg: *const KzgAmdConfig, err: *mut c_int) -> *mut c_void;
     fn kzgamd_poly_free(ph: *mut c_void);
@@ -490,6 +497,72 @@ impl GpuKzg {
             5 => Err(String::from("x must not be zero")),
             6 => Err(String::from("the setup has too few G2 points")),
             e => Err(format!("GPU KZG check failed: {e}")),
+        }
+    }
+
+    fn batch_error(what: &str, code: c_int) -> String {
+        match code {
+            1 => String::from("Polynomial is longer than secret g1"),
+            3 => String::from("n is not a power of two"),
+            4 => String::from("Supplied list is longer than the available max width"),
+            5 => String::from("x must not be zero"),
+            6 => String::from("the setup has too few G2 points"),
+            7 => String::from("a commitment or proof is not on the curve or not in G1"),
+            e => format!("GPU KZG {what} failed: {e}"),
+        }
+    }
+
+    /// All `xs.len()` tuples under ONE pairing (`kzgamd_kzg_check_batch`), weighted by the powers of `r`.  `None`: the
+    /// library derives r from the inputs (`batch_challenge`); a caller's own r must be fixed after the inputs are.
+    /// With `each` the per-tuple verdicts come back too: all true when the batch passes, `check`'s when it fails.
+    pub fn check_batch(&self, commitments: &[blst_p1], proofs: &[blst_p1], xs: &[blst_fr], ys: &[blst_fr], n: usize,
+                       r: Option<&blst_fr>, each: bool) -> Result<(bool, Vec<bool>), String> {
+        let count = xs.len();
+        if commitments.len() != count || proofs.len() != count || ys.len() != count * n {
+            return Err(String::from("commitments, proofs, xs and ys must describe the same number of tuples"));
+        }
+        let mut ok = false;
+        let mut per = vec![false; if each { count } else { 0 }];
+        let per_ptr = if each { per.as_mut_ptr() } else { core::ptr::null_mut() };
+        let r_ptr = r.map_or(core::ptr::null(), |v| v as *const blst_fr);
+        match unsafe {
+            kzgamd_kzg_check_batch(self.ctx, &mut ok, per_ptr, commitments.as_ptr(), proofs.as_ptr(), xs.as_ptr(), ys.as_ptr(), n,
+                                   count, r_ptr)
+        } {
+            0 => Ok((ok, per)),
+            e => Err(Self::batch_error("check_batch", e)),
+        }
+    }
+
+    /// The two G1 sides of `check_batch`, no pairing: `[L, P]` with e(L, G2) == e(P, [s^n]G2) the verdict.
+    pub fn check_batch_g1(&self, commitments: &[blst_p1], proofs: &[blst_p1], xs: &[blst_fr], ys: &[blst_fr], n: usize,
+                          r: Option<&blst_fr>) -> Result<[blst_p1; 2], String> {
+        let count = xs.len();
+        if commitments.len() != count || proofs.len() != count || ys.len() != count * n {
+            return Err(String::from("commitments, proofs, xs and ys must describe the same number of tuples"));
+        }
+        let mut out = [blst_p1::default(); 2];
+        let r_ptr = r.map_or(core::ptr::null(), |v| v as *const blst_fr);
+        match unsafe {
+            kzgamd_kzg_check_batch_g1(self.ctx, out.as_mut_ptr(), commitments.as_ptr(), proofs.as_ptr(), xs.as_ptr(), ys.as_ptr(), n,
+                                      count, r_ptr)
+        } {
+            0 => Ok(out),
+            e => Err(Self::batch_error("check_batch_g1", e)),
+        }
+    }
+
+    /// The weight base `check_batch(r = None)` derives: SHA-256 over the buffers' bytes as passed (host only).
+    pub fn batch_challenge(commitments: &[blst_p1], proofs: &[blst_p1], xs: &[blst_fr], ys: &[blst_fr],
+                           n: usize) -> Result<blst_fr, String> {
+        let count = xs.len();
+        if commitments.len() != count || proofs.len() != count || ys.len() != count * n {
+            return Err(String::from("commitments, proofs, xs and ys must describe the same number of tuples"));
+        }
+        let mut r = blst_fr::default();
+        match unsafe { kzgamd_kzg_batch_challenge(&mut r, commitments.as_ptr(), proofs.as_ptr(), xs.as_ptr(), ys.as_ptr(), n, count) } {
+            0 => Ok(r),
+            e => Err(format!("kzgamd_kzg_batch_challenge failed: {e}")),
         }
     }
 

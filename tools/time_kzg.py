@@ -11,6 +11,10 @@ difference between a call and its floor is what the upload of the polynomial and
   open_64x16      n = 64, 16 points                                     floor: 16 MSMs of 2^15 - 64 in one batch
   check_64x16     kzgamd_kzg_check, n = 64, 16 tuples; host_side = the G2 work and the pairings of the same tuples
                   alone, through the library's host helpers (kzgamd_p2_mult / _p2_add / kzgamd_pairings_verify)
+  check_batch_NxC kzgamd_kzg_check_batch (derived r), n = 64 with 16 / 256 / 4096 tuples and n = 1 with 16 / 4096, beside
+                  kzgamd_kzg_check on the same tuples (up to 256) in the same loop; and its stages, each timed alone:
+                  hash = kzgamd_kzg_batch_challenge, g1_sides = kzgamd_kzg_check_batch_g1 with a given r (everything on
+                  the GPU), given_r = kzgamd_kzg_check_batch with a given r (g1_sides + the pairing)
 
 One process, legs alternating, after warm-up; host clock around synchronous calls (every entry point returns when its
 output is in host memory), as tools/time_fk20.py.  The setup points are [i + 1]G (valid G1 points; the time does not
@@ -133,9 +137,46 @@ def main():
             line = json.dumps(row)
             print(line, flush=True)
             f.write(line + "\n")
+    batch_rows(kzg, kz, fp, rnd, reps, budget_gb, out_path, date)
     kz.close()
     floor.close()
     fs.close()
+
+
+def batch_rows(kzg, kz, fp, rnd, reps, budget_gb, out_path, date):
+    """check_batch beside the per-tuple check on the same tuples: 256 openings of the polynomial per n, repeated to 4096"""
+    base = 256
+    xs = [rnd.randrange(1, R) for _ in range(base)]
+    fx = fr_bulk(xs)
+    com = bytes(kz.commit(fp, LEN))[:144]
+    with open(out_path, "a") as f:
+        for n, counts in ((64, (16, 256, 4096)), (1, (16, 4096))):
+            proofs, ys = kz.open(fp, LEN, 1, fx, base, n)
+            proofs, ys, xraw = bytes(proofs)[:144 * base], bytes(ys)[:32 * n * base], bytes(fx)[:32 * base]
+            for count in counts:
+                rep = -(-count // base)
+                c, p_, x_, y_ = com * count, (proofs * rep)[:144 * count], (xraw * rep)[:32 * count], (ys * rep)[:32 * n * count]
+                r = kzg.batch_challenge(c, p_, x_, y_, n, count)
+                legs = [("new", lambda: kz.check_batch(c, p_, x_, y_, n, count)),
+                        ("hash", lambda: kzg.batch_challenge(c, p_, x_, y_, n, count)),
+                        ("g1_sides", lambda: kz.check_batch_g1(c, p_, x_, y_, n, count, r=r)),
+                        ("given_r", lambda: kz.check_batch(c, p_, x_, y_, n, count, r=r))]
+                if count <= 256:
+                    legs.append(("per_tuple_check", lambda: kz.check(c, p_, x_, y_, n, count)))
+                kz.check_batch(c, p_, x_, y_, n, count)  # warm-up: workspaces, the line table of [s^n]G2
+                for _, fn in legs:
+                    fn()
+                ts = {name: [] for name, _ in legs}
+                for _ in range(reps):
+                    for name, fn in legs:
+                        t0 = time.perf_counter()
+                        fn()
+                        ts[name].append((time.perf_counter() - t0) * 1e3)
+                row = {"date": date, "row": "check_batch_%dx%d" % (n, count), "len": LEN, "table_budget_gb": budget_gb}
+                row.update({name: stats(v) for name, v in ts.items()})
+                line = json.dumps(row)
+                print(line, flush=True)
+                f.write(line + "\n")
 
 
 if __name__ == "__main__":
