@@ -531,6 +531,50 @@ C_KZG_RET kzgamd_recover_cells_and_kzg_proofs_batch(Cell *recovered_cells, KZGPr
 C_KZG_RET verify_cell_kzg_proof_batch(bool *ok, const Bytes48 *commitments_bytes, const uint64_t *cell_indices,
                                       const Cell *cells, const Bytes48 *proofs_bytes, uint64_t num_cells,
                                       const CKZGSettings *s);
+/* kzgamd_verify_cell_kzg_proof_batch_many: nbatch independent verify_cell_kzg_proof_batch inputs in one call under ONE
+ * pairing — the data-column sidecars of a slot, each with its own verdict.  Batch b owns the next num_cells[b] entries
+ * of commitments_bytes / cell_indices / cells / proofs_bytes (concatenated in batch order, the convention of
+ * kzgamd_recover_cells_and_kzg_proofs_batch).  For valid input ok_each[b] is what verify_cell_kzg_proof_batch returns
+ * for batch b alone, and *ok is their conjunction.
+ *   Inner challenges: r_b = compute_verify_cell_kzg_proof_batch_challenge of batch b alone (over its own de-duplicated
+ *     commitments in order of first appearance; a batch of zero cells hashes its header only and contributes no points).
+ *   Outer weights: rho_b = rho^b (rho_0 = 1).
+ *     rho == NULL: rho = hash_to_bls_field(SHA-256("KZGAMD_VCELLSET1" (16 bytes) | u64_be(nbatch) | the nbatch r_b as
+ *       canonical 32-byte big-endian scalars)) — the digest as a big-endian integer mod the group order;
+ *     rho != NULL (Montgomery): used as given, for callers with a transcript of their own (and for tests).  Such a rho
+ *       MUST be fixed after every input of the call is: a rho the prover can anticipate lets errors of different
+ *       batches cancel (rho = 1 adds the batches up unweighted, rho = 0 checks batch 0 alone).
+ *   With (P_b, L_b) the reference's pair of batch b (proof_lincomb and the right-hand side, das.rs:294-389):
+ *     P = sum rho_b P_b,   L = sum rho_b L_b,   *ok = e(L, G2) == e(P, [s^64]G2).
+ * One call makes one set of uploads, one aggregated interpolation polynomial (sum_b rho_b I_b is 64 coefficients: the
+ * outer weights are folded into the cell weights rho_b r_b^i), one two-row MSM over [all proofs | the commitments
+ * de-duplicated across the call | g1_monomial[0..64)] and one download; the r_b are hashed on up to 8 host threads
+ * meanwhile.  The cells go to the GPU as passed and are range-checked there.
+ * ok_each (may be NULL): when the combined check passes every entry is true; when it fails the entries are
+ * verify_cell_kzg_proof_batch's, batch by batch (nbatch more pairings: the slow path, taken only on failure).
+ * Anything the single call rejects, in any batch (index >= 128, cell element >= r, bad G1 encoding, proof or
+ * commitment outside G1), and a NULL argument, is C_KZG_BADARGS with nothing written.  nbatch = 0: *ok = true (the
+ * input arrays are not looked at); batches without cells are true.
+ * kzgamd_verify_cell_kzg_proof_batch_many_g1: out[0] = P, out[1] = L (Jacobian) of the same inputs and the same rho, no
+ * pairing, for callers that pair themselves; nbatch = 0, or no cells at all: two identities.
+ * kzgamd_vcells_info: the number of cells one wave of the aggregation kernel sums (a column with more is cut into
+ * slices of that many); returns 0.
+ * kzgamd_vcells_timing: host wall-clock milliseconds of the stages of the last _many / _many_g1 call on `s` that
+ * reached the GPU, for measurements (tools/time_verify_cells_many.py): [0] de-duplication and staging until the decode
+ * is enqueued, [1] handing the cells to the copy engine, [2] until every r_b is hashed (from the same start as [1]: the
+ * upload and the table building run beside the hashes), [3] rho, weights and row scalars, [4] the aggregation kernels
+ * to the 64 coefficients, [5] the two-row MSM with the wait for the decode, [6] the pairing, [7] the per-batch fallback
+ * (0 when not taken; [6] and [7] are _many's).  0 ok, -1 NULL argument or unknown settings. */
+C_KZG_RET kzgamd_verify_cell_kzg_proof_batch_many(bool *ok, bool *ok_each, const Bytes48 *commitments_bytes,
+                                                  const uint64_t *cell_indices, const Cell *cells,
+                                                  const Bytes48 *proofs_bytes, const uint64_t *num_cells, size_t nbatch,
+                                                  const blst_fr *rho, const CKZGSettings *s);
+C_KZG_RET kzgamd_verify_cell_kzg_proof_batch_many_g1(blst_p1 out[2], const Bytes48 *commitments_bytes,
+                                                     const uint64_t *cell_indices, const Cell *cells,
+                                                     const Bytes48 *proofs_bytes, const uint64_t *num_cells, size_t nbatch,
+                                                     const blst_fr *rho, const CKZGSettings *s);
+int kzgamd_vcells_info(size_t *slice_cells);
+int kzgamd_vcells_timing(const CKZGSettings *s, double ms[8]);
 /* blst/src/eip_7594.rs:35-97: the Fiat-Shamir scalar of a cell batch over DEDUPLICATED commitments (Montgomery blst_fr) */
 C_KZG_RET compute_verify_cell_kzg_proof_batch_challenge(blst_fr *challenge_out, const Bytes48 *commitment_bytes,
                                                         uint64_t num_commitments, const uint64_t *commitment_indices,

@@ -77,6 +77,8 @@ EXPORTS = [
     "bytes_to_kzg_commitment", "bytes_from_bls_field", "compute_cells_and_kzg_proofs",
     "recover_cells_and_kzg_proofs", "verify_cell_kzg_proof_batch", "compute_verify_cell_kzg_proof_batch_challenge",
     "kzgamd_recover_cells_and_kzg_proofs_batch",
+    "kzgamd_verify_cell_kzg_proof_batch_many", "kzgamd_verify_cell_kzg_proof_batch_many_g1", "kzgamd_vcells_info",
+    "kzgamd_vcells_timing",
     "kzgamd_compute_cells_and_kzg_proofs_batch", "kzgamd_compute_challenges_and_evaluate_batch",
     "kzgamd_blob_to_kzg_commitment_batch", "kzgamd_blob_to_kzg_commitment_device", "kzgamd_settings_msm_handle",
     "kzgamd_msm_reserve", "kzgamd_msm_device", "kzgamd_set_device", "kzgamd_get_device", "kzgamd_settings_device",
@@ -316,6 +318,14 @@ def lib():
     L.kzgamd_compute_cells_and_kzg_proofs_batch.restype = C.c_int
     L.kzgamd_compute_cells_and_kzg_proofs_batch.argtypes = [vp, vp, vp, sz, sp]
     L.kzgamd_recover_cells_and_kzg_proofs_batch.argtypes = [vp, vp, vp, vp, vp, sz, sp]
+    L.kzgamd_verify_cell_kzg_proof_batch_many.restype = C.c_int
+    L.kzgamd_verify_cell_kzg_proof_batch_many.argtypes = [vp, vp, vp, vp, vp, vp, vp, sz, vp, sp]
+    L.kzgamd_verify_cell_kzg_proof_batch_many_g1.restype = C.c_int
+    L.kzgamd_verify_cell_kzg_proof_batch_many_g1.argtypes = [vp, vp, vp, vp, vp, vp, sz, vp, sp]
+    L.kzgamd_vcells_info.restype = C.c_int
+    L.kzgamd_vcells_info.argtypes = [vp]
+    L.kzgamd_vcells_timing.restype = C.c_int
+    L.kzgamd_vcells_timing.argtypes = [sp, vp]
     L.kzgamd_settings_msm_handle.restype = vp
     L.kzgamd_settings_msm_handle.argtypes = [sp]
     L.kzgamd_msm_reserve.restype = RustError
@@ -1345,6 +1355,65 @@ def verify_cell_kzg_proof_batch(commitments: bytes, cell_indices, cells: bytes, 
     if rc != C_KZG_OK:
         raise KzgAmdError("verify_cell_kzg_proof_batch: C_KZG_RET %d" % rc)
     return bool(ok.value)
+
+
+def _vcells_many_args(batches):
+    """batches: a list of (commitments bytes, cell_indices, cells bytes, proofs bytes), one per batch, as
+    verify_cell_kzg_proof_batch takes them -> the concatenated arrays of the C call"""
+    counts = [len(b[1]) for b in batches]
+    if any(len(b[0]) != 48 * k or len(b[2]) != 2048 * k or len(b[3]) != 48 * k for b, k in zip(batches, counts)):
+        # arrays that do not match their indices cannot be expressed through (pointer, num_cells)
+        raise KzgAmdError("kzgamd_verify_cell_kzg_proof_batch_many: C_KZG_RET %d" % C_KZG_BADARGS)
+    flat = [i for b in batches for i in b[1]]
+    idx = (C.c_uint64 * max(len(flat), 1))(*flat)
+    num = (C.c_uint64 * max(len(batches), 1))(*counts)
+    return b"".join(b[0] for b in batches), idx, b"".join(b[2] for b in batches), b"".join(b[3] for b in batches), num
+
+
+def verify_cell_kzg_proof_batch_many(batches, settings: KZGSettings, rho=None, want_each=True):
+    """kzgamd_verify_cell_kzg_proof_batch_many: len(batches) verify_cell_kzg_proof_batch inputs (tuples of commitments
+    bytes, cell_indices, cells bytes, proofs bytes) under one pairing -> (ok, ok_each): ok_each[b] is the single call's
+    verdict for batch b (None with want_each=False), ok their conjunction.  rho (a BlstFr, Montgomery; None: derived
+    from the batches' own challenges) must be fixed after every input is."""
+    coms, idx, cells, proofs, num = _vcells_many_args(batches)
+    n = len(batches)
+    ok = C.c_bool(False)
+    per = (C.c_bool * max(1, n))() if want_each else None
+    rc = lib().kzgamd_verify_cell_kzg_proof_batch_many(C.byref(ok), per, coms, idx, cells, proofs, num, n, _one_fr(rho),
+                                                       C.byref(settings.c))
+    if rc != C_KZG_OK:
+        raise KzgAmdError("kzgamd_verify_cell_kzg_proof_batch_many: C_KZG_RET %d" % rc)
+    return bool(ok.value), ([bool(per[b]) for b in range(n)] if want_each else None)
+
+
+def verify_cell_kzg_proof_batch_many_g1(batches, settings: KZGSettings, rho=None):
+    """The two G1 sides of verify_cell_kzg_proof_batch_many, no pairing: (BlstP1 * 2) = P, L with
+    e(L, G2) == e(P, g2_values_monomial[64]) the verdict"""
+    coms, idx, cells, proofs, num = _vcells_many_args(batches)
+    out = (BlstP1 * 2)()
+    rc = lib().kzgamd_verify_cell_kzg_proof_batch_many_g1(out, coms, idx, cells, proofs, num, len(batches), _one_fr(rho),
+                                                          C.byref(settings.c))
+    if rc != C_KZG_OK:
+        raise KzgAmdError("kzgamd_verify_cell_kzg_proof_batch_many_g1: C_KZG_RET %d" % rc)
+    return out
+
+
+def vcells_info() -> int:
+    """kzgamd_vcells_info: the cells one wave of the aggregation kernel sums (the slice length a column is cut into)"""
+    out = C.c_size_t(0)
+    lib().kzgamd_vcells_info(C.byref(out))
+    return out.value
+
+
+VCELLS_STAGES = ("prepare", "upload", "hash", "scalars", "aggregate", "msm", "pairing", "fallback")
+
+
+def vcells_timing(settings: KZGSettings):
+    """kzgamd_vcells_timing: {stage: host ms} of the last verify_cell_kzg_proof_batch_many(_g1) call on `settings`"""
+    ms = (C.c_double * 8)()
+    if lib().kzgamd_vcells_timing(C.byref(settings.c), ms) != 0:
+        raise KzgAmdError("kzgamd_vcells_timing")
+    return dict(zip(VCELLS_STAGES, ms))
 
 
 def compute_verify_cell_kzg_proof_batch_challenge(commitments: bytes, commitment_indices, cell_indices, cells: bytes, proofs: bytes):

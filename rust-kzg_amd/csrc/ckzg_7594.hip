@@ -863,6 +863,26 @@ void recover_cells_batch(Cell* recovered_cells, KZGProof* recovered_proofs, cons
 
 }  // namespace
 
+// the parts of verify_cell_kzg_proof_batch that ckzg_vcells.hip is built from (ckzg_shared.h)
+namespace ckz {
+ff::Fr vc_challenge(const Bytes48* commitments, size_t ncommit, const uint64_t* commitment_indices, const uint64_t* cell_indices,
+                    const Cell* cells, const Bytes48* proofs, size_t ncells) {
+    return cell_batch_challenge(commitments, ncommit, commitment_indices, cell_indices, cells, proofs, ncells);
+}
+ff::Fr vc_hash_to_fr(const uint8_t digest[32]) { return hash_to_fr(digest); }
+void vc_decode_begin(KzgAmdSettings* dev, const std::vector<uint8_t>& bytes, size_t np, const g1::AffPt* tail, size_t ntail) {
+    decode_points_begin(dev, bytes, np, tail, ntail);
+}
+std::vector<int> vc_decode_status(KzgAmdSettings* dev, size_t np) { return decode_points_status(dev, np); }
+void vc_interp_enqueue(ff::Fr* out, const ff::Fr* v, const ff::Fr* roots8192, hipStream_t st) {
+    hipLaunchKernelGGL(k_vcell_interp, dim3((unsigned)CELL_SIZE), dim3((unsigned)CELLS_PER_EXT_BLOB), 0, st, out, v, roots8192);
+}
+void vc_verify_single(bool* ok, const Bytes48* commitments_bytes, const uint64_t* cell_indices, const Cell* cells,
+                      const Bytes48* proofs_bytes, size_t n, const CKZGSettings* cs, KzgAmdSettings* dev) {
+    verify_cells(ok, commitments_bytes, cell_indices, cells, proofs_bytes, n, cs, dev);
+}
+}  // namespace ckz
+
 // c_bindings.rs:290-355 -> DAS::verify_cell_kzg_proof_batch (kzg/src/das.rs:294-389)
 extern "C" C_KZG_RET verify_cell_kzg_proof_batch(bool* ok, const Bytes48* commitments_bytes, const uint64_t* cell_indices,
                                                  const Cell* cells, const Bytes48* proofs_bytes, uint64_t num_cells,

@@ -1,5 +1,6 @@
 // Shared internals of the c-kzg layer (ckzg.hip: settings object, lanes, EIP-4844 proving; ckzg_verify.hip: the verify_*
-// entry points and the host pairing exports; ckzg_7594.hip: cells, FK20, recovery, cell verification).  Types and
+// entry points and the host pairing exports; ckzg_7594.hip: cells, FK20, recovery, cell verification; ckzg_vcells.hip:
+// many cell-proof batches under one pairing).  Types and
 // templates every one of them needs, and the functions one of them defines for the others (namespace ckz).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -400,6 +401,41 @@ struct KzgAmdSettings {
         CK_HIP(hipMalloc(&d_vc_pw, cap * sizeof(ff::Fr)));
         cap_vc = cap;
     }
+    // kzgamd_verify_cell_kzg_proof_batch_many (ckzg_vcells.hip): the cells as the caller passed them, the weights
+    // rho^b r_b^i, the tables of k_vcells_agg / k_vcells_fold ([129 partial-row starts | 2 words per slice | the cells
+    // grouped by column]), one partial row of 64 sums per slice, and the "an element is >= r" word
+    static constexpr size_t VCELLS_SLICE = 8;  // cells per wave of k_vcells_agg (kzgamd_vcells_info)
+    unsigned char* d_vm_cells = nullptr;
+    ff::Fr* d_vm_w = nullptr;
+    u32* d_vm_tab = nullptr;
+    ff::Fr* d_vm_part = nullptr;
+    int* d_vm_status = nullptr;
+    size_t cap_vm = 0;
+    double vm_ms[8] = {};  // host wall time of the stages of the last such call (kzgamd_vcells_timing)
+    static size_t vcells_many_slices(size_t n) { return n / VCELLS_SLICE + 2 * CELLS_PER_BLOB; }  // at most, for n cells
+    void release_vcells_many() {
+        if (d_vm_cells) (void)hipFree(d_vm_cells);
+        if (d_vm_w) (void)hipFree(d_vm_w);
+        if (d_vm_tab) (void)hipFree(d_vm_tab);
+        if (d_vm_part) (void)hipFree(d_vm_part);
+        if (d_vm_status) (void)hipFree(d_vm_status);
+        d_vm_cells = nullptr;
+        d_vm_w = d_vm_part = nullptr;
+        d_vm_tab = nullptr;
+        d_vm_status = nullptr;
+        cap_vm = 0;
+    }
+    void ensure_vcells_many(size_t n) {
+        if (n <= cap_vm) return;
+        release_vcells_many();
+        const size_t cap = n < 128 ? 128 : n, ns = vcells_many_slices(cap);
+        CK_HIP(hipMalloc(&d_vm_cells, cap * CELL_SIZE * 32));
+        CK_HIP(hipMalloc(&d_vm_w, cap * sizeof(ff::Fr)));
+        CK_HIP(hipMalloc(&d_vm_tab, (2 * CELLS_PER_BLOB + 1 + 2 * ns + cap) * sizeof(u32)));
+        CK_HIP(hipMalloc(&d_vm_part, ns * CELL_SIZE * sizeof(ff::Fr)));
+        CK_HIP(hipMalloc(&d_vm_status, sizeof(int)));
+        cap_vm = cap;
+    }
     // the coset tables and the single call's index buffer once; the per-blob buffers for nblobs blobs (kept, grown on demand)
     void ensure_recover(size_t nblobs) {
         if (!d_pow7inv) {
@@ -472,6 +508,7 @@ struct KzgAmdSettings {
         if (d_vc_cells) (void)hipFree(d_vc_cells);
         if (d_vc_cols) (void)hipFree(d_vc_cols);
         if (d_vc_pw) (void)hipFree(d_vc_pw);
+        release_vcells_many();
         if (d_rec_idx) (void)hipFree(d_rec_idx);
         if (d_pow7) (void)hipFree(d_pow7);
         if (d_pow7inv) (void)hipFree(d_pow7inv);
@@ -563,6 +600,20 @@ void prove_batch(KZGProof* proofs, Bytes32* ys, const Blob* blobs, const Bytes32
 // ---- defined in ckzg_verify.hip
 void verify_g1_begin(const Bytes48* commitments, const Bytes48* proofs, size_t n, KzgAmdSettings* dev);
 void verify_g1_finish(blst_p1* proof_lincomb, blst_p1* rhs, const Bytes48* commitments, const Bytes32* zs, const Bytes32* ys, const Bytes48* proofs, size_t n, KzgAmdSettings* dev);
+// ---- defined in ckzg_7594.hip: what verify_cell_kzg_proof_batch is made of, for ckzg_vcells.hip
+// compute_verify_cell_kzg_proof_batch_challenge (das.rs:391-452) on the caller's bytes, Montgomery form
+ff::Fr vc_challenge(const Bytes48* commitments, size_t ncommit, const uint64_t* commitment_indices, const uint64_t* cell_indices,
+                    const Cell* cells, const Bytes48* proofs, size_t ncells);
+ff::Fr vc_hash_to_fr(const uint8_t digest[32]);  // hash_to_bls_field
+// decode + both tests of np compressed points on stream2 into dev->d_vpts / d_vstat, `ntail` ready slots appended;
+// the status words (0 ok, 1 not an encoding of a curve point, 2 outside G1) once stream2 has drained.  Caller holds dev->vmu.
+void vc_decode_begin(KzgAmdSettings* dev, const std::vector<uint8_t>& bytes, size_t np, const g1::AffPt* tail, size_t ntail);
+std::vector<int> vc_decode_status(KzgAmdSettings* dev, size_t np);
+// out[k] = sum_col v[col][k] h_col^-k, k < 64 (k_vcell_interp): enqueue only
+void vc_interp_enqueue(ff::Fr* out, const ff::Fr* v, const ff::Fr* roots8192, hipStream_t st);
+// verify_cell_kzg_proof_batch of n > 0 cells (takes dev->vmu)
+void vc_verify_single(bool* ok, const Bytes48* commitments_bytes, const uint64_t* cell_indices, const Cell* cells,
+                      const Bytes48* proofs_bytes, size_t n, const CKZGSettings* cs, KzgAmdSettings* dev);
 }  // namespace ckz
 using namespace ckz;
 

@@ -837,6 +837,17 @@ pub mod ckzg {
                                                          n: usize, s: &CKZGSettings) -> CKzgRet;
         pub fn verify_cell_kzg_proof_batch(ok: *mut bool, commitments_bytes: *const Bytes48, cell_indices: *const u64,
                                            cells: *const Cell, proofs_bytes: *const Bytes48, num_cells: u64, s: &CKZGSettings) -> CKzgRet;
+        /// `nbatch` cell-proof batches (data-column sidecars) under one pairing; batch b owns the next `num_cells[b]`
+        /// entries of the four arrays.  `ok_each` and `rho` may be null (`rho`: derived from the batches' challenges).
+        pub fn kzgamd_verify_cell_kzg_proof_batch_many(ok: *mut bool, ok_each: *mut bool, commitments_bytes: *const Bytes48,
+                                                       cell_indices: *const u64, cells: *const Cell, proofs_bytes: *const Bytes48,
+                                                       num_cells: *const u64, nbatch: usize, rho: *const blst::blst_fr,
+                                                       s: &CKZGSettings) -> CKzgRet;
+        pub fn kzgamd_verify_cell_kzg_proof_batch_many_g1(out: *mut blst::blst_p1, commitments_bytes: *const Bytes48,
+                                                          cell_indices: *const u64, cells: *const Cell,
+                                                          proofs_bytes: *const Bytes48, num_cells: *const u64, nbatch: usize,
+                                                          rho: *const blst::blst_fr, s: &CKZGSettings) -> CKzgRet;
+        pub fn kzgamd_vcells_info(slice_cells: *mut usize) -> core::ffi::c_int;
         // batched and multi-GPU forms (new API, include/kzg_mi355x.h): contiguous slabs of the batch per settings object
         pub fn kzgamd_blob_to_kzg_commitment_batch(out: *mut KZGCommitment, blobs: *const Blob, n: usize, s: &CKZGSettings) -> CKzgRet;
         pub fn kzgamd_compute_blob_kzg_proof_batch(out: *mut KZGProof, blobs: *const Blob, commitments: *const Bytes48, n: usize,
