@@ -310,7 +310,11 @@ __device__ __forceinline__ void ntt_round(u32* sh, Fr* __restrict__ out, const F
 //   execute in order, no barrier — so a wave that has its data starts computing while others still wait for theirs,
 //   and a 4096-point transform synchronises the workgroup once (between stages 5 and 6).
 //   Butterflies are lazy (fr29.hip.h): a round's inputs have normalised limbs, its outputs are renormalised once;
-//   values grow by < 5r per stage (8r for the multiplication-free stage 1 of a transform): < 61r after 12 stages.
+//   values grow by < 5r per stage.  A transform's first two stages: x + y and x + 4r - y (< 5r for inputs below r), then
+//   (x + y) + 8r - y' with x + y < 2r, or < 5r + 5r: < 10r after two stages, < 60r after 12.  The forward half of the
+//   fused DAS extension starts below 2r (< 12r after two stages, < 62r after 12), as does any 256-bit input (< 62.5r):
+//   always below the 64r that mul_signed, reduce_lazy and finish take.  tests/ntt_lazy_model.py computes the values
+//   exactly; its worst inputs reach 58.3r (canonical), 57.6r (DAS forward half) and 59.0r (inputs of 2^256 - 1).
 template <int KIND, int V>
 __global__ void __launch_bounds__(NT) k_ntt_pass(Fr* __restrict__ out, const Fr* __restrict__ in, const PassParams P) {
     extern __shared__ __attribute__((aligned(16))) u32 sh[];

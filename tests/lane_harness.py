@@ -1,5 +1,6 @@
-"""Builds and runs tests/device_checks/lane_check.hip for the lane-arithmetic tests (the GPU module and the
-cross-compilation check of the CPU module).  The compiler and the flags are the product's, from rust-kzg_amd/build.py."""
+"""Builds the test-only device harnesses under tests/device_checks/ — lane_check.hip for the lane-arithmetic tests,
+fr_check.hip for the Fr arithmetic of the NTT — for the GPU modules and the cross-compilation checks of the CPU modules.
+The compiler and the flags are the product's, from rust-kzg_amd/build.py."""
 import importlib.util
 import os
 import subprocess
@@ -13,6 +14,12 @@ SOURCE = os.path.join(HERE, "device_checks", "lane_check.hip")
 DEFINE_SETS = {"product": [], "exact": ["-DKZGAMD_FORCE_EXACT_TESTS"], "digit_ahead": ["-DKZGAMD_WMUL_DIGIT_AHEAD"]}
 PLANTED = {"planted": ["-DLANE_CHECK_PLANT_ERROR"]}
 
+# fr_check.hip: the product's form, mul_signed without the opaque accumulator chain (the form tools/ instantiate), and
+# the planted errors
+FR_SOURCE = os.path.join(HERE, "device_checks", "fr_check.hip")
+FR_DEFINE_SETS = {"product": [], "unchained": ["-DFR_CHECK_UNCHAINED"]}
+FR_PLANTED = {"planted": ["-DFR_CHECK_PLANT_ERROR"]}
+
 
 def product_build():
     spec = importlib.util.spec_from_file_location("rust_kzg_amd_build", os.path.join(ROOT, "rust-kzg_amd", "build.py"))
@@ -21,17 +28,18 @@ def product_build():
     return mod
 
 
-def compile_command(out, defines):
+def compile_command(out, defines, source=SOURCE):
     b = product_build()
-    return [b.hipcc_path()] + list(b.COMPILE_FLAGS) + list(defines) + ["-I", CSRC, SOURCE, "-o", out]
+    return [b.hipcc_path()] + list(b.COMPILE_FLAGS) + list(defines) + ["-I", CSRC, source, "-o", out]
 
 
-def compile_all(outdir, define_sets):
+def compile_all(outdir, define_sets, source=SOURCE):
     """name -> executable; the compilations run side by side (a device compilation of these headers is one thread)"""
     procs = {}
+    stem = os.path.splitext(os.path.basename(source))[0]
     for name, defines in define_sets.items():
-        out = os.path.join(str(outdir), "lane_check_" + name)
-        procs[name] = (out, subprocess.Popen(compile_command(out, defines), stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True))
+        out = os.path.join(str(outdir), stem + "_" + name)
+        procs[name] = (out, subprocess.Popen(compile_command(out, defines, source), stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True))
     built, errors = {}, {}
     for name, (out, p) in procs.items():
         log, _ = p.communicate()

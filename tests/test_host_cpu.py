@@ -953,100 +953,14 @@ def test_fr29_butterfly_arithmetic_at_its_documented_bounds(tmp_path):
     butterfly_lazy / butterfly_lazy8 (value identities, no limb wraps), one radix-4 round exactly as ntt.hip's ntt_round
     chains them (two butterfly levels, then ONE carry pass: limbs normalised, value grown by < 10r, never negative),
     reduce_lazy on EVERY multiple of r below 64r and its neighbours (its quotient estimate is off by one there or
-    nowhere), finish, mul."""
-    import random
+    nowhere), finish, mul.  The same cases run on the device in tests/test_fr_arith_gpu.py."""
     import shutil
     import subprocess
 
-    R = 0x73eda753299d7d483339d80809a1d80553bda402fffe5bfeffffffff00000001
-    M29 = (1 << 29) - 1
-    RINV = pow(1 << 261, -1, R)
-    rnd = random.Random(2929)
+    import fr29_cases
 
-    def limbs(v):
-        assert 0 <= v < 1 << (232 + 31)
-        return [(v >> (29 * i)) & M29 for i in range(8)] + [v >> 232]
-
-    def sval(l):  # top limb signed
-        top = l[8] - (1 << 32) if l[8] >> 31 else l[8]
-        return sum(x << (29 * i) for i, x in enumerate(l[:8])) + (top << 232)
-
-    def edge(k):
-        out = [0, 1, k * R - 1, (1 << 232) - 1, 1 << 232]
-        for j in range(0, k, max(1, k // 8)):
-            out += [j * R, j * R + 1, max(0, j * R - 1)]
-        return [v for v in out if v < k * R] + [rnd.randrange(k * R) for _ in range(30)]
-
-    cases = []
-
-    def normalized(l):
-        return all(x <= M29 for x in l[:8]) and not l[8] >> 31
-
-    # ---- one radix-4 round, the way ntt_round<..., FIRST = false> runs it: inputs normalised, value < 51r ----
-    def chk_round(es, ws):
-        def net(e, w):
-            e = list(e)
-            for (a, b, wi) in ((0, 1, 0), (2, 3, 1), (0, 2, 2), (1, 3, 3)):
-                t = e[b] * w[wi] * RINV
-                e[a], e[b] = e[a] + t, e[a] - t
-            return e
-
-        want = net(es, ws)
-
-        def chk(out):
-            got = [out[9 * i:9 * i + 9] for i in range(4)]
-            for g, w, e in zip(got, want, es):
-                assert normalized(g), "round output not normalised"
-                assert (sval(g) - w) % R == 0, "round residue"
-                assert 0 <= sval(g) < max(es) + 10 * R + 1, "round growth"
-        return chk
-
-    for _ in range(400):
-        top = rnd.choice([1, 2, 8, 30, 51])
-        es = [rnd.choice(edge(top)) for _ in range(4)]
-        ws = [rnd.choice([0, 1, R - 1, rnd.randrange(R), rnd.randrange(R)]) for _ in range(4)]
-        cases.append(("round", [limbs(e) for e in es] + [limbs(w) for w in ws], chk_round(es, ws)))
-    # ---- mul_signed alone on lazy multiplicands: limbs up to 1.5 * 2^30, top limb down to -1 ----
-    for _ in range(400):
-        a = [rnd.randrange(3 << 29) for _ in range(8)] + [rnd.choice([0, 1, 0xFFFFFFFF, rnd.randrange(64 * 0x73eda7)])]
-        if not -R < sval(a) < 64 * R:
-            continue
-        b = rnd.choice([0, 1, R - 1, rnd.randrange(R)])
-
-        def chk(out, want=sval(a) * b):
-            assert all(x <= M29 for x in out[:8]) and -R < sval(out) < R and (sval(out) - want * RINV) % R == 0
-        cases.append(("msig", [a, limbs(b)], chk))
-    # ---- the three butterflies: values and limb growth ----
-    for _ in range(300):
-        x = rnd.choice(edge(51))
-        t = rnd.randrange(-R + 1, 2 * R)  # what mul_signed returns, or a normalised value below 2r
-        tl = [(t >> (29 * i)) & M29 for i in range(8)] + [(t >> 232) & 0xFFFFFFFF]
-
-        def chk_s(out, x=x, t=t):
-            a, b = out[:9], out[9:]
-            assert sval(a) == x + t + R and sval(b) == x + 4 * R - t
-            assert all(v < (1 << 29) + (1 << 30) for v in a[:8] + b[:8])
-        cases.append(("bfs", [limbs(x), tl], chk_s))
-        t3 = rnd.choice(edge(3))
-        cases.append(("bfl", [limbs(x), limbs(t3)], lambda out, x=x, t=t3: (sval(out[:9]) == x + t and sval(out[9:]) == x + 4 * R - t and all(v < 3 << 29 for v in out[:8] + out[9:17])) or (_ for _ in ()).throw(AssertionError("bfl"))))
-        t7 = rnd.choice(edge(7))
-        cases.append(("bfl8", [limbs(x), limbs(t7)], lambda out, x=x, t=t7: (sval(out[:9]) == x + t and sval(out[9:]) == x + 8 * R - t and all(v < 3 << 29 for v in out[:8] + out[9:17])) or (_ for _ in ()).throw(AssertionError("bfl8"))))
-    # ---- reduce_lazy / finish: every multiple of r below 64r with its neighbours, the maximum, random ----
-    vals = [64 * R - 1]
-    for j in range(64):
-        vals += [j * R, j * R + 1, j * R + R - 1, j * R + (R >> 1)]
-    vals += [rnd.randrange(64 * R) for _ in range(3000)]
-    for v in vals:
-        cases.append(("redl", [limbs(v)], lambda out, v=v: sum(x << (32 * i) for i, x in enumerate(out)) == v % R or (_ for _ in ()).throw(AssertionError("reduce_lazy %x" % v))))
-    for v in vals[:600]:
-        m = rnd.choice([1, R - 1, rnd.randrange(R)])
-        cases.append(("fin", [limbs(v), limbs(m)], lambda out, v=v, m=m: sum(x << (32 * i) for i, x in enumerate(out)) == v * m * RINV % R or (_ for _ in ()).throw(AssertionError("finish"))))
-    # ---- mul: multiplicand limbs < 2^31, multiplier normalised, a*b < 2^261 r ----
-    for _ in range(300):
-        a = [rnd.randrange(1 << 31) for _ in range(8)] + [rnd.randrange(64 * 0x73eda7)]
-        b = rnd.randrange(R)
-        if sval(a) * b < (R << 261):
-            cases.append(("mul", [a, limbs(b)], lambda out, w=sval(a) * b: (normalized(out) and sval(out) < 2 * R and (sval(out) - w * RINV) % R == 0) or (_ for _ in ()).throw(AssertionError("mul"))))
+    cases = fr29_cases.base_cases()  # the construction lives in tests/fr29_cases.py, shared with the device harness
+    sval = fr29_cases.sval
 
     cxx = shutil.which("g++") or shutil.which("clang++") or "/opt/rocm/lib/llvm/bin/clang++"
     src = tmp_path / "fr29check.cpp"

@@ -255,3 +255,77 @@ def test_three_pass_2p25_matches_oracle(kzg, oracle):
     assert bytes(back) == raw.tobytes()
     L.offt_settings_free(C.byref(ofs))
     fs.close()
+
+
+# ---- the stored worst-case inputs (tests/golden/ntt_worst_inputs.json): built by tests/ntt_lazy_model.py so that the
+# lazy values inside a pass come within a few r of the bound reduce_lazy / finish / the twist rely on (< 64r) — 57r to
+# 59r at n = 4096 where random inputs stop at 53r.  tests/test_fr_device_cases_cpu.py holds the vectors to the model.
+def _worst_vectors():
+    import json
+    import os
+
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ntt_worst_inputs.json")) as f:
+        return json.load(f)["vectors"]
+
+
+WORST = {v["name"]: v for v in _worst_vectors()}
+
+
+def _expected(L, v, rows):
+    """per transform the 32 n bytes the library must return: the oracle's for canonical inputs; for an input with
+    elements >= r the oracle's behaviour is not defined and the exact-integer model's residues stand in"""
+    import ntt_lazy_model as M
+
+    n = 1 << v["logn"]
+    if any(x >= O.R for row in rows for x in row):
+        assert v["name"] == "fwd4096_fill_2p256_minus_1"
+        return [b"".join(x.to_bytes(32, "little") for x in out) for out in M.run_vector(v)[2]]
+    scale = v["logn"] + 1 if v["shape"] == "das" else max(v["logn"], 1)
+    ofs = O.FFTSettings()
+    assert L.offt_settings_new(C.byref(ofs), scale) == 0
+    exp = []
+    for row in rows:
+        one = (O.Fr * n).from_buffer_copy(b"".join(x.to_bytes(32, "little") for x in row))
+        e = (O.Fr * n)()
+        if v["shape"] == "das":
+            assert L.odas_fft_extension(C.byref(ofs), e, one, n) == 0
+        else:
+            assert L.offt_fr(C.byref(ofs), e, one, n, 1 if v["shape"] == "inv" else 0) == 0
+        exp.append(bytes(e))
+    L.offt_settings_free(C.byref(ofs))
+    return exp
+
+
+@pytest.mark.parametrize("name", sorted(WORST))
+def test_worst_case_lazy_values_match_oracle(kzg, oracle, name):
+    """every stored vector through fft_fr / das_fft_extension (transform by transform) and through fft_fr_device /
+    das_fft_extension_device (the whole batch in one call: the 512- and 64-point batches fill a tile, each transform
+    aimed at another output), byte for byte"""
+    if kzg.LIB_PATH.endswith("_exact.so"):
+        pytest.skip("the Fr transforms contain no exact-zero test: both builds are the same kernels")
+    import torch
+
+    import ntt_lazy_model as M
+
+    v = WORST[name]
+    n, nbatch, das = 1 << v["logn"], v["nbatch"], v["shape"] == "das"
+    rows = M.materialise(v)
+    exp = _expected(oracle.lib(), v, rows)
+    fs = kzg.FFTSettings(v["logn"] + 1 if das else max(v["logn"], 1))
+    raw = b"".join(x.to_bytes(32, "little") for row in rows for x in row)
+    for b in range(min(nbatch, 4)):
+        one = (O.Fr * n).from_buffer_copy(raw[32 * n * b: 32 * n * (b + 1)])
+        got = fs.das_fft_extension(one, n) if das else fs.fft_fr(one, n, inverse=v["shape"] == "inv")
+        assert bytes(got)[: 32 * n] == exp[b], (name, b)
+    d_in = torch.frombuffer(bytearray(raw), dtype=torch.uint8).cuda()
+    d_out, d_tmp = torch.zeros_like(d_in), torch.zeros_like(d_in)
+    stream = torch.cuda.current_stream().cuda_stream
+    if das:
+        fs.das_fft_extension_device(d_out.data_ptr(), d_in.data_ptr(), d_tmp.data_ptr(), n, nbatch, stream)
+    else:
+        fs.fft_fr_device(d_out.data_ptr(), d_in.data_ptr(), n, nbatch, v["shape"] == "inv", stream)
+    torch.cuda.synchronize()
+    got = d_out.cpu().numpy().tobytes()
+    for b in range(nbatch):
+        assert got[32 * n * b: 32 * n * (b + 1)] == exp[b], (name, "device", b)
+    fs.close()
