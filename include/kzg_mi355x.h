@@ -247,8 +247,13 @@ int kzgamd_fk20_info(void *fk, size_t *n2, size_t *chunk_len, int *form);
  *   n = 1 (check_proof_single, :178-196):  e(com - [y]g1_monomial[0], G2) == e(proof, [s]G2 - [x]G2)
  *   n > 1 (check_proof_multi, :236-277):   e(com - [I(s)]G, G2) == e(proof, [s^n]G2 - [x^n]G2), I = the interpolation
  *         polynomial of the values on the coset: ifft(ys), coefficient i times x^-i.
- * The G1 sides run on the GPU for all tuples together, the G2 sides and one pairing per tuple on the host (as in the
- * reference).  0 ok, 3 n is zero or not a power of two, 4 n > max width, 6 num_g2 <= n (or no G2 setup), 1 n > num_g1,
+ * The G1 sides run on the GPU for all tuples together.  Below the handle's tuning key pairing_gpu_min (tuples per
+ * call; 0 = never) the G2 sides and one pairing per tuple run on the host (as in the reference); from it on the pairings
+ * run on the GPU, one wave per tuple, as e(lhs + [x^n] proof, G2) == e(proof, [s^n]G2) against device line tables kept per
+ * handle and n — for the tuples whose commitment and proof are in G1 (tested on the GPU); the others, and every tuple
+ * of a call with a point off the curve, take the host loop, so the verdicts are the same for every input.
+ * pairing_gpu_min is a key of kzgamd_kzg_new alone, read from cfg->tuning only (-1 ... 1048576; -1, the default, is the
+ * measured built-in, 4): it is not in kzgamd_tuning_keys() and the environment does not carry it.  0 ok, 3 n is zero or not a power of two, 4 n > max width, 6 num_g2 <= n (or no G2 setup), 1 n > num_g1,
  * 5 x == 0 in a tuple with n > 1 — the reference feeds inverse(0) into its arithmetic there (:253-261), which has no
  * meaningful result; negatives as above.  count = 0: ok, nothing written.
  *
@@ -501,6 +506,16 @@ C_KZG_RET kzgamd_verify_blob_kzg_proof_batch_g1(blst_p1 *proof_lincomb_out, blst
  * (1 if e(a1,a2) == e(b1,b2), 0 if not, -1 on NULL); uncompress = FsG2::from_bytes (0 ok, 1 invalid encoding /
  * not on the curve); mult takes a Montgomery blst_fr like G2Mul (blst/src/types/g2.rs:24-39). */
 int kzgamd_pairings_verify(const blst_p1 *a1, const blst_p2 *a2, const blst_p1 *b1, const blst_p2 *b2);
+/* The same check for many G1 pairs against two shared G2 points, ON THE GPU (the calling thread's current device), one
+ * wave per check: ok[i] = e(a1[i], *a2) == e(b1[i], *b2), i < count, the verdicts of kzgamd_pairings_verify item by
+ * item (a side with Z = 0 or an identity G2 point is skipped; two skipped sides give true).  Coordinates are canonical
+ * (below p), as blst produces them: for a Z that is a non-zero multiple of p neither form is defined.  0 ok, -1 NULL argument,
+ * -2 or -(100 + hipError_t) device errors.  count = 0: success, nothing written, the pointers are not looked at.
+ * Thread-safe; the line tables of the G2 points are cached per (device, point); large counts run in slices of
+ * kzgamd_pairing_info's slice_checks (may be NULL; returns 0). */
+int kzgamd_pairings_verify_batch(bool *ok, const blst_p1 *a1, const blst_p2 *a2, const blst_p1 *b1, const blst_p2 *b2,
+                                 size_t count);
+int kzgamd_pairing_info(size_t *slice_checks);
 int kzgamd_p2_uncompress(blst_p2 *out, const uint8_t in[96]);
 void kzgamd_p2_compress(uint8_t out[96], const blst_p2 *in);
 void kzgamd_p2_generator(blst_p2 *out);

@@ -84,6 +84,7 @@ EXPORTS = [
     "kzgamd_msm_reserve", "kzgamd_msm_device", "kzgamd_set_device", "kzgamd_get_device", "kzgamd_settings_device",
     "kzgamd_settings_reserve", "kzgamd_settings_table_info", "kzgamd_verify_kzg_proof_batch_g1", "kzgamd_verify_blob_kzg_proof_batch_g1",
     "verify_kzg_proof", "verify_blob_kzg_proof", "verify_blob_kzg_proof_batch", "kzgamd_pairings_verify",
+    "kzgamd_pairings_verify_batch", "kzgamd_pairing_info",
     "kzgamd_compute_blob_kzg_proof_device",
     "kzgamd_p2_uncompress", "kzgamd_p2_compress", "kzgamd_p2_generator", "kzgamd_p2_mult", "kzgamd_p2_add",
     "kzgamd_load_trusted_setup_file_multi", "kzgamd_free_trusted_setup_multi", "kzgamd_blob_to_kzg_commitment_batch_multi",
@@ -352,6 +353,10 @@ def lib():
     L.verify_blob_kzg_proof_batch.argtypes = [bp, vp, vp, vp, sz, sp]
     L.kzgamd_pairings_verify.restype = C.c_int
     L.kzgamd_pairings_verify.argtypes = [vp, vp, vp, vp]
+    L.kzgamd_pairings_verify_batch.restype = C.c_int
+    L.kzgamd_pairings_verify_batch.argtypes = [vp, vp, vp, vp, vp, C.c_size_t]
+    L.kzgamd_pairing_info.restype = C.c_int
+    L.kzgamd_pairing_info.argtypes = [vp]
     L.kzgamd_p2_uncompress.restype = C.c_int
     L.kzgamd_p2_uncompress.argtypes = [vp, vp]
     L.kzgamd_p2_compress.restype = None
@@ -1239,6 +1244,30 @@ def pairings_verify(a1, a2, b1, b2) -> bool:
     if rc < 0:
         raise KzgAmdError("kzgamd_pairings_verify")
     return rc == 1
+
+
+def pairings_verify_batch(a1, a2, b1, b2):
+    """[e(a1[i], a2) == e(b1[i], b2)] for sequences (or ctypes arrays) of BlstP1 against two shared BlstP2 values, on the
+    GPU, one wave per check: kzgamd_pairings_verify's verdicts item by item."""
+    n = len(a1)
+    if len(b1) != n:
+        raise KzgAmdError("kzgamd_pairings_verify_batch: %d against %d G1 points" % (n, len(b1)))
+    if n == 0:
+        return []
+    aa = a1 if isinstance(a1, C.Array) else (BlstP1 * n)(*a1)
+    bb = b1 if isinstance(b1, C.Array) else (BlstP1 * n)(*b1)
+    ok = (C.c_bool * n)()
+    rc = lib().kzgamd_pairings_verify_batch(ok, aa, C.byref(a2), bb, C.byref(b2), n)
+    if rc != 0:
+        raise KzgAmdError("kzgamd_pairings_verify_batch: %d" % rc)
+    return [bool(v) for v in ok]
+
+
+def pairing_info() -> int:
+    """the checks one launch of pairings_verify_batch takes (larger batches run in slices)"""
+    out = C.c_size_t(0)
+    lib().kzgamd_pairing_info(C.byref(out))
+    return out.value
 
 
 def p2_uncompress(b: bytes) -> BlstP2:

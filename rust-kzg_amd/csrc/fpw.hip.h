@@ -100,6 +100,11 @@ __device__ __forceinline__ u32 rows4(int row, u32 a0, u32 a1, u32 a2, u32 a3) {
 // the quotient digit off the first multiply-add — m = acc_0 * p' + (a_0 * p') * b_j mod 2^28, the second product known
 // before the chain starts: six instructions on the chain, but nine issued, and in-order issue puts the three others on
 // the path: 1.48 us per doubling against 1.40 (tools/wmul_bench.hip; same checksums: the digits are the same digits).
+// Contract beyond the product bound of the header (fp12w.hip.h relies on it; tests/test_pairing_arith_gpu.py runs it on
+// every tower operation): the chain is exact Montgomery for ANY operands with limbs 0..12 <= 2^29 and lanes 14, 15 zero —
+// the result is (a*b + m*p) / 2^392 with m < 2^392, normalized, value < a*b / 2^392 + p — as long as the accumulator
+// fits: its value stays below 2a + 2p, so for a, b < 1000p the top limb stays below 2^28 and no product or sum of a
+// step reaches 2^64 / 2^32.  a*b < 2520 p^2 is the case "value < 2p".  A change to this routine must keep both.
 __device__ __forceinline__ u32 wmul4(u32 a, u32 b, const Lane& c) {
     u32 acc = 0;
     // the 14 broadcasts of b do not depend on the accumulator chain: taken up front, they leave the chain

@@ -61,7 +61,9 @@
 #include "host_fp64.h"
 #include "host_pairing.h"
 #include "msm_internal.h"
+#include "glv.hip.h"
 #include "ntt_internal.h"
+#include "pairing_internal.h"
 #include "sha256.h"
 
 using ff::Fr;
@@ -219,6 +221,35 @@ __global__ void __launch_bounds__(64) k_kzg_g1_sub(ff::Fp* __restrict__ out, con
     g1::to_blst_jacobian(out + 3 * t, A);
 }
 
+// ---- check on the GPU (pairing.hip) ----
+// flags[t] = 1 when slot t is in the r-torsion subgroup (what k_kzg_in_g1 counts per call, kept per point): a tuple
+// whose commitment or proof is outside G1 goes to the host loop, because the GLV multiplication and the rearrangement
+// e(lhs + [x^n] proof, G2) == e(proof, [s^n]G2) only hold in G1
+__global__ void __launch_bounds__(64) k_kzg_in_g1_each(const AffPt* __restrict__ pts, size_t total, uint8_t* __restrict__ flags) {
+    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= total) return;
+    flags[t] = g1io::affpt_in_g1(pts[t]) ? 1 : 0;
+}
+// out = a + b: a blst Jacobian, b g1::Xyzz (the products [x^n] proof), out blst Jacobian
+__global__ void __launch_bounds__(64) k_kzg_g1_add_xyzz(ff::Fp* __restrict__ out, const ff::Fp* __restrict__ a, const Xyzz* __restrict__ b,
+                                                        size_t count) {
+    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= count) return;
+    const ff::Fp* src = a + 3 * t;
+    Xyzz A;
+    if (src[2].is_zero()) {
+        g1::set_inf(A);
+    } else {
+        const fp28::Fe z = fp28::from_blst(src[2]);
+        A.x = fp28::from_blst(src[0]);
+        A.y = fp28::from_blst(src[1]);
+        A.zz = fp28::sqr(z);
+        A.zzz = fp28::mul(A.zz, z);
+    }
+    g1::dadd(A, b[t]);
+    g1::to_blst_jacobian(out + 3 * t, A);
+}
+
 // ---- check_batch ----
 constexpr int PT_CHUNK = 8;        // points per lane of k_kzg_points: one inversion per PT_CHUNK points
 constexpr int AGG_WAVE = 64;       // tuples per block of k_kzg_batch_agg: one wave
@@ -320,6 +351,10 @@ __global__ void __launch_bounds__(256) k_kzg_batch_fold(Fr* __restrict__ agg, co
     agg[i] = s;
 }
 
+// Built-in pairing_gpu_min (tuning key of kzgamd_kzg_new; -1 selects this): the smallest count at which the GPU form of check_each beat the
+// host loop in tools/time_pairing_batch.py (profiles/pairing_batch_time.jsonl, NOTES 33)
+constexpr size_t PAIRING_GPU_MIN_DEFAULT = 4;
+
 struct KzErr {
     hipError_t e;
 };
@@ -364,12 +399,20 @@ struct KzgCtx {
     kzgamd::Options opt;
     kzgamd::MsmContext* vmsm = nullptr;
     std::map<size_t, std::shared_ptr<const kzgamd::pairing::LineTable>> lines;
+    // check on the GPU: the count from which check_each takes it (0 = never), the device line tables of G2 and of
+    // [s^n]G2 per n, kept for the life of the handle
+    size_t pairing_gpu_min = 0;
+    kzgamd::pairing_gpu::DeviceTable dgen;
+    bool have_dgen = false;
+    std::map<size_t, kzgamd::pairing_gpu::DeviceTable> dlines;
     // workspace, grown as calls need it
     DevBuf polys, xs, pw, q, r, r2, sums, local, out, pts;
     DevBuf aff, pref, stat, xinv, rho, rows, part, agg;
+    DevBuf gjac, gflags, gsplit, gxyzz, gprod, gtab, gsum, gok;
 
     ~KzgCtx() {
-        for (DevBuf* b : {&polys, &xs, &pw, &q, &r, &r2, &sums, &local, &out, &pts, &aff, &pref, &stat, &xinv, &rho, &rows, &part, &agg})
+        for (DevBuf* b : {&polys, &xs, &pw, &q, &r, &r2, &sums, &local, &out, &pts, &aff, &pref, &stat, &xinv, &rho, &rows, &part, &agg,
+                           &gjac, &gflags, &gsplit, &gxyzz, &gprod, &gtab, &gsum, &gok})
             b->drop();
         if (vmsm) kzgamd::msm_destroy(vmsm);
         if (msm) kzgamd::msm_destroy(msm);
@@ -449,6 +492,31 @@ void enqueue_quotients(KzgCtx* kz, size_t len, size_t n, size_t nx, size_t pair0
     KZ_TRY(hipGetLastError());
 }
 
+// "pairing_gpu_min=<v>" out of a "key=value;key=value" tuning string (separators as config.h takes them): *value is set
+// when the key is there, *rest is the string without it; false when its value is not a number in -1 ... 2^20
+bool take_pairing_gpu_min(const char* str, long* value, std::string* rest) {
+    static const char key[] = "pairing_gpu_min";
+    auto is_sep = [](char c) { return c == ';' || c == ',' || c == ' ' || c == '\t' || c == '\n'; };
+    const char* p = str;
+    while (*p) {
+        while (*p && is_sep(*p)) ++p;
+        const char* e = p;
+        while (*e && !is_sep(*e)) ++e;
+        if (e == p) break;
+        if ((size_t)(e - p) > sizeof key - 1 && !strncmp(p, key, sizeof key - 1) && p[sizeof key - 1] == '=') {
+            char* end = nullptr;
+            const long v = strtol(p + sizeof key, &end, 10);
+            if (end != e || end == p + sizeof key || v < -1 || v > (1 << 20)) return false;
+            *value = v;
+        } else {
+            if (!rest->empty()) *rest += ';';
+            rest->append(p, e);
+        }
+        p = e;
+    }
+    return true;
+}
+
 bool g1_affine(const blst_p1* p, ff::Fp& x, ff::Fp& y) {  // returns "is the identity"
     const ff::Fp* P = reinterpret_cast<const ff::Fp*>(p);
     if (P[2].is_zero()) return true;
@@ -474,8 +542,22 @@ extern "C" void* kzgamd_kzg_new(void* vntt, const blst_p1* g1_monomial, size_t n
         *err = -1;
         return nullptr;
     }
+    // pairing_gpu_min is a key of this handle type alone (as fk20_table is of kzgamd_fk20_new): it is taken out of
+    // cfg->tuning here, the rest goes to the library's table of keys (config.h) as for every other handle
+    long gpu_min = -1;
+    KzgAmdConfig local;
+    std::string rest, msg;
+    if (cfg && cfg->struct_size >= offsetof(KzgAmdConfig, tuning) + sizeof(cfg->tuning) && cfg->tuning) {
+        if (!take_pairing_gpu_min(cfg->tuning, &gpu_min, &rest)) {
+            fprintf(stderr, "kzg_mi355x: kzgamd_kzg_new: tuning: 'pairing_gpu_min' takes -1 ... 1048576\n");
+            *err = -2;
+            return nullptr;
+        }
+        local = *cfg;
+        local.tuning = rest.c_str();
+        cfg = &local;
+    }
     kzgamd::Options opt;
-    std::string msg;
     if (!kzgamd::Options::resolve(opt, cfg, &msg)) {
         fprintf(stderr, "kzg_mi355x: kzgamd_kzg_new: %s\n", msg.c_str());
         *err = -2;
@@ -489,6 +571,7 @@ extern "C" void* kzgamd_kzg_new(void* vntt, const blst_p1* g1_monomial, size_t n
         kz->ntt = ntt;
         kz->device = ntt->device;
         kz->opt = opt;
+        kz->pairing_gpu_min = gpu_min < 0 ? PAIRING_GPU_MIN_DEFAULT : (size_t)gpu_min;
         kz->num_g1 = num_g1;
         kz->num_g2 = g2_monomial ? num_g2 : 0;
         kz->g2.resize(kz->num_g2);
@@ -641,6 +724,98 @@ extern "C" int kzgamd_kzg_open(void* vkz, blst_p1* proofs, blst_fr* ys, const bl
 
 namespace {
 
+// The pairings of check_each on the GPU, for the tuples whose commitment and proof are in G1 (the handle's lock held, the
+// stream holding lhs = commitment - [interp(s)]G in `dif`):   e(lhs + [x^n] proof, G2) == e(proof, [s^n]G2),
+// the per-tuple G2 term moved to the G1 side as check_batch does.  [x^n] proof by the GLV lanes of g1_varmul_sum_device
+// (group = 1), the sums by k_kzg_g1_add_xyzz, the verdicts by one wave per tuple (pairing_internal.h) against the device
+// tables of G2 and g2[n].  to_host[t] = 1: the tuple stays with the host loop (a point outside G1, or the identity).
+// false: a point off the curve somewhere in the call — every tuple stays with the host loop.  Synchronises the stream.
+bool check_each_gpu(KzgCtx* kz, std::vector<uint8_t>& verdict, std::vector<uint8_t>& to_host, const ff::Fp* dif, const blst_p1* proofs,
+                    const blst_p1* commitments, const Fr* hx, size_t n, size_t count) {
+    namespace pg = kzgamd::pairing_gpu;
+    const size_t np = 2 * count;
+    hipStream_t st = kz->st;
+    kz->gjac.ensure(np * sizeof(blst_p1));
+    kz->aff.ensure(np * sizeof(AffPt));
+    kz->pref.ensure(np * sizeof(fp28::Fe));
+    kz->stat.ensure(2 * sizeof(int));
+    kz->gflags.ensure(np);
+    kz->gsplit.ensure(count * sizeof(kzgamd::RootSplit));
+    kz->gxyzz.ensure(count * sizeof(Xyzz));
+    kz->gprod.ensure(count * sizeof(Xyzz));
+    kz->gtab.ensure(18 * count * sizeof(Xyzz));
+    kz->gsum.ensure(count * sizeof(blst_p1));
+    kz->gok.ensure(count);
+    ff::Fp* jac = kz->gjac.as<ff::Fp>();  // [proofs | commitments]
+    int* stat = kz->stat.as<int>();
+    KZ_TRY(hipMemcpyAsync(jac, proofs, count * sizeof(blst_p1), hipMemcpyHostToDevice, st));
+    KZ_TRY(hipMemcpyAsync(jac + 3 * count, commitments, count * sizeof(blst_p1), hipMemcpyHostToDevice, st));
+    KZ_TRY(hipMemsetAsync(stat, 0, 2 * sizeof(int), st));
+    hipLaunchKernelGGL(k_kzg_points, dim3(blocks(blocks(np, PT_CHUNK), 64)), dim3(64), 0, st, kz->aff.as<AffPt>(), (const ff::Fp*)jac,
+                       kz->pref.as<fp28::Fe>(), np, stat);
+    hipLaunchKernelGGL(k_kzg_in_g1_each, dim3(blocks(np, 64)), dim3(64), 0, st, (const AffPt*)kz->aff.as<AffPt>(), np,
+                       kz->gflags.as<uint8_t>());
+    KZ_TRY(hipGetLastError());
+    int hstat[2] = {1, 1};
+    std::vector<uint8_t> flags(np);
+    KZ_TRY(hipMemcpyAsync(hstat, stat, 2 * sizeof(int), hipMemcpyDeviceToHost, st));
+    KZ_TRY(hipMemcpyAsync(flags.data(), kz->gflags.p, np, hipMemcpyDeviceToHost, st));
+    KZ_TRY(hipStreamSynchronize(st));
+    if (hstat[0]) return false;
+    to_host.assign(count, 0);
+    std::vector<kzgamd::RootSplit> split(count);
+    size_t taken = 0;
+    for (size_t t = 0; t < count; ++t) {
+        const ff::Fp* P = reinterpret_cast<const ff::Fp*>(&proofs[t]);
+        const ff::Fp* Cm = reinterpret_cast<const ff::Fp*>(&commitments[t]);
+        kzgamd::RootSplit rs;
+        memset(&rs, 0, sizeof rs);
+        if (!flags[t] || !flags[count + t] || P[2].is_zero() || Cm[2].is_zero()) {
+            to_host[t] = 1;  // its scalar stays zero: the lane gives the identity
+        } else {
+            Fr xn = hx[t];
+            for (size_t m = 1; m < n; m <<= 1) xn = ff::mul(xn, xn);
+            xn = ff::from_mont(xn);
+            u32 k1[8], k2[8];
+            kzgamd::glv_split(xn.v, k1, k2, rs.neg[0], rs.neg[1]);
+            for (int i = 0; i < 4; ++i) {
+                rs.k[0][i] = k1[i];
+                rs.k[1][i] = k2[i];
+            }
+            ++taken;
+        }
+        split[t] = rs;
+    }
+    verdict.assign(count, 0);
+    if (taken == 0) return true;
+    if (!kz->have_dgen) {
+        const kzgamd::pairing::G2Jac gen = kzgamd::pairing::g2_generator();
+        blst_p2 g;
+        memcpy(&g, &gen, sizeof g);
+        KZ_TRY(pg::device_table(&kz->dgen, &g));
+        kz->have_dgen = true;
+    }
+    auto it = kz->dlines.find(n);
+    if (it == kz->dlines.end()) {
+        blst_p2 q;
+        memcpy(&q, &kz->g2[n], sizeof q);
+        pg::DeviceTable tab;
+        KZ_TRY(pg::device_table(&tab, &q));
+        it = kz->dlines.emplace(n, tab).first;
+    }
+    KZ_TRY(hipMemcpyAsync(kz->gsplit.p, split.data(), count * sizeof(kzgamd::RootSplit), hipMemcpyHostToDevice, st));
+    kzgamd::g1_jacobian_to_xyzz(kz->gxyzz.p, jac, count, st);
+    kzgamd::g1_varmul_sum_device(kz->ntt, kz->gprod.p, nullptr, kz->gtab.p, kz->gxyzz.p, count, (const kzgamd::RootSplit*)kz->gsplit.p, count, 1,
+                                 st);
+    hipLaunchKernelGGL(k_kzg_g1_add_xyzz, dim3(blocks(count, 64)), dim3(64), 0, st, kz->gsum.as<ff::Fp>(), dif, (const Xyzz*)kz->gprod.p,
+                       count);
+    KZ_TRY(hipGetLastError());
+    KZ_TRY(pg::check_on_stream(kz->gok.as<uint8_t>(), (const blst_p1*)kz->gsum.p, (const blst_p1*)jac, kz->dgen, it->second, count, st));
+    KZ_TRY(hipMemcpyAsync(verdict.data(), kz->gok.p, count, hipMemcpyDeviceToHost, st));
+    KZ_TRY(hipStreamSynchronize(st));
+    return true;
+}
+
 // kzgamd_kzg_check: one pairing per tuple (also what check_batch fills ok_each with when a batch fails)
 int check_each(KzgCtx* kz, bool* ok, const blst_p1* commitments, const blst_p1* proofs, const blst_fr* xs, const blst_fr* ys, size_t n,
                size_t count) {
@@ -657,6 +832,9 @@ int check_each(KzgCtx* kz, bool* ok, const blst_p1* commitments, const blst_p1* 
         for (size_t i = 0; i < count; ++i)
             if (hx[i].is_zero()) return 5;
     std::vector<blst_p1> lhs(count);
+    // the GPU form: verdict bytes of the tuples it took, and which tuples stay with the host loop
+    bool gpu = kz->pairing_gpu_min != 0 && count >= kz->pairing_gpu_min;
+    std::vector<uint8_t> gverdict, to_host;
     int rc = 0;
     {
         std::lock_guard<std::mutex> lk(kz->mu);
@@ -689,6 +867,7 @@ int check_each(KzgCtx* kz, bool* ok, const blst_p1* commitments, const blst_p1* 
                                    (const ff::Fp*)kz->out.p, count);
                 KZ_TRY(hipGetLastError());
                 KZ_TRY(hipMemcpyAsync(lhs.data(), dif, count * sizeof(blst_p1), hipMemcpyDeviceToHost, st));
+                if (gpu) gpu = check_each_gpu(kz, gverdict, to_host, (const ff::Fp*)dif, proofs, commitments, hx, n, count);
             } catch (...) {
                 (void)hipStreamSynchronize(st);
                 throw;
@@ -705,6 +884,10 @@ int check_each(KzgCtx* kz, bool* ok, const blst_p1* commitments, const blst_p1* 
     const pr::G2Jac gen = pr::g2_generator();
     const std::shared_ptr<const pr::LineTable> tgen = pr::prepared_lines(gen);
     for (size_t i = 0; i < count; ++i) {
+        if (gpu && !to_host[i]) {
+            ok[i] = gverdict[i] != 0;
+            continue;
+        }
         Fr xn = hx[i];
         for (size_t m = 1; m < n; m <<= 1) xn = ff::mul(xn, xn);
         xn = ff::from_mont(xn);

@@ -848,6 +848,10 @@ pub mod ckzg {
                                                           proofs_bytes: *const Bytes48, num_cells: *const u64, nbatch: usize,
                                                           rho: *const blst::blst_fr, s: &CKZGSettings) -> CKzgRet;
         pub fn kzgamd_vcells_info(slice_cells: *mut usize) -> core::ffi::c_int;
+        // batched pairing checks on the GPU, one wave per check: ok[i] = e(a1[i], *a2) == e(b1[i], *b2)
+        pub fn kzgamd_pairings_verify_batch(ok: *mut bool, a1: *const blst::blst_p1, a2: *const blst::blst_p2,
+                                            b1: *const blst::blst_p1, b2: *const blst::blst_p2, count: usize) -> core::ffi::c_int;
+        pub fn kzgamd_pairing_info(slice_checks: *mut usize) -> core::ffi::c_int;
         // batched and multi-GPU forms (new API, include/kzg_mi355x.h): contiguous slabs of the batch per settings object
         pub fn kzgamd_blob_to_kzg_commitment_batch(out: *mut KZGCommitment, blobs: *const Blob, n: usize, s: &CKZGSettings) -> CKzgRet;
         pub fn kzgamd_compute_blob_kzg_proof_batch(out: *mut KZGProof, blobs: *const Blob, commitments: *const Bytes48, n: usize,
