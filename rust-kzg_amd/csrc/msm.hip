@@ -32,6 +32,7 @@
 #include "g1_io.hip.h"
 #include "g1w.hip.h"
 #include "g1grp.hip.h"
+#include "g1_30s.hip.h"
 #include "glv.hip.h"
 #include "host_g1.h"
 #include "config.h"
@@ -1671,6 +1672,8 @@ template <int SPL, bool GLV>
 __global__ void __launch_bounds__(256) k_fbw_accum(DigitParams P, const u32* __restrict__ scalars,
                                                    const WidePt* __restrict__ wide, Xyzz* __restrict__ partial,
                                                    size_t lanes_per_msm) {
+    // (first of all: fp30s.hip.h says why the seeds of the column sums are made before anything they are added to)
+    const fp30s::Seeds sd = fp30s::seeds();
     size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= lanes_per_msm * P.nbatch) return;
     const size_t b = t / lanes_per_msm;
@@ -1679,9 +1682,11 @@ __global__ void __launch_bounds__(256) k_fbw_accum(DigitParams P, const u32* __r
     // the selectors k_fbw_digits wrote, DW words per (scalar, half)
     const u32 part = GLV ? (u32)(l & 1) : 0u;
     if (GLV) l >>= 1;
-    Xyzz acc;
-    g1::set_inf(acc);
-    u32 st = g1::CHAIN_EMPTY;  // what acc holds (g1::chain_add): nothing, one table point, a sum
+    // the chain runs over fp30s (g1_30s.hip.h: 13 signed limbs, on the isomorphic curve the table's integers are a
+    // point of in that radix); its one partial sum goes back to the fp28 form below
+    g1s::Xyzz acc;
+    g1s::set_inf(acc);
+    u32 st = g1::CHAIN_EMPTY;  // what acc holds (g1s::chain_add): nothing, one table point, a sum
     const u32 half = 1u << (P.c - 1);
     const int sh = P.c - 1;
     const size_t seg0 = P.nseg ? (b % P.nseg) * P.n : 0;  // first table base of this MSM
@@ -1703,7 +1708,7 @@ __global__ void __launch_bounds__(256) k_fbw_accum(DigitParams P, const u32* __r
                     if (e == FBW_SKIP) continue;
                     const WidePt pk = wide[(((size_t)(w4 + q) * P.row_stride + seg0 + i) << sh) + (e & 0x7fffffffu)];
                     if (pk.pad[0]) continue;  // multiple of a base at infinity
-                    g1::chain_add(acc, st, pk.x, pk.y, 0u - (e >> 31));
+                    g1s::chain_add(acc, st, pk.x, pk.y, 0u - (e >> 31), sd);
                 }
             }
         } else {
@@ -1722,15 +1727,17 @@ __global__ void __launch_bounds__(256) k_fbw_accum(DigitParams P, const u32* __r
                 if (d == 0) continue;
                 const WidePt pk = wide[(((size_t)w * P.row_stride + seg0 + i) << sh) + (d - 1)];
                 if (pk.pad[0]) continue;  // multiple of a base at infinity
-                g1::chain_add(acc, st, pk.x, pk.y, 0u - neg);
+                g1s::chain_add(acc, st, pk.x, pk.y, 0u - neg, sd);
             }
         }
     }
+    Xyzz sum;
+    g1s::to_xyzz28(sum, acc, st, sd);
     if (GLV && part && st != g1::CHAIN_EMPTY) {
-        acc.x = fp28::mul(acc.x, beta28());                     // psi(X, Y, ZZ, ZZZ) = (beta X, -Y, ZZ, ZZZ)
-        acc.y = fp28::mul(fp28::neg<8>(acc.y), fp28::one());    // -Y, back under the 2p bound
+        sum.x = fp28::mul(sum.x, beta28());                     // psi(X, Y, ZZ, ZZZ) = (beta X, -Y, ZZ, ZZZ)
+        sum.y = fp28::mul(fp28::neg<8>(sum.y), fp28::one());    // -Y, back under the 2p bound
     }
-    partial[t] = acc;
+    partial[t] = sum;
 }
 
 // k_fbw_accum<1, true> with FOUR lanes per (scalar, half) chain (g1grp.hip.h): the eight mixed additions of a chain are

@@ -21,8 +21,8 @@ LLVM = "/opt/rocm/lib/llvm/bin"
 CLASSES = [
     ("mad64", re.compile(r"^v_mad_(u64_u32|i64_i32)$"), "v_mad_u64_u32 (1 chain)"),
     ("mul32", re.compile(r"^v_mul_(lo|hi)_u32$"), "v_mul_lo_u32"),
-    ("wide_or_three_operand", re.compile(r"^v_(lshrrev_b64|lshlrev_b64|lshl_add_u64|add3_u32|alignbit_b32|and_or_b32|lshl_or_b32|"
-                                         r"lshl_add_u32|add_lshl_u32|bfe_u32|bfi_b32|mad_u32_u24|xad_u32|or3_b32|perm_b32|"
+    ("wide_or_three_operand", re.compile(r"^v_(lshrrev_b64|lshlrev_b64|ashrrev_i64|lshl_add_u64|add3_u32|alignbit_b32|and_or_b32|lshl_or_b32|"
+                                         r"lshl_add_u32|add_lshl_u32|bfe_u32|bfe_i32|bfi_b32|mad_u32_u24|xad_u32|or3_b32|perm_b32|"
                                          r"cndmask_b32|addc_co_u32|subb_co_u32|add_co_u32|sub_co_u32|sad_u32|mov_b64).*$"), "v_add3_u32"),
     ("two_operand_32", re.compile(r"^v_.*$"), "v_add_u32"),
 ]
