@@ -522,6 +522,40 @@ void kzgamd_p2_generator(blst_p2 *out);
 void kzgamd_p2_mult(blst_p2 *out, const blst_p2 *in, const blst_fr *scalar);
 void kzgamd_p2_add(blst_p2 *out, const blst_p2 *a, const blst_p2 *b);
 
+/* Fixed-base batched scalar multiplication ON THE GPU, in G1 and in G2 (G1Mul::mul / G2Mul::mul of the reference,
+ * kzg/src/lib.rs:138-140, 413-415, for many scalars and one base), and the trusted setups made of it.  Handle-less: the
+ * calls run on the calling thread's current device (cfg->device, when cfg is given and names one), take host buffers
+ * and are thread-safe.  Outputs are Jacobian with canonical coordinates; infinity is Z == 0 (all-zero), as everywhere.
+ *
+ * out[i] = scalars[i] * (*base), i < n; base == NULL: the generator.  Scalars are Montgomery blst_fr (as G1Mul/G2Mul take
+ * them).  The base is a Jacobian point of the prime-order subgroup with any Z (Z == 0: every output is infinity).  The G1
+ * base is tested (blst_p1_in_g1); a G2 base is the caller's responsibility, like every blst_p2 this library accepts: for
+ * one outside the subgroup the outputs are still the multiples k_i * base of the curve's group law.
+ * n == 0: success, nothing written, the pointers are not looked at.
+ *
+ * kzgamd_generate_trusted_setup is generate_trusted_setup of the reference (blst/src/utils.rs:16-37):
+ * s = hash_to_bls_field(secret) (the 32 bytes as a big-endian integer mod r), g1_monomial[i] = [s^i]G1 (i < num_g1),
+ * g2_monomial[j] = [s^j]G2 (j < num_g2), g1_lagrange = fft_g1(g1_monomial, inverse) in natural order, computed on the
+ * device from the device-resident points through the NTT handle `ntt` (kzgamd_ntt_new; only the Lagrange form needs it,
+ * and the call then runs on the handle's device).  The powers of s are computed on the device.  Any of the three outputs
+ * may be NULL (not computed).  Both counts 0: success, nothing written.
+ *
+ * Return codes:  0 ok;  1 g1_lagrange wanted, but num_g1 is not a power of two or ntt is NULL;  2 num_g1 exceeds the NTT
+ * handle's max width;  3 the G1 base is not in the subgroup;  -1 a needed pointer is NULL;  -2 or -(100 + hipError_t)
+ * device errors (-2 also for a malformed cfg).
+ * cfg may be NULL.  Its tuning string takes ONE key, of these calls alone and not listed by kzgamd_tuning_keys:
+ * mul_slice=<outputs per slice of workspace: a power of two, at least 64>; any other key fails the call.
+ * Memory the library keeps: the window tables of the two generators (1.5 MB of device memory together) are built at the
+ * first call that needs them on a device and stay until the process ends; there is no call that frees them, and they
+ * do not survive a hipDeviceReset by the application (do not reset a device these calls have run on).  Everything
+ * else a call allocates is freed before it returns.
+ * kzgamd_group_mul_info: the default slice and the window widths of the two tables (any pointer may be NULL; returns 0). */
+int kzgamd_g1_mul_batch(blst_p1 *out, const blst_p1 *base, const blst_fr *scalars, size_t n, const KzgAmdConfig *cfg);
+int kzgamd_g2_mul_batch(blst_p2 *out, const blst_p2 *base, const blst_fr *scalars, size_t n, const KzgAmdConfig *cfg);
+int kzgamd_generate_trusted_setup(void *ntt, blst_p1 *g1_monomial, blst_p1 *g1_lagrange, blst_p2 *g2_monomial,
+                                  size_t num_g1, size_t num_g2, const uint8_t secret[32], const KzgAmdConfig *cfg);
+int kzgamd_group_mul_info(size_t *slice_points, int *g1_window_bits, int *g2_window_bits);
+
 typedef struct { uint8_t bytes[2048]; } Cell;
 C_KZG_RET compute_cells_and_kzg_proofs(Cell *cells, KZGProof *proofs, const Blob *blob, const CKZGSettings *s);
 C_KZG_RET kzgamd_compute_cells_and_kzg_proofs_batch(Cell *cells, KZGProof *proofs, const Blob *blobs, size_t n,

@@ -87,6 +87,7 @@ EXPORTS = [
     "kzgamd_pairings_verify_batch", "kzgamd_pairing_info",
     "kzgamd_compute_blob_kzg_proof_device",
     "kzgamd_p2_uncompress", "kzgamd_p2_compress", "kzgamd_p2_generator", "kzgamd_p2_mult", "kzgamd_p2_add",
+    "kzgamd_g1_mul_batch", "kzgamd_g2_mul_batch", "kzgamd_generate_trusted_setup", "kzgamd_group_mul_info",
     "kzgamd_load_trusted_setup_file_multi", "kzgamd_free_trusted_setup_multi", "kzgamd_blob_to_kzg_commitment_batch_multi",
     "kzgamd_compute_blob_kzg_proof_batch_multi", "kzgamd_compute_cells_and_kzg_proofs_batch_multi",
     "kzgamd_verify_blob_kzg_proof_batch_multi", "kzgamd_mult_pippenger_prepared_multi", "kzgamd_shard_range",
@@ -367,6 +368,14 @@ def lib():
     L.kzgamd_p2_mult.argtypes = [vp, vp, vp]
     L.kzgamd_p2_add.restype = None
     L.kzgamd_p2_add.argtypes = [vp, vp, vp]
+    L.kzgamd_g1_mul_batch.restype = C.c_int
+    L.kzgamd_g1_mul_batch.argtypes = [vp, vp, vp, C.c_size_t, vp]
+    L.kzgamd_g2_mul_batch.restype = C.c_int
+    L.kzgamd_g2_mul_batch.argtypes = [vp, vp, vp, C.c_size_t, vp]
+    L.kzgamd_generate_trusted_setup.restype = C.c_int
+    L.kzgamd_generate_trusted_setup.argtypes = [vp, vp, vp, vp, C.c_size_t, C.c_size_t, vp, vp]
+    L.kzgamd_group_mul_info.restype = C.c_int
+    L.kzgamd_group_mul_info.argtypes = [vp, vp, vp]
     L.kzgamd_load_trusted_setup_file_multi.restype = C.c_int
     L.kzgamd_load_trusted_setup_file_multi.argtypes = [vp, vp, sz, vp]
     L.kzgamd_free_trusted_setup_multi.restype = None
@@ -1299,6 +1308,57 @@ def p2_add(a, b) -> BlstP2:
     out = BlstP2()
     lib().kzgamd_p2_add(C.byref(out), C.byref(a), C.byref(b))
     return out
+
+
+def _group_mul_check(rc, what):
+    if rc == 1:
+        raise KzgAmdError("%s: the Lagrange form needs an FFTSettings and a power-of-two number of G1 points" % what)
+    if rc == 2:
+        raise KzgAmdError("Supplied list is longer than the available max width")
+    if rc == 3:
+        raise KzgAmdError("%s: the base is not in the G1 subgroup" % what)
+    if rc != 0:
+        raise KzgAmdError("%s: %d" % (what, rc))
+
+
+def g1_mul_batch(scalars, n, base=None, config=None):
+    """out[i] = scalars[i] * base on the GPU (base None: the generator).  scalars: blst_fr[n] in Montgomery form (ctypes
+    array / buffer), base: a BlstP1 of the subgroup.  Returns a new (BlstP1 * n)."""
+    out = (BlstP1 * max(n, 1))()
+    rc = lib().kzgamd_g1_mul_batch(out, C.byref(base) if base is not None else None, _addr(scalars) if n else None, n, _cfgp(config))
+    _group_mul_check(rc, "kzgamd_g1_mul_batch")
+    return out
+
+
+def g2_mul_batch(scalars, n, base=None, config=None):
+    """the same in G2: base a BlstP2 of the subgroup (not tested), returns a new (BlstP2 * n)."""
+    out = (BlstP2 * max(n, 1))()
+    rc = lib().kzgamd_g2_mul_batch(out, C.byref(base) if base is not None else None, _addr(scalars) if n else None, n, _cfgp(config))
+    _group_mul_check(rc, "kzgamd_g2_mul_batch")
+    return out
+
+
+def generate_trusted_setup(num_g1, secret, num_g2=None, fft_settings=None, want_lagrange=True, config=None):
+    """generate_trusted_setup of the reference (blst/src/utils.rs:16-37) on the GPU: ([s^i]G1 as BlstP1 * num_g1, their
+    Lagrange form (or None), [s^j]G2 as BlstP2 * num_g2) for s = the 32 bytes `secret` as a big-endian integer mod r.
+    num_g2 None: num_g1, as the reference.  The Lagrange form takes an FFTSettings of at least num_g1 points."""
+    if len(secret) != 32:
+        raise KzgAmdError("generate_trusted_setup: the secret is 32 bytes")
+    num_g2 = num_g1 if num_g2 is None else num_g2
+    mono = (BlstP1 * max(num_g1, 1))()
+    lag = (BlstP1 * max(num_g1, 1))() if want_lagrange else None
+    g2 = (BlstP2 * max(num_g2, 1))()
+    rc = lib().kzgamd_generate_trusted_setup(fft_settings.handle if fft_settings is not None else None, mono, lag, g2, num_g1, num_g2,
+                                             bytes(secret), _cfgp(config))
+    _group_mul_check(rc, "kzgamd_generate_trusted_setup")
+    return mono, lag, g2
+
+
+def group_mul_info():
+    """{"slice_points", "g1_window_bits", "g2_window_bits"} of g1_mul_batch / g2_mul_batch / generate_trusted_setup"""
+    s, a, b = C.c_size_t(0), C.c_int(0), C.c_int(0)
+    lib().kzgamd_group_mul_info(C.byref(s), C.byref(a), C.byref(b))
+    return {"slice_points": s.value, "g1_window_bits": a.value, "g2_window_bits": b.value}
 
 
 def compute_challenge(blob: bytes, commitment_p1) -> BlstFr:

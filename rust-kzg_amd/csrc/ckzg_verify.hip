@@ -191,19 +191,8 @@ bool check_proof_single(const blst_p1& commitment, const blst_p1& proof, const f
                         KzgAmdSettings* dev) {
     using namespace kzgamd::pairing;
     kzgamd::HostJac g;
-    {
-        const uint64_t GX[6] = {0x5cb38790fd530c16ull, 0x7817fc679976fff5ull, 0x154f95c7143ba1c1ull,
-                                0xf0ae6acdf3d0e747ull, 0xedce6ecc21dbf440ull, 0x120177419e0bfb75ull};
-        const uint64_t GY[6] = {0xbaac93d50ce72271ull, 0x8c22631a7918fd8eull, 0xdd595f13570725ceull,
-                                0x51ac582950405194ull, 0x0e1c8c3fad0059c0ull, 0x0bbc3efc5008a26aull};
-        for (int k = 0; k < 6; ++k) {
-            g.x.v[2 * k] = (u32)GX[k];
-            g.x.v[2 * k + 1] = (u32)(GX[k] >> 32);
-            g.y.v[2 * k] = (u32)GY[k];
-            g.y.v[2 * k + 1] = (u32)(GY[k] >> 32);
-        }
-        g.z = ff::Fp::one();
-    }
+    kzgamd::host_g1_generator(g.x, g.y);
+    g.z = ff::Fp::one();
     g.y = hfp::neg(g.y);  // -G
     kzgamd::HostJac pi;
     memcpy(&pi, &proof, sizeof pi);

@@ -527,8 +527,8 @@ FF_HD Field<P> inverse_plain_fast(const Field<P>& y) {
                 g0 -= g1;
             }
             xa >>= 1;
-            f1 <<= 1;
-            g1 <<= 1;
+            f1 *= 2;  // (not <<= 1: they go negative, and shifting a negative value left is undefined before C++20)
+            g1 *= 2;
         }
         u32 nA[P::N], nB[P::N], nU[P::N], nV[P::N];
         if (lincomb_exact(nA, A, B, f0, g0)) {

@@ -11,6 +11,20 @@
 
 namespace kzgamd {
 
+// the G1 generator's affine coordinates in blst layout (Montgomery 2^384; blst/src/consts.rs:52-84)
+inline void host_g1_generator(ff::Fp& x, ff::Fp& y) {
+    static const uint64_t GX[6] = {0x5cb38790fd530c16ull, 0x7817fc679976fff5ull, 0x154f95c7143ba1c1ull,
+                                   0xf0ae6acdf3d0e747ull, 0xedce6ecc21dbf440ull, 0x120177419e0bfb75ull};
+    static const uint64_t GY[6] = {0xbaac93d50ce72271ull, 0x8c22631a7918fd8eull, 0xdd595f13570725ceull,
+                                   0x51ac582950405194ull, 0x0e1c8c3fad0059c0ull, 0x0bbc3efc5008a26aull};
+    for (int k = 0; k < 6; ++k) {
+        x.v[2 * k] = (uint32_t)GX[k];
+        x.v[2 * k + 1] = (uint32_t)(GX[k] >> 32);
+        y.v[2 * k] = (uint32_t)GY[k];
+        y.v[2 * k + 1] = (uint32_t)(GY[k] >> 32);
+    }
+}
+
 inline ff::Fp host_fp_from_be48(const uint8_t* in, bool* lt_p) {
     ff::Fp r;
     for (int i = 0; i < 12; ++i) {

@@ -7,7 +7,7 @@ use alloc::string::{String, ToString};
 use alloc::vec::Vec;
 
 use kzg::eip_4844::{load_trusted_setup_string, FIELD_ELEMENTS_PER_CELL};
-use kzg::{EcBackend, Fr, G1Mul, G2Mul, KZGSettings, G1, G2};
+use kzg::{EcBackend, KZGSettings, G1, G2};
 use rust_kzg_blst::types::fp::FsFp;
 use rust_kzg_blst::types::fr::FsFr;
 use rust_kzg_blst::types::g2::FsG2;
@@ -69,18 +69,17 @@ pub fn load_trusted_setup_filename_rust(filepath: &str) -> Result<MiKZGSettings,
     load_trusted_setup_rust(&g1_monomial, &g1_lagrange, &g2_monomial)
 }
 
-/// blst/src/utils.rs `generate_trusted_setup`: powers of a secret for the unit tests (insecure by construction).
+/// blst/src/utils.rs:16-37 `generate_trusted_setup`: powers of a secret for the unit tests and benches (insecure by
+/// construction), as one GPU call (`kzgamd_generate_trusted_setup`): `[s^i]G1`, their Lagrange form (the inverse
+/// `fft_g1`, natural order, as the reference returns it) and `[s^i]G2`.  `n` is a power of two, as in the reference
+/// (its `log2_pow2(n)` FFT settings); like the reference's `unwrap()`s, a failure panics.
 pub fn generate_trusted_setup(n: usize, secret: [u8; 32usize]) -> (Vec<MiG1>, Vec<MiG1>, Vec<FsG2>) {
-    let s = FsFr::hash_to_bls_field(&secret);
-    let mut s_pow = FsFr::one();
-    let mut s1 = Vec::with_capacity(n);
-    let mut s2 = Vec::with_capacity(n);
-    let mut s3 = Vec::with_capacity(n);
-    for _ in 0..n {
-        s1.push(MiG1::generator().mul(&s_pow));
-        s2.push(MiG1::generator()); // unused by the tests that take the monomial form
-        s3.push(FsG2::generator().mul(&s_pow));
-        s_pow = s_pow.mul(&s);
-    }
-    (s1, s2, s3)
+    assert!(n.is_power_of_two(), "generate_trusted_setup: n = {n} is not a power of two");
+    let ntt = rust_kzg_mi355x_sys::GpuNtt::new(n.trailing_zeros() as usize).expect("kzgamd_ntt_new");
+    let (mono, lagrange, g2) = ntt.generate_trusted_setup(n, &secret).expect("kzgamd_generate_trusted_setup");
+    (
+        mono.into_iter().map(MiG1::from_blst).collect(),
+        lagrange.into_iter().map(MiG1::from_blst).collect(),
+        g2.into_iter().map(FsG2).collect(),
+    )
 }

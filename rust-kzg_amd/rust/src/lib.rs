@@ -106,6 +106,48 @@ extern "C" {
                            nprob: usize, coeffs: c_int) -> c_int;
     fn kzgamd_poly_zero_info(ph: *mut c_void, leaf_roots: *mut usize, direct_max: *mut usize) -> c_int;
     fn kzgamd_poly_zero_plan(count: usize, levels: *mut usize) -> usize;
+
+    fn kzgamd_g1_mul_batch(out: *mut blst_p1, base: *const blst_p1, scalars: *const blst_fr, n: usize,
+                           cfg: *const KzgAmdConfig) -> c_int;
+    fn kzgamd_g2_mul_batch(out: *mut blst_p2, base: *const blst_p2, scalars: *const blst_fr, n: usize,
+                           cfg: *const KzgAmdConfig) -> c_int;
+    fn kzgamd_generate_trusted_setup(ntt: *mut c_void, g1_monomial: *mut blst_p1, g1_lagrange: *mut blst_p1,
+                                     g2_monomial: *mut blst_p2, num_g1: usize, num_g2: usize, secret: *const u8,
+                                     cfg: *const KzgAmdConfig) -> c_int;
+    fn kzgamd_group_mul_info(slice_points: *mut usize, g1_window_bits: *mut c_int, g2_window_bits: *mut c_int) -> c_int;
+}
+
+fn group_mul_result(rc: c_int, what: &str) -> Result<(), String> {
+    match rc {
+        0 => Ok(()),
+        1 => Err(format!("{what}: the Lagrange form needs an NTT handle and a power-of-two number of G1 points")),
+        2 => Err(String::from("Supplied list is longer than the available max width")),
+        3 => Err(format!("{what}: the base is not in the G1 subgroup")),
+        e => Err(format!("{what}: {e}")),
+    }
+}
+
+/// `out[i] = scalars[i] * base` on the GPU (`base` None: the generator); scalars in Montgomery form, as `G1Mul::mul`.
+pub fn g1_mul_batch(base: Option<&blst_p1>, scalars: &[blst_fr]) -> Result<Vec<blst_p1>, String> {
+    let mut out = vec![blst_p1::default(); scalars.len()];
+    let b = base.map_or(core::ptr::null(), |p| p as *const blst_p1);
+    let rc = unsafe { kzgamd_g1_mul_batch(out.as_mut_ptr(), b, scalars.as_ptr(), scalars.len(), core::ptr::null()) };
+    group_mul_result(rc, "kzgamd_g1_mul_batch").map(|_| out)
+}
+
+/// The same in G2 (`G2Mul::mul`); the base is not tested for the subgroup.
+pub fn g2_mul_batch(base: Option<&blst_p2>, scalars: &[blst_fr]) -> Result<Vec<blst_p2>, String> {
+    let mut out = vec![blst_p2::default(); scalars.len()];
+    let b = base.map_or(core::ptr::null(), |p| p as *const blst_p2);
+    let rc = unsafe { kzgamd_g2_mul_batch(out.as_mut_ptr(), b, scalars.as_ptr(), scalars.len(), core::ptr::null()) };
+    group_mul_result(rc, "kzgamd_g2_mul_batch").map(|_| out)
+}
+
+/// (outputs per slice of workspace, window bits of the G1 table, of the G2 table)
+pub fn group_mul_info() -> (usize, i32, i32) {
+    let (mut s, mut a, mut b) = (0usize, 0 as c_int, 0 as c_int);
+    unsafe { kzgamd_group_mul_info(&mut s, &mut a, &mut b) };
+    (s, a as i32, b as i32)
 }
 
 fn check(err: RustError, what: &str) -> Result<(), String> {
@@ -325,6 +367,21 @@ impl GpuNtt {
             2 => Err(String::from("A list with power-of-two length expected")),
             e => Err(format!("GPU fft_g1 failed: {e}")),
         }
+    }
+
+    /// `generate_trusted_setup(n, secret)` of the reference (blst/src/utils.rs:16-37) on the GPU: `[s^i]G1`, their
+    /// Lagrange form (the inverse `fft_g1`, natural order) and `[s^i]G2`, `n` of each; `n` a power of two within
+    /// this handle's width.
+    #[allow(clippy::type_complexity)]
+    pub fn generate_trusted_setup(&self, n: usize, secret: &[u8; 32]) -> Result<(Vec<blst_p1>, Vec<blst_p1>, Vec<blst_p2>), String> {
+        let mut mono = vec![blst_p1::default(); n];
+        let mut lagrange = vec![blst_p1::default(); n];
+        let mut g2 = vec![blst_p2::default(); n];
+        let rc = unsafe {
+            kzgamd_generate_trusted_setup(self.ctx, mono.as_mut_ptr(), lagrange.as_mut_ptr(), g2.as_mut_ptr(), n, n, secret.as_ptr(),
+                                          core::ptr::null())
+        };
+        group_mul_result(rc, "kzgamd_generate_trusted_setup").map(|_| (mono, lagrange, g2))
     }
 
     /// `DASExtension::das_fft_extension`.
