@@ -315,7 +315,8 @@ int kzgamd_kzg_batch_challenge(blst_fr *r_out, const blst_p1 *commitments, const
  * highest coefficient is non-zero — so results equal the reference's element for element, whichever route runs.
  *
  * kzgamd_poly_new keeps `ntt` by pointer and uses it in every call: free the poly handle FIRST, the NTT handle after
- * it.  *err (may be NULL): 0 ok, -1 NULL argument, -2 malformed configuration, or a device error.  kzgamd_poly_free
+ * it.  *err (may be NULL): 0 ok, -1 NULL argument, -2 malformed configuration, -(100 + hipError_t) a device error, -4 any
+ * other failure (out of host memory).  kzgamd_poly_free
  * gives every byte of HBM back.  kzgamd_poly_info: the max width of `ntt`, the coefficients a lane of eval takes, the
  * multiplications per lane up to which form 0 of mul takes the direct product, the coefficients of an inverse that
  * come from the one-launch recurrence before Newton steps begin; any pointer may be NULL. */

@@ -867,14 +867,10 @@ KzgAmdSettings* make_lane(KzgAmdSettings* parent) {
     ln->msm = parent->msm;
     // the MSM workspace of this lane's stream, sized now for every batch size a lane runs: no call on a lane allocates
     for (size_t nb = KzgAmdSettings::LANE_MAX_BLOBS; nb >= 1; --nb) {
-        kzgamd::msm_lock(parent->msm);
-        try {
+        {
+            kzgamd::MsmLock locked(parent->msm);
             kzgamd::msm_enqueue(parent->msm, nullptr, nullptr, N, nb, 0, ln->stream, kzgamd::OUT_COMPRESSED, true);
-        } catch (...) {
-            kzgamd::msm_unlock(parent->msm);
-            throw;
         }
-        kzgamd::msm_unlock(parent->msm);
     }
     ln->d_brp_roots = parent->d_brp_roots;
     ln->brp_roots = parent->brp_roots;
@@ -1112,14 +1108,10 @@ void commit_enqueue(KzgAmdSettings* dev, void* d_out, int* d_status, const void*
     else
         hipLaunchKernelGGL(k_blob_to_scalars, dim3((unsigned)((n * N + 255) / 256)), dim3(256), 0, stream, d_scalars, d_status,
                            (const u32*)d_blobs, n);
-    kzgamd::msm_lock(dev->msm);
-    try {
+    {
+        kzgamd::MsmLock locked(dev->msm);
         kzgamd::msm_enqueue(dev->msm, d_out, d_scalars, N, n, 0, stream, out_mode);
-    } catch (...) {
-        kzgamd::msm_unlock(dev->msm);
-        throw;
     }
-    kzgamd::msm_unlock(dev->msm);
 }
 
 
@@ -1156,15 +1148,11 @@ void prove_enqueue(KzgAmdSettings* dev, size_t off, size_t n, hipStream_t stream
                            (const ff::Fr*)dev->d_brp_roots, n_inverse());
     }
     if (evaluate_only) return;  // y = p(z) is all the caller wants (the field work of batched verification)
-    kzgamd::msm_lock(dev->msm);
-    try {
+    {
+        kzgamd::MsmLock locked(dev->msm);
         kzgamd::msm_enqueue(dev->msm, dev->d_out + off * (out_mode == kzgamd::OUT_JACOBIAN ? 144 : 48), scal, N, n, 0, stream,
                             out_mode);
-    } catch (...) {
-        kzgamd::msm_unlock(dev->msm);
-        throw;
     }
-    kzgamd::msm_unlock(dev->msm);
 }
 
 // compute_challenge_rust (kzg/src/eip_4844.rs:920-945) on already-validated inputs: the canonical
@@ -1776,14 +1764,10 @@ extern "C" C_KZG_RET kzgamd_settings_reserve(const CKZGSettings* s, size_t n, vo
     return guarded([&] {
         kzgamd::DeviceGuard on_device(dev->device);
         CK_HIP(on_device.err);
-        kzgamd::msm_lock(dev->msm);
-        try {
+        {
+            kzgamd::MsmLock locked(dev->msm);
             kzgamd::msm_enqueue(dev->msm, nullptr, nullptr, N, n, 0, (hipStream_t)stream, kzgamd::OUT_COMPRESSED, true);
-        } catch (...) {
-            kzgamd::msm_unlock(dev->msm);
-            throw;
         }
-        kzgamd::msm_unlock(dev->msm);
     });
 }
 
@@ -1817,14 +1801,10 @@ extern "C" C_KZG_RET kzgamd_compute_blob_kzg_proof_device(void* d_proofs, void* 
                            (const unsigned char*)d_commitments, n);
         hipLaunchKernelGGL(k_quotient, dim3((unsigned)n), dim3(QT), 0, st, scal, y, stat, (const u32*)d_blobs, (const u32*)z,
                            (const ff::Fr*)dev->d_brp_roots, n_inverse());
-        kzgamd::msm_lock(dev->msm);
-        try {
+        {
+            kzgamd::MsmLock locked(dev->msm);
             kzgamd::msm_enqueue(dev->msm, d_proofs, scal, N, n, 0, st, kzgamd::OUT_COMPRESSED);
-        } catch (...) {
-            kzgamd::msm_unlock(dev->msm);
-            throw;
         }
-        kzgamd::msm_unlock(dev->msm);
         CK_HIP(hipGetLastError());
     });
 }

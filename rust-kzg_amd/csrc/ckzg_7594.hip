@@ -110,28 +110,8 @@ __global__ void __launch_bounds__(256) k_fk20_brp(g1::Xyzz* __restrict__ out, co
 void fk20_prepare(KzgAmdSettings* dev, const CKZGSettings* cs) {
     if (dev->msm_xext) return;
     const size_t K2 = 2 * CELLS_PER_BLOB, total = K2 * CELL_SIZE;
-    std::vector<ff::Fp> aff(2 * total);  // blst_p1_affine: x, y
-    std::vector<ff::Fp> pre(total);
-    // Montgomery's trick over the Z coordinates (the columns hold no point at infinity for a valid setup; a zero Z
-    // is skipped and its point written as (0, 0), blst's affine infinity)
-    ff::Fp run = ff::Fp::one();
-    for (size_t k = 0; k < total; ++k) {
-        const ff::Fp* P = reinterpret_cast<const ff::Fp*>(&cs->x_ext_fft_columns[k / CELL_SIZE][k % CELL_SIZE]);
-        pre[k] = run;
-        if (!P[2].is_zero()) run = hfp::mul(run, P[2]);
-    }
-    ff::Fp inv = ff::inverse_bgcd(run);
-    for (size_t k = total; k-- > 0;) {
-        const ff::Fp* P = reinterpret_cast<const ff::Fp*>(&cs->x_ext_fft_columns[k / CELL_SIZE][k % CELL_SIZE]);
-        if (P[2].is_zero()) {
-            aff[2 * k] = aff[2 * k + 1] = ff::Fp::zero();
-            continue;
-        }
-        const ff::Fp zi = hfp::mul(inv, pre[k]), zi2 = hfp::sqr(zi);
-        inv = hfp::mul(inv, P[2]);
-        aff[2 * k] = hfp::mul(P[0], zi2);
-        aff[2 * k + 1] = hfp::mul(P[1], hfp::mul(zi2, zi));
-    }
+    std::vector<ff::Fp> aff(2 * total);  // blst_p1_affine: x, y (the columns hold no point at infinity for a valid setup)
+    kzgamd::host_p1_to_affine_batch(aff.data(), total, [&](size_t k) { return &cs->x_ext_fft_columns[k / CELL_SIZE][k % CELL_SIZE]; });
     dev->msm_xext = kzgamd::msm_create(aff.data(), total, false, true, false, kzgamd::G1_TRUSTED, &dev->opt);
 }
 
@@ -150,14 +130,10 @@ void enqueue_cell_proofs(KzgAmdSettings* dev, size_t n, hipStream_t st, bool fk2
         hipLaunchKernelGGL(k_fk20_transpose, dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, st, dev->d_fk_a,
                            (const ff::Fr*)dev->d_fk_b, n, inv128);
         // h_ext_fft[blob][j] = sum_i coeffs[j][i] * x_ext_fft_columns[j][i]: 128 n MSMs of 64 points, column j of the table
-        kzgamd::msm_lock(dev->msm_xext);
-        try {
+        {
+            kzgamd::MsmLock locked(dev->msm_xext);
             kzgamd::msm_enqueue(dev->msm_xext, dev->d_fk_h, dev->d_fk_a, CELL_SIZE, n * 128, 1, st, kzgamd::OUT_XYZZ, false, 128);
-        } catch (...) {
-            kzgamd::msm_unlock(dev->msm_xext);
-            throw;
         }
-        kzgamd::msm_unlock(dev->msm_xext);
         // h = ifft_g1(h_ext_fft), upper half cleared, proofs = fft_g1(h), bit-reversed, compressed
         g1::Xyzz* h = (g1::Xyzz*)kzgamd::fftg1_device((NttCtx*)dev->ntt, dev->d_fk_h, dev->d_fk_h2, 128, n, 1, st, false);
         if (!h) throw CkErr{C_KZG_ERROR, "fft_g1"};
@@ -171,14 +147,10 @@ void enqueue_cell_proofs(KzgAmdSettings* dev, size_t n, hipStream_t st, bool fk2
     } else {
         hipLaunchKernelGGL(k_cell_quotients, dim3((unsigned)(n * 128)), dim3(64), 0, st, dev->d_q, (const ff::Fr*)dev->d_fr_b,
                            (const ff::Fr*)dev->d_roots8192, n);
-        kzgamd::msm_lock(dev->msm_monomial);
-        try {
+        {
+            kzgamd::MsmLock locked(dev->msm_monomial);
             kzgamd::msm_enqueue(dev->msm_monomial, dev->d_proofs, dev->d_q, N, n * 128, 0, st, kzgamd::OUT_COMPRESSED);
-        } catch (...) {
-            kzgamd::msm_unlock(dev->msm_monomial);
-            throw;
         }
-        kzgamd::msm_unlock(dev->msm_monomial);
     }
 }
 

@@ -111,6 +111,35 @@ inline bool tune_value_allowed(int id, long v) {
     }
 }
 
+// what separates the "key=value" tokens of a tuning string
+inline bool is_sep(char c) { return c == ';' || c == ',' || c == ' ' || c == '\t' || c == '\n'; }
+
+// A key that belongs to one entry point, not to the table above (pairing_gpu_min of kzgamd_kzg_new, fk20_table of
+// kzgamd_fk20_new, mul_slice of the group multiplications), taken out of a tuning string before Options::parse sees it:
+// a token "<key>=<integer>" sets *value (the last one wins), every other token is appended to *rest, joined with ';'.
+// false when the key's value is missing, is not wholly an integer or lies outside lo ... hi.
+inline bool take_key(const char* str, const char* key, long long lo, long long hi, long long* value, std::string* rest) {
+    const size_t klen = strlen(key);
+    const char* p = str;
+    while (*p) {
+        while (*p && is_sep(*p)) ++p;
+        const char* e = p;
+        while (*e && !is_sep(*e)) ++e;
+        if (e == p) break;
+        if ((size_t)(e - p) > klen && !strncmp(p, key, klen) && p[klen] == '=') {
+            char* end = nullptr;
+            const long long v = strtoll(p + klen + 1, &end, 10);
+            if (end != e || end == p + klen + 1 || v < lo || v > hi) return false;
+            *value = v;
+        } else {
+            if (!rest->empty()) *rest += ';';
+            rest->append(p, e);
+        }
+        p = e;
+    }
+    return true;
+}
+
 struct Options {
     int device = -1;               // -1: the calling thread's current device
     double table_budget_gb = -1;   // per fixed-base table; < 0: 160 GB, capped by what is free
@@ -126,10 +155,10 @@ struct Options {
         const TuneKey* k = tune_keys();
         const char* p = str;
         while (*p) {
-            while (*p == ';' || *p == ',' || *p == ' ' || *p == '\t' || *p == '\n') ++p;
+            while (is_sep(*p)) ++p;
             if (!*p) break;
             const char* e = p;
-            while (*e && *e != '=' && *e != ';' && *e != ',' && *e != ' ') ++e;
+            while (*e && *e != '=' && !is_sep(*e)) ++e;
             const std::string name(p, e);
             if (*e != '=') {
                 if (err) *err = "tuning: '" + name + "' has no value";

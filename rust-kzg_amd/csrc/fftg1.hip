@@ -624,23 +624,23 @@ void ensure_g1(NttCtx* ctx, size_t total, size_t tab_lanes) {
     if (!ctx->d_kroots) {
         std::vector<RootSplit> split(ctx->W + 1);
         for (size_t i = 0; i <= ctx->W; ++i) split[i] = split_scalar(ff::from_mont(ctx->roots[i]));
-        NTT_TRY(hipMalloc(&ctx->d_kroots, (ctx->W + 1) * sizeof(RootSplit)));
-        NTT_TRY(hipMemcpy(ctx->d_kroots, split.data(), (ctx->W + 1) * sizeof(RootSplit), hipMemcpyHostToDevice));
+        DEV_TRY(hipMalloc(&ctx->d_kroots, (ctx->W + 1) * sizeof(RootSplit)));
+        DEV_TRY(hipMemcpy(ctx->d_kroots, split.data(), (ctx->W + 1) * sizeof(RootSplit), hipMemcpyHostToDevice));
     }
     if (total > ctx->cap_g1) {
         if (ctx->d_p1) (void)hipFree(ctx->d_p1);
         if (ctx->d_pts) (void)hipFree(ctx->d_pts);
         ctx->d_p1 = ctx->d_pts = nullptr;
         ctx->cap_g1 = 0;
-        NTT_TRY(hipMalloc(&ctx->d_p1, total * sizeof(blst_p1)));
-        NTT_TRY(hipMalloc(&ctx->d_pts, 2 * total * sizeof(Xyzz)));  // ping-pong halves
+        DEV_TRY(hipMalloc(&ctx->d_p1, total * sizeof(blst_p1)));
+        DEV_TRY(hipMalloc(&ctx->d_pts, 2 * total * sizeof(Xyzz)));  // ping-pong halves
         ctx->cap_g1 = total;
     }
     if (tab_lanes > ctx->cap_tab) {
         if (ctx->d_tab) (void)hipFree(ctx->d_tab);
         ctx->d_tab = nullptr;
         ctx->cap_tab = 0;
-        NTT_TRY(hipMalloc(&ctx->d_tab, tab_lanes * NTAB * sizeof(Xyzz)));
+        DEV_TRY(hipMalloc(&ctx->d_tab, tab_lanes * NTAB * sizeof(Xyzz)));
         ctx->cap_tab = tab_lanes;
     }
 }
@@ -649,14 +649,14 @@ void ensure_g1_tab(NttCtx* ctx, size_t tab_lanes) {
     if (!ctx->d_kroots) {
         std::vector<RootSplit> split(ctx->W + 1);
         for (size_t i = 0; i <= ctx->W; ++i) split[i] = split_scalar(ff::from_mont(ctx->roots[i]));
-        NTT_TRY(hipMalloc(&ctx->d_kroots, (ctx->W + 1) * sizeof(RootSplit)));
-        NTT_TRY(hipMemcpy(ctx->d_kroots, split.data(), (ctx->W + 1) * sizeof(RootSplit), hipMemcpyHostToDevice));
+        DEV_TRY(hipMalloc(&ctx->d_kroots, (ctx->W + 1) * sizeof(RootSplit)));
+        DEV_TRY(hipMemcpy(ctx->d_kroots, split.data(), (ctx->W + 1) * sizeof(RootSplit), hipMemcpyHostToDevice));
     }
     if (tab_lanes > ctx->cap_tab) {
         if (ctx->d_tab) (void)hipFree(ctx->d_tab);
         ctx->d_tab = nullptr;
         ctx->cap_tab = 0;
-        NTT_TRY(hipMalloc(&ctx->d_tab, tab_lanes * NTAB * sizeof(Xyzz)));
+        DEV_TRY(hipMalloc(&ctx->d_tab, tab_lanes * NTAB * sizeof(Xyzz)));
         ctx->cap_tab = tab_lanes;
     }
 }
@@ -691,9 +691,9 @@ static void* fftg1_enqueue(NttCtx* ctx, void* data_v, void* scratch_v, size_t n,
             const RootSplit inv_n = split_scalar(ff::from_mont(ff::inverse_bgcd(ff::to_mont(v))));
             enqueue_scale(ctx, res, tab, inv_n, total, st);
         }
-        NTT_TRY(hipGetLastError());
+        DEV_TRY(hipGetLastError());
         return res;
-    } catch (const NttErr&) {
+    } catch (const kzgamd::DevErr&) {
         return nullptr;
     }
 }
@@ -731,14 +731,14 @@ extern "C" int kzgamd_fft_g1_batch(void* vctx, blst_p1* out, const blst_p1* in, 
     std::lock_guard<std::mutex> lk(ctx->mu);
     try {
         kzgamd::DeviceGuard on_device(ctx->device);
-        NTT_TRY(on_device.err);
+        DEV_TRY(on_device.err);
         const size_t total = n * nbatch, bf = total / 2;
         const int logn = ilog2(n);
         ensure_g1(ctx, total, inverse ? 2 * total : (bf ? 2 * bf : 2));
         Xyzz* pts = (Xyzz*)ctx->d_pts;
         Xyzz* tab = (Xyzz*)ctx->d_tab;
         hipStream_t st = ctx->stream;
-        NTT_TRY(hipMemcpyAsync(ctx->d_p1, in, total * sizeof(blst_p1), hipMemcpyHostToDevice, st));
+        DEV_TRY(hipMemcpyAsync(ctx->d_p1, in, total * sizeof(blst_p1), hipMemcpyHostToDevice, st));
         hipLaunchKernelGGL(k_g1_load, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, pts, (const ff::Fp*)ctx->d_p1,
                            (u32)n, logn, total);
         Xyzz* bufs[2] = {pts, pts + total};
@@ -751,11 +751,11 @@ extern "C" int kzgamd_fft_g1_batch(void* vctx, blst_p1* out, const blst_p1* in, 
         }
         hipLaunchKernelGGL(k_g1_store, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (ff::Fp*)ctx->d_p1, (const Xyzz*)res,
                            total);
-        NTT_TRY(hipGetLastError());
-        NTT_TRY(hipMemcpyAsync(out, ctx->d_p1, total * sizeof(blst_p1), hipMemcpyDeviceToHost, st));
-        NTT_TRY(hipStreamSynchronize(st));
-    } catch (const NttErr& e) {
-        return -(int)e.e - 100;
+        DEV_TRY(hipGetLastError());
+        DEV_TRY(hipMemcpyAsync(out, ctx->d_p1, total * sizeof(blst_p1), hipMemcpyDeviceToHost, st));
+        DEV_TRY(hipStreamSynchronize(st));
+    } catch (const kzgamd::DevErr& e) {
+        return kzgamd::dev_code(e.e);
     }
     return 0;
 }

@@ -34,13 +34,18 @@
 #include "ff.hip.h"
 #include "g1_28.hip.h"
 #include "glv.hip.h"
+#include "host_call.h"
 #include "host_fp64.h"
+#include "host_g1.h"
 #include "msm_internal.h"
 #include "ntt_internal.h"
 
 using ff::Fr;
 using ff::u32;
 using g1::Xyzz;
+using kzgamd::blocks;
+using kzgamd::DevBuf;
+using kzgamd::DevErr;
 using kzgamd::RootSplit;
 
 namespace {
@@ -111,15 +116,6 @@ __global__ void __launch_bounds__(256) k_fk20g_brp(Xyzz* __restrict__ out, const
     out[t] = in[t - j + r];
 }
 
-struct FkErr {
-    hipError_t e;
-};
-#define FK_TRY(x)                              \
-    do {                                       \
-        hipError_t _e = (x);                   \
-        if (_e != hipSuccess) throw FkErr{_e}; \
-    } while (0)
-
 constexpr size_t CHUNK_PRODUCTS = (size_t)1 << 19;  // products per pass of a call: bounds the workspace (2.2 GB of lane tables)
 
 struct Fk20Ctx {
@@ -131,74 +127,39 @@ struct Fk20Ctx {
     Fr inv_k2;
     std::mutex mu;
     hipStream_t st = nullptr;
-    Xyzz* d_x = nullptr;                  // direct form: X[j][i], k2 * l points
+    DevBuf x;                             // direct form: X[j][i], k2 * l points
     kzgamd::MsmContext* msm = nullptr;    // table form: the same points as k2 base sets of l
     // workspace of a pass of `cap` polynomials
     size_t cap = 0;
-    Fr *d_poly = nullptr, *d_t = nullptr, *d_f = nullptr;
-    void* d_sc = nullptr;
-    Xyzz *d_prod = nullptr, *d_tab = nullptr, *d_h = nullptr, *d_h2 = nullptr;
-    void* d_out = nullptr;
+    DevBuf poly, t, f, sc, prod, tab, h, h2, out;
 
     void drop_workspace() {
-        void* all[] = {d_poly, d_t, d_f, d_sc, d_prod, d_tab, d_h, d_h2, d_out};
-        for (void* p : all)
-            if (p) (void)hipFree(p);
-        d_poly = d_t = d_f = nullptr;
-        d_sc = d_out = nullptr;
-        d_prod = d_tab = d_h = d_h2 = nullptr;
+        for (DevBuf* b : {&poly, &t, &f, &sc, &prod, &tab, &h, &h2, &out}) b->drop();
         cap = 0;
     }
     void ensure(size_t npoly) {
         if (npoly <= cap) return;
         drop_workspace();
         const size_t nprod = npoly * 2 * n, npos = npoly * k2;
-        FK_TRY(hipMalloc(&d_poly, npoly * n * sizeof(Fr)));
-        FK_TRY(hipMalloc(&d_t, nprod * sizeof(Fr)));
-        FK_TRY(hipMalloc(&d_f, nprod * sizeof(Fr)));
-        FK_TRY(hipMalloc(&d_sc, nprod * sizeof(RootSplit)));
-        if (form == 1 && l > 1) FK_TRY(hipMalloc(&d_prod, nprod * sizeof(Xyzz)));
+        poly.ensure(npoly * n * sizeof(Fr));
+        t.ensure(nprod * sizeof(Fr));
+        f.ensure(nprod * sizeof(Fr));
+        sc.ensure(nprod * sizeof(RootSplit));
+        if (form == 1 && l > 1) prod.ensure(nprod * sizeof(Xyzz));
         // lane tables: 9 slots per half-product (direct form) or per half-butterfly of the G1 transforms
-        FK_TRY(hipMalloc(&d_tab, 9 * (form == 1 ? 2 * nprod : npos) * sizeof(Xyzz)));
-        FK_TRY(hipMalloc(&d_h, npos * sizeof(Xyzz)));
-        FK_TRY(hipMalloc(&d_h2, npos * sizeof(Xyzz)));
-        FK_TRY(hipMalloc(&d_out, npos * sizeof(blst_p1)));
+        tab.ensure(9 * (form == 1 ? 2 * nprod : npos) * sizeof(Xyzz));
+        h.ensure(npos * sizeof(Xyzz));
+        h2.ensure(npos * sizeof(Xyzz));
+        out.ensure(npos * sizeof(blst_p1));
         cap = npoly;
     }
     ~Fk20Ctx() {
         drop_workspace();
-        if (d_x) (void)hipFree(d_x);
+        x.drop();
         if (msm) kzgamd::msm_destroy(msm);
         if (st) (void)hipStreamDestroy(st);
     }
 };
-
-inline unsigned blocks(size_t total) { return (unsigned)((total + 255) / 256); }
-
-// "fk20_table=<v>" out of a "key=value;key=value" tuning string (separators as config.h takes them): *value is set when
-// the key is there, *rest is the string without it; false when its value is not -1, 0 or 1
-bool take_fk20_table(const char* str, long* value, std::string* rest) {
-    static const char key[] = "fk20_table";
-    auto is_sep = [](char c) { return c == ';' || c == ',' || c == ' ' || c == '\t' || c == '\n'; };
-    const char* p = str;
-    while (*p) {
-        while (*p && is_sep(*p)) ++p;
-        const char* e = p;
-        while (*e && !is_sep(*e)) ++e;
-        if (e == p) break;
-        if ((size_t)(e - p) > sizeof key - 1 && !strncmp(p, key, sizeof key - 1) && p[sizeof key - 1] == '=') {
-            char* end = nullptr;
-            const long v = strtol(p + sizeof key, &end, 10);
-            if (end != e || end == p + sizeof key || v < -1 || v > 1) return false;
-            *value = v;
-        } else {
-            if (!rest->empty()) *rest += ';';
-            rest->append(p, e);
-        }
-        p = e;
-    }
-    return true;
-}
 
 // X[j][i] on the device from the monomial setup points: one batched G1 transform of l x k2 points
 void build_x(Fk20Ctx* fk, const blst_p1* mono) {
@@ -207,59 +168,41 @@ void build_x(Fk20Ctx* fk, const blst_p1* mono) {
     memset(x.data(), 0, total * sizeof(blst_p1));  // Z == 0: the identity
     for (size_t i = 0; i < l; ++i)
         for (size_t m = 0; m + 1 < k; ++m) x[i * k2 + m] = mono[n - l - 1 - i - l * m];
-    void *d_p1 = nullptr, *d_a = nullptr, *d_b = nullptr, *d_tab = nullptr;
+    kzgamd::ScopedBuf p1, a, b, tab;
     try {
-        FK_TRY(hipMalloc(&d_p1, total * sizeof(blst_p1)));
-        FK_TRY(hipMalloc(&d_a, total * sizeof(Xyzz)));
-        FK_TRY(hipMalloc(&d_b, total * sizeof(Xyzz)));
-        FK_TRY(hipMalloc(&d_tab, 9 * total * sizeof(Xyzz)));
-        FK_TRY(hipMalloc(&fk->d_x, total * sizeof(Xyzz)));
-        FK_TRY(hipMemcpyAsync(d_p1, x.data(), total * sizeof(blst_p1), hipMemcpyHostToDevice, fk->st));
-        kzgamd::g1_jacobian_to_xyzz(d_a, d_p1, total, fk->st);
-        void* res = kzgamd::fftg1_device_tab(fk->ntt, d_a, d_b, k2, l, 0, fk->st, d_tab);
-        if (!res) throw FkErr{hipErrorOutOfMemory};
-        hipLaunchKernelGGL(k_fk20g_transpose_x, dim3(blocks(total)), dim3(256), 0, fk->st, fk->d_x, (const Xyzz*)res, l, k2);
-        FK_TRY(hipGetLastError());
-        FK_TRY(hipStreamSynchronize(fk->st));
+        p1.alloc(total * sizeof(blst_p1));
+        a.alloc(total * sizeof(Xyzz));
+        b.alloc(total * sizeof(Xyzz));
+        tab.alloc(9 * total * sizeof(Xyzz));
+        fk->x.ensure(total * sizeof(Xyzz));
+        DEV_TRY(hipMemcpyAsync(p1.p, x.data(), total * sizeof(blst_p1), hipMemcpyHostToDevice, fk->st));
+        kzgamd::g1_jacobian_to_xyzz(a.p, p1.p, total, fk->st);
+        void* res = kzgamd::fftg1_device_tab(fk->ntt, a.p, b.p, k2, l, 0, fk->st, tab.p);
+        if (!res) throw DevErr{hipErrorOutOfMemory};
+        hipLaunchKernelGGL(k_fk20g_transpose_x, dim3(blocks(total)), dim3(256), 0, fk->st, fk->x.as<Xyzz>(), (const Xyzz*)res, l, k2);
+        DEV_TRY(hipGetLastError());
+        DEV_TRY(hipStreamSynchronize(fk->st));
     } catch (...) {
-        (void)hipStreamSynchronize(fk->st);
-        for (void* p : {d_p1, d_a, d_b, d_tab})
-            if (p) (void)hipFree(p);
+        (void)hipStreamSynchronize(fk->st);  // before the buffers of the call go
         throw;
     }
-    for (void* p : {d_p1, d_a, d_b, d_tab}) (void)hipFree(p);
 }
 
-// the table form: X[j][i] as affine points on the host (Montgomery's trick over the Z coordinates; the identity as
-// (0, 0), blst's affine infinity) -> a wide fixed-base table of k2 base sets of l points.  false: no table fits.
+// the table form: X[j][i] as affine points on the host -> a wide fixed-base table of k2 base sets of l points.
+// false: no table fits.
 bool build_table(Fk20Ctx* fk, const kzgamd::Options& opt) {
     const size_t total = fk->k2 * fk->l;
     if (!kzgamd::msm_wide_table_fits(total, &opt)) return false;
-    std::vector<ff::Fp> jac(3 * total), aff(2 * total), pre(total);
-    void* d_p1 = nullptr;
-    FK_TRY(hipMalloc(&d_p1, total * sizeof(blst_p1)));
-    kzgamd::g1_xyzz_to_jacobian(d_p1, fk->d_x, total, fk->st);
-    hipError_t e = hipMemcpyAsync(jac.data(), d_p1, total * sizeof(blst_p1), hipMemcpyDeviceToHost, fk->st);
-    if (e == hipSuccess) e = hipStreamSynchronize(fk->st);
-    (void)hipFree(d_p1);
-    FK_TRY(e);
-    ff::Fp run = ff::Fp::one();
-    for (size_t i = 0; i < total; ++i) {
-        pre[i] = run;
-        if (!jac[3 * i + 2].is_zero()) run = hfp::mul(run, jac[3 * i + 2]);
+    std::vector<blst_p1> jac(total);
+    std::vector<ff::Fp> aff(2 * total);
+    {
+        kzgamd::ScopedBuf p1;
+        p1.alloc(total * sizeof(blst_p1));
+        kzgamd::g1_xyzz_to_jacobian(p1.p, fk->x.p, total, fk->st);
+        DEV_TRY(hipMemcpyAsync(jac.data(), p1.p, total * sizeof(blst_p1), hipMemcpyDeviceToHost, fk->st));
+        DEV_TRY(hipStreamSynchronize(fk->st));
     }
-    ff::Fp inv = ff::inverse_bgcd(run);
-    for (size_t i = total; i-- > 0;) {
-        const ff::Fp* P = &jac[3 * i];
-        if (P[2].is_zero()) {
-            aff[2 * i] = aff[2 * i + 1] = ff::Fp::zero();
-            continue;
-        }
-        const ff::Fp zi = hfp::mul(inv, pre[i]), zi2 = hfp::sqr(zi);
-        inv = hfp::mul(inv, P[2]);
-        aff[2 * i] = hfp::mul(P[0], zi2);
-        aff[2 * i + 1] = hfp::mul(P[1], hfp::mul(zi2, zi));
-    }
+    kzgamd::host_p1_to_affine_batch(aff.data(), total, [&](size_t i) { return &jac[i]; });
     kzgamd::MsmContext* m = nullptr;
     try {
         m = kzgamd::msm_create(aff.data(), total, false, true, false, kzgamd::G1_TRUSTED, &opt);
@@ -279,39 +222,37 @@ void run_pass(Fk20Ctx* fk, blst_p1* out, const blst_fr* polys, size_t cnt, int o
     const size_t n = fk->n, l = fk->l, k = fk->k, k2 = fk->k2;
     const size_t nprod = cnt * k2 * l, npos = cnt * k2;
     hipStream_t st = fk->st;
-    FK_TRY(hipMemcpyAsync(fk->d_poly, polys, cnt * n * sizeof(Fr), hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_fk20g_toeplitz, dim3(blocks(nprod)), dim3(256), 0, st, fk->d_t, (const Fr*)fk->d_poly, n, l, k, nprod);
-    if (kzgamd_ntt_fr_device(fk->ntt, fk->d_f, fk->d_t, k2, l * cnt, 0, st) != 0) throw FkErr{hipErrorUnknown};
-    hipLaunchKernelGGL(k_fk20g_scalars, dim3(blocks(nprod)), dim3(256), 0, st, fk->d_sc, (const Fr*)fk->d_f, l, k2, fk->inv_k2,
+    Fr *d_t = fk->t.as<Fr>(), *d_f = fk->f.as<Fr>();
+    Xyzz *d_h = fk->h.as<Xyzz>(), *d_h2 = fk->h2.as<Xyzz>(), *d_tab = fk->tab.as<Xyzz>();
+    DEV_TRY(hipMemcpyAsync(fk->poly.p, polys, cnt * n * sizeof(Fr), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_fk20g_toeplitz, dim3(blocks(nprod)), dim3(256), 0, st, d_t, (const Fr*)fk->poly.p, n, l, k, nprod);
+    if (kzgamd_ntt_fr_device(fk->ntt, d_f, d_t, k2, l * cnt, 0, st) != 0) throw DevErr{hipErrorUnknown};
+    hipLaunchKernelGGL(k_fk20g_scalars, dim3(blocks(nprod)), dim3(256), 0, st, fk->sc.p, (const Fr*)d_f, l, k2, fk->inv_k2,
                        fk->form == 1 ? 1 : 0, nprod);
     if (fk->form == 1) {
-        kzgamd::g1_varmul_sum_device(fk->ntt, fk->d_h, fk->d_prod, fk->d_tab, fk->d_x, k2 * l, (const RootSplit*)fk->d_sc, nprod, l, st);
+        kzgamd::g1_varmul_sum_device(fk->ntt, d_h, fk->prod.p, d_tab, fk->x.p, k2 * l, (const RootSplit*)fk->sc.p, nprod, l, st);
     } else {
         // h_ext[poly][j] = sum_i scalars[poly][j][i] * X[j][i]: cnt * k2 MSMs of l points, base set j of the table
-        kzgamd::msm_lock(fk->msm);
-        try {
-            kzgamd::msm_enqueue(fk->msm, fk->d_h, fk->d_sc, l, npos, 1, st, kzgamd::OUT_XYZZ, false, k2);
-        } catch (...) {
-            kzgamd::msm_unlock(fk->msm);
-            throw FkErr{hipErrorUnknown};
-        }
-        kzgamd::msm_unlock(fk->msm);
+        kzgamd::foreign([&] {
+            kzgamd::MsmLock locked(fk->msm);
+            kzgamd::msm_enqueue(fk->msm, d_h, fk->sc.p, l, npos, 1, st, kzgamd::OUT_XYZZ, false, k2);
+        });
     }
     // h = ifft_g1(h_ext) (its k2^-1 is in the scalars), upper half cleared, proofs = fft_g1(h)
-    Xyzz* h = (Xyzz*)kzgamd::fftg1_device_tab(fk->ntt, fk->d_h, fk->d_h2, k2, cnt, 1, st, fk->d_tab);
-    if (!h) throw FkErr{hipErrorUnknown};
-    Xyzz* other = h == fk->d_h ? fk->d_h2 : fk->d_h;
+    Xyzz* h = (Xyzz*)kzgamd::fftg1_device_tab(fk->ntt, d_h, d_h2, k2, cnt, 1, st, d_tab);
+    if (!h) throw DevErr{hipErrorUnknown};
+    Xyzz* other = h == d_h ? d_h2 : d_h;
     hipLaunchKernelGGL(k_fk20g_zero_upper, dim3(blocks(cnt * k)), dim3(256), 0, st, h, k, cnt * k);
-    Xyzz* pr = (Xyzz*)kzgamd::fftg1_device_tab(fk->ntt, h, other, k2, cnt, 0, st, fk->d_tab);
-    if (!pr) throw FkErr{hipErrorUnknown};
+    Xyzz* pr = (Xyzz*)kzgamd::fftg1_device_tab(fk->ntt, h, other, k2, cnt, 0, st, d_tab);
+    if (!pr) throw DevErr{hipErrorUnknown};
     if (!optimized) {
         Xyzz* fin = pr == h ? other : h;
         hipLaunchKernelGGL(k_fk20g_brp, dim3(blocks(npos)), dim3(256), 0, st, fin, (const Xyzz*)pr, k2, fk->logk2, npos);
         pr = fin;
     }
-    kzgamd::g1_xyzz_to_jacobian(fk->d_out, pr, npos, st);
-    FK_TRY(hipGetLastError());
-    FK_TRY(hipMemcpyAsync(out, fk->d_out, npos * sizeof(blst_p1), hipMemcpyDeviceToHost, st));
+    kzgamd::g1_xyzz_to_jacobian(fk->out.p, pr, npos, st);
+    DEV_TRY(hipGetLastError());
+    DEV_TRY(hipMemcpyAsync(out, fk->out.p, npos * sizeof(blst_p1), hipMemcpyDeviceToHost, st));
 }
 
 }  // namespace
@@ -336,11 +277,11 @@ extern "C" void* kzgamd_fk20_new(void* vntt, const blst_p1* g1_monomial, size_t 
     if (*err) return nullptr;
     // fk20_table is a key of this handle type alone: it is taken out of cfg->tuning here, the rest goes to the library's
     // table of keys (config.h) as for every other handle
-    long want = -1;
+    long long want = -1;
     KzgAmdConfig local;
     std::string rest, msg;
     if (cfg && cfg->struct_size >= offsetof(KzgAmdConfig, tuning) + sizeof(cfg->tuning) && cfg->tuning) {
-        if (!take_fk20_table(cfg->tuning, &want, &rest)) {
+        if (!kzgamd::take_key(cfg->tuning, "fk20_table", -1, 1, &want, &rest)) {
             fprintf(stderr, "kzg_mi355x: kzgamd_fk20_new: tuning: 'fk20_table' takes -1, 0 or 1\n");
             *err = -2;
             return nullptr;
@@ -356,12 +297,8 @@ extern "C" void* kzgamd_fk20_new(void* vntt, const blst_p1* g1_monomial, size_t 
         return nullptr;
     }
     opt.device = ntt->device;  // the handle lives where its NTT handle lives
-    auto* fk = new Fk20Ctx();
-    try {
-        kzgamd::DeviceGuard on_device(ntt->device);
-        FK_TRY(on_device.err);
+    Fk20Ctx* fk = kzgamd::create_handle<Fk20Ctx>(ntt->device, err, [&](Fk20Ctx* fk) {
         fk->ntt = ntt;
-        fk->device = ntt->device;
         fk->n2 = n2;
         fk->n = n2 / 2;
         fk->l = chunk_len;
@@ -372,28 +309,18 @@ extern "C" void* kzgamd_fk20_new(void* vntt, const blst_p1* g1_monomial, size_t 
         v.v[0] = (u32)fk->k2;
         v.v[1] = (u32)((uint64_t)fk->k2 >> 32);
         fk->inv_k2 = ff::inverse_bgcd(ff::to_mont(v));  // Montgomery form of 1 / k2
-        FK_TRY(hipStreamCreateWithFlags(&fk->st, hipStreamNonBlocking));
+        DEV_TRY(hipStreamCreateWithFlags(&fk->st, hipStreamNonBlocking));
         build_x(fk, g1_monomial);
         if (want != 0 && build_table(fk, opt)) {
             fk->form = 2;
-            (void)hipFree(fk->d_x);  // the table holds the points now
-            fk->d_x = nullptr;
-        } else if (want == 1) {
-            fprintf(stderr, "kzg_mi355x: kzgamd_fk20_new: fk20_table=1, but no wide table of %zu x %zu points fits the budget\n",
-                    fk->k2, fk->l);
-            *err = -3;
-            delete fk;
-            return nullptr;
+            fk->x.drop();  // the table holds the points now
         }
-    } catch (const FkErr& e) {
-        *err = -(int)e.e - 100;
-        kzgamd::DeviceGuard on_device(ntt->device);
-        delete fk;
-        return nullptr;
-    } catch (...) {
-        *err = -4;
-        kzgamd::DeviceGuard on_device(ntt->device);
-        delete fk;
+    });
+    if (fk && want == 1 && fk->form != 2) {
+        fprintf(stderr, "kzg_mi355x: kzgamd_fk20_new: fk20_table=1, but no wide table of %zu x %zu points fits the budget\n", fk->k2,
+                fk->l);
+        *err = -3;
+        kzgamd_fk20_free(fk);
         return nullptr;
     }
     return fk;
@@ -421,29 +348,14 @@ extern "C" int kzgamd_fk20_da(void* vfk, blst_p1* out, const blst_fr* polys, siz
     if (n != fk->n) return 3;
     if (npoly == 0) return 0;
     if (!out || !polys) return -1;
-    std::lock_guard<std::mutex> lk(fk->mu);
-    int rc = 0;
-    try {
-        kzgamd::DeviceGuard on_device(fk->device);
-        FK_TRY(on_device.err);
+    return kzgamd::run_call(fk, [&] {
         size_t per = CHUNK_PRODUCTS / (2 * fk->n);
         if (per == 0) per = 1;
         if (per > npoly) per = npoly;
         fk->ensure(per);
-        try {
-            for (size_t done = 0; done < npoly; done += per) {
-                const size_t cnt = npoly - done < per ? npoly - done : per;
-                run_pass(fk, out + done * fk->k2, polys + done * fk->n, cnt, optimized);
-            }
-        } catch (...) {
-            (void)hipStreamSynchronize(fk->st);  // a copy into the caller's buffer may be in flight
-            throw;
+        for (size_t done = 0; done < npoly; done += per) {
+            const size_t cnt = npoly - done < per ? npoly - done : per;
+            run_pass(fk, out + done * fk->k2, polys + done * fk->n, cnt, optimized);
         }
-        FK_TRY(hipStreamSynchronize(fk->st));
-    } catch (const FkErr& e) {
-        rc = -(int)e.e - 100;
-    } catch (...) {
-        rc = -2;
-    }
-    return rc;
+    });
 }

@@ -30,12 +30,14 @@
 #include <vector>
 
 #include "../../include/kzg_mi355x.h"
+#include "config.h"
 #include "device_guard.h"
 #include "ff.hip.h"
 #include "fr29.hip.h"
 #include "g1_28.hip.h"
 #include "g1_io.hip.h"
 #include "g2_28.hip.h"
+#include "host_call.h"
 #include "host_fp64.h"
 #include "host_g1.h"
 #include "host_pairing.h"
@@ -45,6 +47,8 @@ using ff::Fr;
 using ff::u32;
 using ff::u64;
 using g1::Xyzz;
+using kzgamd::blocks;
+using kzgamd::ScopedBuf;
 
 namespace {
 
@@ -56,17 +60,6 @@ constexpr int POW_CHUNK = 16;             // consecutive powers per lane of k_fr
 constexpr size_t SLICE_DEFAULT = (size_t)1 << 18;  // outputs per slice: 8 MB of scalars, 58 MB of XYZZ, 75 MB of blst_p2
 constexpr size_t SLICE_MIN = 64;
 constexpr size_t FFT_TAB = 9;             // g1::Xyzz of table per point that fftg1_device_tab asks for (ntt_internal.h)
-
-struct GmErr {
-    hipError_t e;
-};
-#define GM_TRY(x)                              \
-    do {                                       \
-        hipError_t _e = (x);                   \
-        if (_e != hipSuccess) throw GmErr{_e}; \
-    } while (0)
-
-inline unsigned blocks(size_t total, unsigned threads) { return (unsigned)((total + threads - 1) / threads); }
 
 // out[i] = c * s^(start + i), i < n; blst Montgomery form in and out
 __global__ void __launch_bounds__(256) k_fr_powers(Fr* __restrict__ out, Fr s, Fr c, u64 start, size_t n) {
@@ -204,19 +197,9 @@ __global__ void __launch_bounds__(64) k_g2_mul(ff::Fp* __restrict__ out, const F
 // ---------------------------------------------------------------- host side
 namespace hp = kzgamd::pairing;
 
-struct DevBuf {  // freed when the call ends, whichever way
-    void* p = nullptr;
-    ~DevBuf() {
-        if (p) (void)hipFree(p);
-    }
-    void alloc(size_t bytes) { GM_TRY(hipMalloc(&p, bytes ? bytes : 1)); }
-    DevBuf() = default;
-    DevBuf(const DevBuf&) = delete;
-    DevBuf& operator=(const DevBuf&) = delete;
-};
 struct Stream {
     hipStream_t st = nullptr;
-    Stream() { GM_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking)); }
+    Stream() { DEV_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking)); }
     ~Stream() {
         if (st) {
             (void)hipStreamSynchronize(st);
@@ -246,22 +229,22 @@ g2::AffPt g2_affpt(const hp::G2Affine& q) {
 
 // the table of `base` on the current device, built on `st` and complete when this returns
 void build_g1_table(g1::AffPt* d_tab, const g1::AffPt& base, hipStream_t st) {
-    DevBuf tmp;
+    ScopedBuf tmp;
     tmp.alloc((size_t)NTAB * sizeof(Xyzz));
     hipLaunchKernelGGL(k_g1_tab_chain, dim3(1), dim3(64), 0, st, (Xyzz*)tmp.p, base);
     hipLaunchKernelGGL(k_g1_tab_affine, dim3(blocks(NTAB, 64)), dim3(64), 0, st, d_tab, (const Xyzz*)tmp.p);
-    GM_TRY(hipGetLastError());
-    GM_TRY(hipStreamSynchronize(st));
+    DEV_TRY(hipGetLastError());
+    DEV_TRY(hipStreamSynchronize(st));
 }
 void build_g2_table(g2::AffPt* d_tab, const g2::AffPt& base, hipStream_t st) {
-    DevBuf tmp, bases;
+    ScopedBuf tmp, bases;
     tmp.alloc((size_t)NTAB * sizeof(g2::Jac));
     bases.alloc((size_t)NWIN * sizeof(g2::AffPt));
     hipLaunchKernelGGL(k_g2_tab_base, dim3(1), dim3(64), 0, st, (g2::AffPt*)bases.p, base);
     hipLaunchKernelGGL(k_g2_tab_chain, dim3(1), dim3(64), 0, st, (g2::Jac*)tmp.p, (const g2::AffPt*)bases.p);
     hipLaunchKernelGGL(k_g2_tab_affine, dim3(blocks(NTAB, 64)), dim3(64), 0, st, d_tab, (const g2::Jac*)tmp.p);
-    GM_TRY(hipGetLastError());
-    GM_TRY(hipStreamSynchronize(st));
+    DEV_TRY(hipGetLastError());
+    DEV_TRY(hipStreamSynchronize(st));
 }
 
 // the generators' tables: built at first use on a device, read-only and kept from then on
@@ -283,7 +266,7 @@ const g1::AffPt* g1_generator_table(int device, hipStream_t st) {
     std::lock_guard<std::mutex> lk(g_mu);
     GenTables* t = gen_entry(device);
     if (!t->g1) {
-        DevBuf tab;
+        ScopedBuf tab;
         tab.alloc((size_t)NTAB * sizeof(g1::AffPt));
         ff::Fp x, y;
         kzgamd::host_g1_generator(x, y);
@@ -297,34 +280,13 @@ const g2::AffPt* g2_generator_table(int device, hipStream_t st) {
     std::lock_guard<std::mutex> lk(g_mu);
     GenTables* t = gen_entry(device);
     if (!t->g2) {
-        DevBuf tab;
+        ScopedBuf tab;
         tab.alloc((size_t)NTAB * sizeof(g2::AffPt));
         build_g2_table((g2::AffPt*)tab.p, g2_affpt(hp::g2_to_affine(hp::g2_generator())), st);
         t->g2 = (g2::AffPt*)tab.p;
         tab.p = nullptr;
     }
     return t->g2;
-}
-
-// "mul_slice=<v>" out of a "key=value;key=value" tuning string (separators as config.h takes them).  It is the one key
-// of these calls, so anything else in the string fails them; false also when the value is no power of two >= 64.
-bool take_mul_slice(const char* str, size_t* value) {
-    static const char key[] = "mul_slice";
-    auto is_sep = [](char c) { return c == ';' || c == ',' || c == ' ' || c == '\t' || c == '\n'; };
-    const char* p = str;
-    while (*p) {
-        while (*p && is_sep(*p)) ++p;
-        const char* e = p;
-        while (*e && !is_sep(*e)) ++e;
-        if (e == p) break;
-        if ((size_t)(e - p) <= sizeof key - 1 || strncmp(p, key, sizeof key - 1) || p[sizeof key - 1] != '=') return false;
-        char* end = nullptr;
-        const long long v = strtoll(p + sizeof key, &end, 10);
-        if (end != e || end == p + sizeof key || v < (long long)SLICE_MIN || v > (1ll << 30) || (v & (v - 1))) return false;
-        *value = (size_t)v;
-        p = e;
-    }
-    return true;
 }
 
 // what a KzgAmdConfig means to these calls: 0, or the call's return code
@@ -337,10 +299,15 @@ int read_config(const KzgAmdConfig* cfg, const char* who, int* device, size_t* s
         return -2;
     }
     *device = cfg->device;
-    if (cfg->tuning && !take_mul_slice(cfg->tuning, slice)) {
+    // mul_slice is the one key of these calls: anything else in the string fails them
+    long long v = (long long)*slice;
+    std::string rest;
+    if (cfg->tuning &&
+        (!kzgamd::take_key(cfg->tuning, "mul_slice", (long long)SLICE_MIN, 1ll << 30, &v, &rest) || !rest.empty() || (v & (v - 1)))) {
         fprintf(stderr, "kzg_mi355x: %s: tuning: the one key of this call is 'mul_slice' (a power of two, at least 64)\n", who);
         return -2;
     }
+    *slice = (size_t)v;
     return 0;
 }
 
@@ -354,7 +321,7 @@ int current_or(int device, hipError_t* e) {
 
 // per-call workspace of one slice
 struct SliceBufs {
-    DevBuf sc, xyzz, pts;
+    ScopedBuf sc, xyzz, pts;
     void alloc(size_t slice, bool g1, bool g2) {
         sc.alloc(slice * sizeof(Fr));
         if (g1) xyzz.alloc(slice * sizeof(Xyzz));
@@ -371,8 +338,6 @@ void enqueue_g2_mul(void* d_out, const Fr* d_sc, const g2::AffPt* tab, size_t n,
 void enqueue_powers(Fr* d_out, const Fr& s, const Fr& c, size_t start, size_t n, hipStream_t st) {
     hipLaunchKernelGGL(k_fr_powers, dim3(blocks((n + POW_CHUNK - 1) / POW_CHUNK, 256)), dim3(256), 0, st, d_out, s, c, (u64)start, n);
 }
-
-int code_of(hipError_t e) { return -(int)e - 100; }
 
 }  // namespace
 
@@ -391,23 +356,22 @@ extern "C" int kzgamd_g1_mul_batch(blst_p1* out, const blst_p1* base, const blst
     if (int rc = read_config(cfg, "kzgamd_g1_mul_batch", &device, &slice)) return rc;
     g1::AffPt b;
     if (base) {
-        const ff::Fp* P = reinterpret_cast<const ff::Fp*>(base);
-        if (P[2].is_zero()) {
+        ff::Fp x, y;
+        if (kzgamd::host_p1_to_affine(base, x, y)) {
             memset(out, 0, n * sizeof(blst_p1));
             return 0;
         }
         if (!kzgamd::host_p1_in_g1(base)) return 3;
-        const ff::Fp zi = ff::inverse_bgcd(P[2]), zi2 = hfp::sqr(zi);
-        b = g1_affpt(hfp::mul(P[0], zi2), hfp::mul(P[1], hfp::mul(zi2, zi)));
+        b = g1_affpt(x, y);
     }
-    try {
+    return kzgamd::status_of([&] {
         hipError_t e;
         device = current_or(device, &e);
-        GM_TRY(e);
+        DEV_TRY(e);
         kzgamd::DeviceGuard on_device(device);
-        GM_TRY(on_device.err);
+        DEV_TRY(on_device.err);
         Stream s;
-        DevBuf own;
+        ScopedBuf own;
         const g1::AffPt* tab;
         if (base) {
             own.alloc((size_t)NTAB * sizeof(g1::AffPt));
@@ -421,19 +385,14 @@ extern "C" int kzgamd_g1_mul_batch(blst_p1* out, const blst_p1* base, const blst
         w.alloc(slice, true, false);
         for (size_t at = 0; at < n; at += slice) {
             const size_t cnt = n - at < slice ? n - at : slice;
-            GM_TRY(hipMemcpyAsync(w.sc.p, scalars + at, cnt * sizeof(Fr), hipMemcpyHostToDevice, s.st));
+            DEV_TRY(hipMemcpyAsync(w.sc.p, scalars + at, cnt * sizeof(Fr), hipMemcpyHostToDevice, s.st));
             enqueue_g1_mul((Xyzz*)w.xyzz.p, (const Fr*)w.sc.p, tab, cnt, s.st);
             kzgamd::g1_xyzz_to_jacobian(w.pts.p, w.xyzz.p, cnt, s.st);
-            GM_TRY(hipGetLastError());
-            GM_TRY(hipMemcpyAsync(out + at, w.pts.p, cnt * sizeof(blst_p1), hipMemcpyDeviceToHost, s.st));
-            GM_TRY(hipStreamSynchronize(s.st));
+            DEV_TRY(hipGetLastError());
+            DEV_TRY(hipMemcpyAsync(out + at, w.pts.p, cnt * sizeof(blst_p1), hipMemcpyDeviceToHost, s.st));
+            DEV_TRY(hipStreamSynchronize(s.st));
         }
-        return 0;
-    } catch (const GmErr& e) {
-        return code_of(e.e);
-    } catch (...) {
-        return -2;
-    }
+    });
 }
 
 extern "C" int kzgamd_g2_mul_batch(blst_p2* out, const blst_p2* base, const blst_fr* scalars, size_t n, const KzgAmdConfig* cfg) {
@@ -452,14 +411,14 @@ extern "C" int kzgamd_g2_mul_batch(blst_p2* out, const blst_p2* base, const blst
         }
         b = g2_affpt(hp::g2_to_affine(p));
     }
-    try {
+    return kzgamd::status_of([&] {
         hipError_t e;
         device = current_or(device, &e);
-        GM_TRY(e);
+        DEV_TRY(e);
         kzgamd::DeviceGuard on_device(device);
-        GM_TRY(on_device.err);
+        DEV_TRY(on_device.err);
         Stream s;
-        DevBuf own;
+        ScopedBuf own;
         const g2::AffPt* tab;
         if (base) {
             own.alloc((size_t)NTAB * sizeof(g2::AffPt));
@@ -473,18 +432,13 @@ extern "C" int kzgamd_g2_mul_batch(blst_p2* out, const blst_p2* base, const blst
         w.alloc(slice, false, true);
         for (size_t at = 0; at < n; at += slice) {
             const size_t cnt = n - at < slice ? n - at : slice;
-            GM_TRY(hipMemcpyAsync(w.sc.p, scalars + at, cnt * sizeof(Fr), hipMemcpyHostToDevice, s.st));
+            DEV_TRY(hipMemcpyAsync(w.sc.p, scalars + at, cnt * sizeof(Fr), hipMemcpyHostToDevice, s.st));
             enqueue_g2_mul(w.pts.p, (const Fr*)w.sc.p, tab, cnt, s.st);
-            GM_TRY(hipGetLastError());
-            GM_TRY(hipMemcpyAsync(out + at, w.pts.p, cnt * sizeof(blst_p2), hipMemcpyDeviceToHost, s.st));
-            GM_TRY(hipStreamSynchronize(s.st));
+            DEV_TRY(hipGetLastError());
+            DEV_TRY(hipMemcpyAsync(out + at, w.pts.p, cnt * sizeof(blst_p2), hipMemcpyDeviceToHost, s.st));
+            DEV_TRY(hipStreamSynchronize(s.st));
         }
-        return 0;
-    } catch (const GmErr& e) {
-        return code_of(e.e);
-    } catch (...) {
-        return -2;
-    }
+    });
 }
 
 extern "C" int kzgamd_generate_trusted_setup(void* vntt, blst_p1* g1_monomial, blst_p1* g1_lagrange, blst_p2* g2_monomial,
@@ -508,12 +462,12 @@ extern "C" int kzgamd_generate_trusted_setup(void* vntt, blst_p1* g1_monomial, b
         s.v[i] = ((u32)q[0] << 24) | ((u32)q[1] << 16) | ((u32)q[2] << 8) | (u32)q[3];
     }
     s = ff::mul(s, Fr::r2());
-    try {
+    return kzgamd::status_of([&] {
         hipError_t e = hipSuccess;
         device = want_lag ? ntt->device : current_or(device, &e);  // the transform runs where its handle lives
-        GM_TRY(e);
+        DEV_TRY(e);
         kzgamd::DeviceGuard on_device(device);
-        GM_TRY(on_device.err);
+        DEV_TRY(on_device.err);
         Stream st;
         const size_t g1n = want_mono || want_lag ? num_g1 : 0, g2n = want_g2 ? num_g2 : 0;  // of the outputs wanted
         const size_t most = g1n > g2n ? g1n : g2n;
@@ -529,14 +483,14 @@ extern "C" int kzgamd_generate_trusted_setup(void* vntt, blst_p1* g1_monomial, b
                     enqueue_powers((Fr*)w.sc.p, s, one, at, cnt, st.st);
                     enqueue_g1_mul((Xyzz*)w.xyzz.p, (const Fr*)w.sc.p, tab, cnt, st.st);
                     kzgamd::g1_xyzz_to_jacobian(w.pts.p, w.xyzz.p, cnt, st.st);
-                    GM_TRY(hipGetLastError());
-                    GM_TRY(hipMemcpyAsync(g1_monomial + at, w.pts.p, cnt * sizeof(blst_p1), hipMemcpyDeviceToHost, st.st));
-                    GM_TRY(hipStreamSynchronize(st.st));
+                    DEV_TRY(hipGetLastError());
+                    DEV_TRY(hipMemcpyAsync(g1_monomial + at, w.pts.p, cnt * sizeof(blst_p1), hipMemcpyDeviceToHost, st.st));
+                    DEV_TRY(hipStreamSynchronize(st.st));
                 }
             }
             if (want_lag) {
                 // the points [s^i / n]G, device-resident, through the unscaled inverse transform
-                DevBuf a, b, ftab;
+                ScopedBuf a, b, ftab;
                 a.alloc(num_g1 * sizeof(Xyzz));
                 b.alloc(num_g1 * sizeof(Xyzz));
                 ftab.alloc(FFT_TAB * num_g1 * sizeof(Xyzz));
@@ -549,15 +503,15 @@ extern "C" int kzgamd_generate_trusted_setup(void* vntt, blst_p1* g1_monomial, b
                     enqueue_powers((Fr*)w.sc.p, s, inv_n, at, cnt, st.st);
                     enqueue_g1_mul((Xyzz*)a.p + at, (const Fr*)w.sc.p, tab, cnt, st.st);
                 }
-                GM_TRY(hipGetLastError());
+                DEV_TRY(hipGetLastError());
                 const Xyzz* res = (const Xyzz*)kzgamd::fftg1_device_tab(ntt, a.p, b.p, num_g1, 1, 1, st.st, ftab.p);
-                if (!res) throw GmErr{hipErrorOutOfMemory};
+                if (!res) throw kzgamd::DevErr{hipErrorOutOfMemory};
                 for (size_t at = 0; at < num_g1; at += slice) {
                     const size_t cnt = num_g1 - at < slice ? num_g1 - at : slice;
                     kzgamd::g1_xyzz_to_jacobian(w.pts.p, res + at, cnt, st.st);
-                    GM_TRY(hipGetLastError());
-                    GM_TRY(hipMemcpyAsync(g1_lagrange + at, w.pts.p, cnt * sizeof(blst_p1), hipMemcpyDeviceToHost, st.st));
-                    GM_TRY(hipStreamSynchronize(st.st));
+                    DEV_TRY(hipGetLastError());
+                    DEV_TRY(hipMemcpyAsync(g1_lagrange + at, w.pts.p, cnt * sizeof(blst_p1), hipMemcpyDeviceToHost, st.st));
+                    DEV_TRY(hipStreamSynchronize(st.st));
                 }
             }
         }
@@ -567,17 +521,10 @@ extern "C" int kzgamd_generate_trusted_setup(void* vntt, blst_p1* g1_monomial, b
                 const size_t cnt = num_g2 - at < slice ? num_g2 - at : slice;
                 enqueue_powers((Fr*)w.sc.p, s, one, at, cnt, st.st);
                 enqueue_g2_mul(w.pts.p, (const Fr*)w.sc.p, tab, cnt, st.st);
-                GM_TRY(hipGetLastError());
-                GM_TRY(hipMemcpyAsync(g2_monomial + at, w.pts.p, cnt * sizeof(blst_p2), hipMemcpyDeviceToHost, st.st));
-                GM_TRY(hipStreamSynchronize(st.st));
+                DEV_TRY(hipGetLastError());
+                DEV_TRY(hipMemcpyAsync(g2_monomial + at, w.pts.p, cnt * sizeof(blst_p2), hipMemcpyDeviceToHost, st.st));
+                DEV_TRY(hipStreamSynchronize(st.st));
             }
         }
-        return 0;
-    } catch (const GmErr& e) {
-        return code_of(e.e);
-    } catch (const NttErr& e) {
-        return code_of(e.e);
-    } catch (...) {
-        return -2;
-    }
+    });
 }

@@ -1,0 +1,144 @@
+// The host-side frame of the generic handles (Poly, ZeroPoly, KZG, FK20, the NTT handle) and of the handle-less group
+// multiplication: one error type, the device buffers, and the frames a call and a handle creation run in.
+// Host-only: nothing here launches a kernel.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stddef.h>
+
+#include <mutex>
+#include <type_traits>
+
+#include "device_guard.h"
+
+namespace kzgamd {
+
+struct DevErr {
+    hipError_t e;
+};
+#define DEV_TRY(x)                                     \
+    do {                                               \
+        hipError_t _e = (x);                           \
+        if (_e != hipSuccess) throw kzgamd::DevErr{_e}; \
+    } while (0)
+
+// what a call returns for a failed HIP call: -(100 + hipError_t)
+inline int dev_code(hipError_t e) { return -(int)e - 100; }
+
+// workspace of a handle: grows when a call needs more, kept until the handle drops it
+struct DevBuf {
+    void* p = nullptr;
+    size_t cap = 0;
+    void ensure(size_t bytes) {
+        if (bytes <= cap) return;
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        cap = 0;
+        DEV_TRY(hipMalloc(&p, bytes));
+        cap = bytes;
+    }
+    void drop() {
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        cap = 0;
+    }
+    template <class T>
+    T* as() const {
+        return (T*)p;
+    }
+};
+
+// workspace of one call: freed when the call ends, whichever way
+struct ScopedBuf {
+    void* p = nullptr;
+    ~ScopedBuf() {
+        if (p) (void)hipFree(p);
+    }
+    void alloc(size_t bytes) { DEV_TRY(hipMalloc(&p, bytes ? bytes : 1)); }
+    ScopedBuf() = default;
+    ScopedBuf(const ScopedBuf&) = delete;
+    ScopedBuf& operator=(const ScopedBuf&) = delete;
+};
+
+inline unsigned blocks(size_t total, unsigned per = 256) { return (unsigned)((total + per - 1) / per); }
+inline size_t next_pow2(size_t v) {
+    size_t n = 1;
+    while (n < v) n <<= 1;
+    return n;
+}
+
+// the status of `body`, which returns nothing (0) or a status of its own: a DevErr it throws becomes dev_code, anything
+// else -2.  The whole frame of the calls that have no handle (groupmul.hip: a stream per call).
+template <class F>
+int status_of(F&& body) {
+    try {
+        if constexpr (std::is_void_v<decltype(body())>) {
+            body();
+            return 0;
+        } else {
+            return body();
+        }
+    } catch (const DevErr& e) {
+        return dev_code(e.e);
+    } catch (...) {
+        return -2;
+    }
+}
+
+// a call into code that throws types of its own (msm_enqueue: HipErr): whatever it throws leaves as a DevErr, so the
+// call returns dev_code(hipErrorUnknown) = -1099
+template <class F>
+void foreign(F&& f) {
+    try {
+        f();
+    } catch (const DevErr&) {
+        throw;
+    } catch (...) {
+        throw DevErr{hipErrorUnknown};
+    }
+}
+
+// one call on a handle (anything with `mu`, `device` and `st`): its lock, its GPU, everything `body` enqueues, one
+// synchronisation; the status as status_of gives it
+template <class Ctx, class F>
+int run_call(Ctx* c, F&& body) {
+    std::lock_guard<std::mutex> lk(c->mu);
+    return status_of([&]() -> int {
+        DeviceGuard on_device(c->device);
+        DEV_TRY(on_device.err);
+        int rc = 0;
+        try {
+            if constexpr (std::is_void_v<decltype(body())>) body();
+            else rc = body();
+        } catch (...) {
+            (void)hipStreamSynchronize(c->st);  // a copy into the caller's buffer may be in flight
+            throw;
+        }
+        DEV_TRY(hipStreamSynchronize(c->st));
+        return rc;
+    });
+}
+
+// the creation of a handle that lives on the device of its NTT handle: `init` fills the new Ctx with that device
+// current.  When `init` throws: NULL with *err = dev_code for a DevErr and -4 for anything else, the Ctx that did not
+// make it deleted with its device current.
+template <class Ctx, class F>
+Ctx* create_handle(int ntt_device, int* err, F&& init) {
+    Ctx* c = nullptr;
+    try {
+        c = new Ctx();
+        DeviceGuard on_device(ntt_device);
+        DEV_TRY(on_device.err);
+        c->device = ntt_device;
+        init(c);
+        return c;
+    } catch (const DevErr& e) {
+        *err = dev_code(e.e);
+    } catch (...) {
+        *err = -4;
+    }
+    DeviceGuard on_device(ntt_device);
+    delete c;
+    return nullptr;
+}
+
+}  // namespace kzgamd

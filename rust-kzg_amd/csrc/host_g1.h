@@ -5,6 +5,8 @@
 #include <stdint.h>
 #include <string.h>
 
+#include <vector>
+
 #include "../../include/kzg_mi355x.h"
 #include "ff.hip.h"
 #include "host_fp64.h"
@@ -61,19 +63,54 @@ inline bool host_fp_lex_largest(const ff::Fp& plain) {  // plain > (p-1)/2
     return borrow != 0;
 }
 
+// blst_p1_to_affine: the affine coordinates of a Jacobian point, Montgomery form.  Returns "is the identity", and then
+// leaves x and y alone.
+inline bool host_p1_to_affine(const blst_p1* p, ff::Fp& x, ff::Fp& y) {
+    const ff::Fp* P = reinterpret_cast<const ff::Fp*>(p);
+    if (P[2].is_zero()) return true;
+    const ff::Fp zi = ff::inverse_bgcd(P[2]), zi2 = hfp::sqr(zi);
+    x = hfp::mul(P[0], zi2);
+    y = hfp::mul(P[1], hfp::mul(zi2, zi));
+    return false;
+}
+
+// The same for the n points point_at(0) ... point_at(n - 1) (const blst_p1* each) with ONE field inversion (Montgomery's
+// trick over the non-zero Z): aff[2 i], aff[2 i + 1] = x, y of point i — blst_p1_affine[n] — the identity as (0, 0),
+// blst's affine infinity.
+template <class PointAt>
+void host_p1_to_affine_batch(ff::Fp* aff, size_t n, PointAt&& point_at) {
+    std::vector<ff::Fp> pre(n);
+    ff::Fp run = ff::Fp::one();
+    for (size_t i = 0; i < n; ++i) {
+        const ff::Fp* P = reinterpret_cast<const ff::Fp*>(point_at(i));
+        pre[i] = run;
+        if (!P[2].is_zero()) run = hfp::mul(run, P[2]);
+    }
+    ff::Fp inv = ff::inverse_bgcd(run);
+    for (size_t i = n; i-- > 0;) {
+        const ff::Fp* P = reinterpret_cast<const ff::Fp*>(point_at(i));
+        if (P[2].is_zero()) {
+            aff[2 * i] = aff[2 * i + 1] = ff::Fp::zero();
+            continue;
+        }
+        const ff::Fp zi = hfp::mul(inv, pre[i]), zi2 = hfp::sqr(zi);
+        inv = hfp::mul(inv, P[2]);
+        aff[2 * i] = hfp::mul(P[0], zi2);
+        aff[2 * i + 1] = hfp::mul(P[1], hfp::mul(zi2, zi));
+    }
+}
+
 // blst_p1_compress
 inline void host_p1_compress(uint8_t out[48], const blst_p1* p) {
-    const ff::Fp* P = reinterpret_cast<const ff::Fp*>(p);
-    if (P[2].is_zero()) {
+    ff::Fp x, y;
+    if (host_p1_to_affine(p, x, y)) {
         memset(out, 0, 48);
         out[0] = 0xc0;
         return;
     }
-    ff::Fp zi = ff::inverse_bgcd(P[2]), zi2 = hfp::sqr(zi);
-    ff::Fp x = hfp::from_mont(hfp::mul(P[0], zi2)), y = hfp::from_mont(hfp::mul(P[1], hfp::mul(zi2, zi)));
-    host_fp_to_be48(out, x);
+    host_fp_to_be48(out, hfp::from_mont(x));
     out[0] |= 0x80;
-    if (host_fp_lex_largest(y)) out[0] |= 0x20;
+    if (host_fp_lex_largest(hfp::from_mont(y))) out[0] |= 0x20;
 }
 
 // blst_p1_compress of n Jacobian points with ONE field inversion (Montgomery's trick over the non-zero Z): the small

@@ -58,7 +58,9 @@
 #include "frscan.hip.h"
 #include "g1_28.hip.h"
 #include "g1_io.hip.h"
+#include "host_call.h"
 #include "host_fp64.h"
+#include "host_g1.h"
 #include "host_pairing.h"
 #include "msm_internal.h"
 #include "glv.hip.h"
@@ -70,6 +72,9 @@ using ff::Fr;
 using ff::u32;
 using g1::AffPt;
 using g1::Xyzz;
+using kzgamd::blocks;
+using kzgamd::DevBuf;
+using kzgamd::DevErr;
 
 namespace {
 
@@ -355,37 +360,6 @@ __global__ void __launch_bounds__(256) k_kzg_batch_fold(Fr* __restrict__ agg, co
 // host loop in tools/time_pairing_batch.py (profiles/pairing_batch_time.jsonl, NOTES 33)
 constexpr size_t PAIRING_GPU_MIN_DEFAULT = 4;
 
-struct KzErr {
-    hipError_t e;
-};
-#define KZ_TRY(x)                              \
-    do {                                       \
-        hipError_t _e = (x);                   \
-        if (_e != hipSuccess) throw KzErr{_e}; \
-    } while (0)
-
-struct DevBuf {
-    void* p = nullptr;
-    size_t cap = 0;
-    void ensure(size_t bytes) {
-        if (bytes <= cap) return;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-        KZ_TRY(hipMalloc(&p, bytes));
-        cap = bytes;
-    }
-    void drop() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-    }
-    template <class T>
-    T* as() const {
-        return (T*)p;
-    }
-};
-
 struct KzgCtx {
     NttCtx* ntt = nullptr;
     int device = 0;
@@ -420,42 +394,12 @@ struct KzgCtx {
     }
 };
 
-inline unsigned blocks(size_t total, unsigned per = 256) { return (unsigned)((total + per - 1) / per); }
-
 // nbatch MSMs of npoints scalars (Montgomery, stride npoints) over the first setup points, Jacobian out, on the stream
 void msm_on_stream(KzgCtx* kz, void* d_out, const void* d_scalars, size_t npoints, size_t nbatch) {
-    kzgamd::msm_lock(kz->msm);
-    try {
+    kzgamd::foreign([&] {
+        kzgamd::MsmLock locked(kz->msm);
         kzgamd::msm_enqueue(kz->msm, d_out, d_scalars, npoints, nbatch, 1, kz->st, kzgamd::OUT_JACOBIAN);
-    } catch (...) {
-        kzgamd::msm_unlock(kz->msm);
-        throw KzErr{hipErrorUnknown};
-    }
-    kzgamd::msm_unlock(kz->msm);
-}
-
-// the Jacobian setup points as blst affine points (Montgomery's trick over the Z coordinates; the identity as (0, 0))
-std::vector<ff::Fp> to_affine(const blst_p1* pts, size_t total) {
-    const ff::Fp* jac = reinterpret_cast<const ff::Fp*>(pts);
-    std::vector<ff::Fp> aff(2 * total), pre(total);
-    ff::Fp run = ff::Fp::one();
-    for (size_t i = 0; i < total; ++i) {
-        pre[i] = run;
-        if (!jac[3 * i + 2].is_zero()) run = hfp::mul(run, jac[3 * i + 2]);
-    }
-    ff::Fp inv = ff::inverse_bgcd(run);
-    for (size_t i = total; i-- > 0;) {
-        const ff::Fp* P = &jac[3 * i];
-        if (P[2].is_zero()) {
-            aff[2 * i] = aff[2 * i + 1] = ff::Fp::zero();
-            continue;
-        }
-        const ff::Fp zi = hfp::mul(inv, pre[i]), zi2 = hfp::sqr(zi);
-        inv = hfp::mul(inv, P[2]);
-        aff[2 * i] = hfp::mul(P[0], zi2);
-        aff[2 * i + 1] = hfp::mul(P[1], hfp::mul(zi2, zi));
-    }
-    return aff;
+    });
 }
 
 // the quotients and remainders of the pairs [pair0, pair0 + npairs) into kz->q (stride len - n) and kz->r (stride n)
@@ -489,41 +433,7 @@ void enqueue_quotients(KzgCtx* kz, size_t len, size_t n, size_t nx, size_t pair0
         }
         hipLaunchKernelGGL(k_kzg_chunk<true>, dim3(blocks(threads)), dim3(256), 0, kz->st, q, r, sums, local, p, pw, s);
     }
-    KZ_TRY(hipGetLastError());
-}
-
-// "pairing_gpu_min=<v>" out of a "key=value;key=value" tuning string (separators as config.h takes them): *value is set
-// when the key is there, *rest is the string without it; false when its value is not a number in -1 ... 2^20
-bool take_pairing_gpu_min(const char* str, long* value, std::string* rest) {
-    static const char key[] = "pairing_gpu_min";
-    auto is_sep = [](char c) { return c == ';' || c == ',' || c == ' ' || c == '\t' || c == '\n'; };
-    const char* p = str;
-    while (*p) {
-        while (*p && is_sep(*p)) ++p;
-        const char* e = p;
-        while (*e && !is_sep(*e)) ++e;
-        if (e == p) break;
-        if ((size_t)(e - p) > sizeof key - 1 && !strncmp(p, key, sizeof key - 1) && p[sizeof key - 1] == '=') {
-            char* end = nullptr;
-            const long v = strtol(p + sizeof key, &end, 10);
-            if (end != e || end == p + sizeof key || v < -1 || v > (1 << 20)) return false;
-            *value = v;
-        } else {
-            if (!rest->empty()) *rest += ';';
-            rest->append(p, e);
-        }
-        p = e;
-    }
-    return true;
-}
-
-bool g1_affine(const blst_p1* p, ff::Fp& x, ff::Fp& y) {  // returns "is the identity"
-    const ff::Fp* P = reinterpret_cast<const ff::Fp*>(p);
-    if (P[2].is_zero()) return true;
-    const ff::Fp zi = ff::inverse_bgcd(P[2]), zi2 = hfp::sqr(zi);
-    x = hfp::mul(P[0], zi2);
-    y = hfp::mul(P[1], hfp::mul(zi2, zi));
-    return false;
+    DEV_TRY(hipGetLastError());
 }
 
 }  // namespace
@@ -544,11 +454,11 @@ extern "C" void* kzgamd_kzg_new(void* vntt, const blst_p1* g1_monomial, size_t n
     }
     // pairing_gpu_min is a key of this handle type alone (as fk20_table is of kzgamd_fk20_new): it is taken out of
     // cfg->tuning here, the rest goes to the library's table of keys (config.h) as for every other handle
-    long gpu_min = -1;
+    long long gpu_min = -1;
     KzgAmdConfig local;
     std::string rest, msg;
     if (cfg && cfg->struct_size >= offsetof(KzgAmdConfig, tuning) + sizeof(cfg->tuning) && cfg->tuning) {
-        if (!take_pairing_gpu_min(cfg->tuning, &gpu_min, &rest)) {
+        if (!kzgamd::take_key(cfg->tuning, "pairing_gpu_min", -1, 1 << 20, &gpu_min, &rest)) {
             fprintf(stderr, "kzg_mi355x: kzgamd_kzg_new: tuning: 'pairing_gpu_min' takes -1 ... 1048576\n");
             *err = -2;
             return nullptr;
@@ -564,33 +474,19 @@ extern "C" void* kzgamd_kzg_new(void* vntt, const blst_p1* g1_monomial, size_t n
         return nullptr;
     }
     opt.device = ntt->device;  // the handle lives where its NTT handle lives
-    auto* kz = new KzgCtx();
-    try {
-        kzgamd::DeviceGuard on_device(ntt->device);
-        KZ_TRY(on_device.err);
+    return kzgamd::create_handle<KzgCtx>(ntt->device, err, [&](KzgCtx* kz) {
         kz->ntt = ntt;
-        kz->device = ntt->device;
         kz->opt = opt;
         kz->pairing_gpu_min = gpu_min < 0 ? PAIRING_GPU_MIN_DEFAULT : (size_t)gpu_min;
         kz->num_g1 = num_g1;
         kz->num_g2 = g2_monomial ? num_g2 : 0;
         kz->g2.resize(kz->num_g2);
         if (kz->num_g2) memcpy(kz->g2.data(), g2_monomial, kz->num_g2 * sizeof(blst_p2));
-        KZ_TRY(hipStreamCreateWithFlags(&kz->st, hipStreamNonBlocking));
-        const std::vector<ff::Fp> aff = to_affine(g1_monomial, num_g1);
+        DEV_TRY(hipStreamCreateWithFlags(&kz->st, hipStreamNonBlocking));
+        std::vector<ff::Fp> aff(2 * num_g1);  // the setup points as blst affine points
+        kzgamd::host_p1_to_affine_batch(aff.data(), num_g1, [&](size_t i) { return &g1_monomial[i]; });
         kz->msm = kzgamd::msm_create(aff.data(), num_g1, false, true, false, kzgamd::G1_CHECK, &opt);
-    } catch (const KzErr& e) {
-        *err = -(int)e.e - 100;
-        kzgamd::DeviceGuard on_device(ntt->device);
-        delete kz;
-        return nullptr;
-    } catch (...) {
-        *err = -4;
-        kzgamd::DeviceGuard on_device(ntt->device);
-        delete kz;
-        return nullptr;
-    }
-    return kz;
+    });
 }
 
 extern "C" void kzgamd_kzg_free(void* vkz) {
@@ -620,28 +516,13 @@ extern "C" int kzgamd_kzg_commit(void* vkz, blst_p1* out, const blst_fr* polys, 
         memset(out, 0, npoly * sizeof(blst_p1));
         return 0;
     }
-    std::lock_guard<std::mutex> lk(kz->mu);
-    int rc = 0;
-    try {
-        kzgamd::DeviceGuard on_device(kz->device);
-        KZ_TRY(on_device.err);
+    return kzgamd::run_call(kz, [&] {
         kz->polys.ensure(npoly * len * sizeof(Fr));
         kz->out.ensure(npoly * sizeof(blst_p1));
-        try {
-            KZ_TRY(hipMemcpyAsync(kz->polys.p, polys, npoly * len * sizeof(Fr), hipMemcpyHostToDevice, kz->st));
-            msm_on_stream(kz, kz->out.p, kz->polys.p, len, npoly);
-            KZ_TRY(hipMemcpyAsync(out, kz->out.p, npoly * sizeof(blst_p1), hipMemcpyDeviceToHost, kz->st));
-        } catch (...) {
-            (void)hipStreamSynchronize(kz->st);  // a copy into the caller's buffer may be in flight
-            throw;
-        }
-        KZ_TRY(hipStreamSynchronize(kz->st));
-    } catch (const KzErr& e) {
-        rc = -(int)e.e - 100;
-    } catch (...) {
-        rc = -2;
-    }
-    return rc;
+        DEV_TRY(hipMemcpyAsync(kz->polys.p, polys, npoly * len * sizeof(Fr), hipMemcpyHostToDevice, kz->st));
+        msm_on_stream(kz, kz->out.p, kz->polys.p, len, npoly);
+        DEV_TRY(hipMemcpyAsync(out, kz->out.p, npoly * sizeof(blst_p1), hipMemcpyDeviceToHost, kz->st));
+    });
 }
 
 extern "C" int kzgamd_kzg_open(void* vkz, blst_p1* proofs, blst_fr* ys, const blst_fr* polys, size_t len, size_t npoly,
@@ -656,15 +537,11 @@ extern "C" int kzgamd_kzg_open(void* vkz, blst_p1* proofs, blst_fr* ys, const bl
     const size_t npairs = npoly * nx;
     if (npairs == 0) return 0;
     if (!proofs || !polys || !xs) return -1;
-    std::lock_guard<std::mutex> lk(kz->mu);
-    int rc = 0;
-    try {
-        kzgamd::DeviceGuard on_device(kz->device);
-        KZ_TRY(on_device.err);
+    return kzgamd::run_call(kz, [&] {
         // the workspace of a pass (quotients, remainders, the MSM's digits beside them) stays within a share of the free
         // HBM: a larger call runs in slices of pairs
         size_t free_b = 0, total_b = 0;
-        KZ_TRY(hipMemGetInfo(&free_b, &total_b));
+        DEV_TRY(hipMemGetInfo(&free_b, &total_b));
         const size_t per_pair = (len + 2 * n) * sizeof(Fr) + sizeof(blst_p1);
         size_t per = (free_b + kz->q.cap + kz->r.cap + kz->r2.cap) / 8 / per_pair;
         if (per == 0) per = 1;
@@ -678,48 +555,37 @@ extern "C" int kzgamd_kzg_open(void* vkz, blst_p1* proofs, blst_fr* ys, const bl
         if (ys && n > 1) kz->r2.ensure(per * n * sizeof(Fr));
         kz->out.ensure(per * sizeof(blst_p1));
         hipStream_t st = kz->st;
-        try {
-            KZ_TRY(hipMemcpyAsync(kz->polys.p, polys, npoly * len * sizeof(Fr), hipMemcpyHostToDevice, st));
-            KZ_TRY(hipMemcpyAsync(kz->xs.p, xs, nx * sizeof(Fr), hipMemcpyHostToDevice, st));
-            hipLaunchKernelGGL(k_kzg_pows, dim3(blocks(nx, 64)), dim3(64), 0, st, kz->pw.as<Fr>(), kz->xs.as<Fr>(), n, nx);
-            for (size_t done = 0; done < npairs; done += per) {
-                const size_t cnt = npairs - done < per ? npairs - done : per;
-                if (L == 0) {
-                    // len <= n: the reference's zero-length quotient (poly.rs:167-170, 226-229); r = p, zero-extended
-                    KZ_TRY(hipMemsetAsync(kz->out.p, 0, cnt * sizeof(blst_p1), st));
-                    if (ys) {
-                        KZ_TRY(hipMemsetAsync(kz->r.p, 0, cnt * n * sizeof(Fr), st));
-                        for (size_t i = 0; i < cnt; ++i)
-                            KZ_TRY(hipMemcpyAsync(kz->r.as<Fr>() + i * n, kz->polys.as<Fr>() + (done + i) / nx * len, len * sizeof(Fr),
-                                                  hipMemcpyDeviceToDevice, st));
-                    }
-                } else {
-                    enqueue_quotients(kz, len, n, nx, done, cnt);
-                    msm_on_stream(kz, kz->out.p, kz->q.p, L, cnt);
+        DEV_TRY(hipMemcpyAsync(kz->polys.p, polys, npoly * len * sizeof(Fr), hipMemcpyHostToDevice, st));
+        DEV_TRY(hipMemcpyAsync(kz->xs.p, xs, nx * sizeof(Fr), hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(k_kzg_pows, dim3(blocks(nx, 64)), dim3(64), 0, st, kz->pw.as<Fr>(), kz->xs.as<Fr>(), n, nx);
+        for (size_t done = 0; done < npairs; done += per) {
+            const size_t cnt = npairs - done < per ? npairs - done : per;
+            if (L == 0) {
+                // len <= n: the reference's zero-length quotient (poly.rs:167-170, 226-229); r = p, zero-extended
+                DEV_TRY(hipMemsetAsync(kz->out.p, 0, cnt * sizeof(blst_p1), st));
+                if (ys) {
+                    DEV_TRY(hipMemsetAsync(kz->r.p, 0, cnt * n * sizeof(Fr), st));
+                    for (size_t i = 0; i < cnt; ++i)
+                        DEV_TRY(hipMemcpyAsync(kz->r.as<Fr>() + i * n, kz->polys.as<Fr>() + (done + i) / nx * len, len * sizeof(Fr),
+                                              hipMemcpyDeviceToDevice, st));
                 }
-                KZ_TRY(hipMemcpyAsync(proofs + done, kz->out.p, cnt * sizeof(blst_p1), hipMemcpyDeviceToHost, st));
-                if (!ys) continue;
-                const Fr* vals = kz->r.as<Fr>();
-                if (n > 1) {
-                    hipLaunchKernelGGL(k_kzg_twist, dim3(blocks(cnt * n)), dim3(256), 0, st, kz->r.as<Fr>(), kz->xs.as<Fr>(), n, nx,
-                                       done, cnt * n);
-                    if (kzgamd_ntt_fr_device(kz->ntt, kz->r2.p, kz->r.p, n, cnt, 0, st) != 0) throw KzErr{hipErrorUnknown};
-                    vals = kz->r2.as<Fr>();
-                }
-                KZ_TRY(hipGetLastError());
-                KZ_TRY(hipMemcpyAsync(ys + done * n, vals, cnt * n * sizeof(Fr), hipMemcpyDeviceToHost, st));
+            } else {
+                enqueue_quotients(kz, len, n, nx, done, cnt);
+                msm_on_stream(kz, kz->out.p, kz->q.p, L, cnt);
             }
-        } catch (...) {
-            (void)hipStreamSynchronize(st);  // a copy into the caller's buffer may be in flight
-            throw;
+            DEV_TRY(hipMemcpyAsync(proofs + done, kz->out.p, cnt * sizeof(blst_p1), hipMemcpyDeviceToHost, st));
+            if (!ys) continue;
+            const Fr* vals = kz->r.as<Fr>();
+            if (n > 1) {
+                hipLaunchKernelGGL(k_kzg_twist, dim3(blocks(cnt * n)), dim3(256), 0, st, kz->r.as<Fr>(), kz->xs.as<Fr>(), n, nx,
+                                   done, cnt * n);
+                if (kzgamd_ntt_fr_device(kz->ntt, kz->r2.p, kz->r.p, n, cnt, 0, st) != 0) throw DevErr{hipErrorUnknown};
+                vals = kz->r2.as<Fr>();
+            }
+            DEV_TRY(hipGetLastError());
+            DEV_TRY(hipMemcpyAsync(ys + done * n, vals, cnt * n * sizeof(Fr), hipMemcpyDeviceToHost, st));
         }
-        KZ_TRY(hipStreamSynchronize(st));
-    } catch (const KzErr& e) {
-        rc = -(int)e.e - 100;
-    } catch (...) {
-        rc = -2;
-    }
-    return rc;
+    });
 }
 
 namespace {
@@ -748,19 +614,19 @@ bool check_each_gpu(KzgCtx* kz, std::vector<uint8_t>& verdict, std::vector<uint8
     kz->gok.ensure(count);
     ff::Fp* jac = kz->gjac.as<ff::Fp>();  // [proofs | commitments]
     int* stat = kz->stat.as<int>();
-    KZ_TRY(hipMemcpyAsync(jac, proofs, count * sizeof(blst_p1), hipMemcpyHostToDevice, st));
-    KZ_TRY(hipMemcpyAsync(jac + 3 * count, commitments, count * sizeof(blst_p1), hipMemcpyHostToDevice, st));
-    KZ_TRY(hipMemsetAsync(stat, 0, 2 * sizeof(int), st));
+    DEV_TRY(hipMemcpyAsync(jac, proofs, count * sizeof(blst_p1), hipMemcpyHostToDevice, st));
+    DEV_TRY(hipMemcpyAsync(jac + 3 * count, commitments, count * sizeof(blst_p1), hipMemcpyHostToDevice, st));
+    DEV_TRY(hipMemsetAsync(stat, 0, 2 * sizeof(int), st));
     hipLaunchKernelGGL(k_kzg_points, dim3(blocks(blocks(np, PT_CHUNK), 64)), dim3(64), 0, st, kz->aff.as<AffPt>(), (const ff::Fp*)jac,
                        kz->pref.as<fp28::Fe>(), np, stat);
     hipLaunchKernelGGL(k_kzg_in_g1_each, dim3(blocks(np, 64)), dim3(64), 0, st, (const AffPt*)kz->aff.as<AffPt>(), np,
                        kz->gflags.as<uint8_t>());
-    KZ_TRY(hipGetLastError());
+    DEV_TRY(hipGetLastError());
     int hstat[2] = {1, 1};
     std::vector<uint8_t> flags(np);
-    KZ_TRY(hipMemcpyAsync(hstat, stat, 2 * sizeof(int), hipMemcpyDeviceToHost, st));
-    KZ_TRY(hipMemcpyAsync(flags.data(), kz->gflags.p, np, hipMemcpyDeviceToHost, st));
-    KZ_TRY(hipStreamSynchronize(st));
+    DEV_TRY(hipMemcpyAsync(hstat, stat, 2 * sizeof(int), hipMemcpyDeviceToHost, st));
+    DEV_TRY(hipMemcpyAsync(flags.data(), kz->gflags.p, np, hipMemcpyDeviceToHost, st));
+    DEV_TRY(hipStreamSynchronize(st));
     if (hstat[0]) return false;
     to_host.assign(count, 0);
     std::vector<kzgamd::RootSplit> split(count);
@@ -792,7 +658,7 @@ bool check_each_gpu(KzgCtx* kz, std::vector<uint8_t>& verdict, std::vector<uint8
         const kzgamd::pairing::G2Jac gen = kzgamd::pairing::g2_generator();
         blst_p2 g;
         memcpy(&g, &gen, sizeof g);
-        KZ_TRY(pg::device_table(&kz->dgen, &g));
+        DEV_TRY(pg::device_table(&kz->dgen, &g));
         kz->have_dgen = true;
     }
     auto it = kz->dlines.find(n);
@@ -800,19 +666,19 @@ bool check_each_gpu(KzgCtx* kz, std::vector<uint8_t>& verdict, std::vector<uint8
         blst_p2 q;
         memcpy(&q, &kz->g2[n], sizeof q);
         pg::DeviceTable tab;
-        KZ_TRY(pg::device_table(&tab, &q));
+        DEV_TRY(pg::device_table(&tab, &q));
         it = kz->dlines.emplace(n, tab).first;
     }
-    KZ_TRY(hipMemcpyAsync(kz->gsplit.p, split.data(), count * sizeof(kzgamd::RootSplit), hipMemcpyHostToDevice, st));
+    DEV_TRY(hipMemcpyAsync(kz->gsplit.p, split.data(), count * sizeof(kzgamd::RootSplit), hipMemcpyHostToDevice, st));
     kzgamd::g1_jacobian_to_xyzz(kz->gxyzz.p, jac, count, st);
     kzgamd::g1_varmul_sum_device(kz->ntt, kz->gprod.p, nullptr, kz->gtab.p, kz->gxyzz.p, count, (const kzgamd::RootSplit*)kz->gsplit.p, count, 1,
                                  st);
     hipLaunchKernelGGL(k_kzg_g1_add_xyzz, dim3(blocks(count, 64)), dim3(64), 0, st, kz->gsum.as<ff::Fp>(), dif, (const Xyzz*)kz->gprod.p,
                        count);
-    KZ_TRY(hipGetLastError());
-    KZ_TRY(pg::check_on_stream(kz->gok.as<uint8_t>(), (const blst_p1*)kz->gsum.p, (const blst_p1*)jac, kz->dgen, it->second, count, st));
-    KZ_TRY(hipMemcpyAsync(verdict.data(), kz->gok.p, count, hipMemcpyDeviceToHost, st));
-    KZ_TRY(hipStreamSynchronize(st));
+    DEV_TRY(hipGetLastError());
+    DEV_TRY(pg::check_on_stream(kz->gok.as<uint8_t>(), (const blst_p1*)kz->gsum.p, (const blst_p1*)jac, kz->dgen, it->second, count, st));
+    DEV_TRY(hipMemcpyAsync(verdict.data(), kz->gok.p, count, hipMemcpyDeviceToHost, st));
+    DEV_TRY(hipStreamSynchronize(st));
     return true;
 }
 
@@ -835,50 +701,34 @@ int check_each(KzgCtx* kz, bool* ok, const blst_p1* commitments, const blst_p1* 
     // the GPU form: verdict bytes of the tuples it took, and which tuples stay with the host loop
     bool gpu = kz->pairing_gpu_min != 0 && count >= kz->pairing_gpu_min;
     std::vector<uint8_t> gverdict, to_host;
-    int rc = 0;
-    {
-        std::lock_guard<std::mutex> lk(kz->mu);
-        try {
-            kzgamd::DeviceGuard on_device(kz->device);
-            KZ_TRY(on_device.err);
-            kz->r.ensure(count * n * sizeof(Fr));
-            kz->r2.ensure(count * n * sizeof(Fr));
-            kz->xs.ensure(count * sizeof(Fr));
-            kz->out.ensure(count * sizeof(blst_p1));
-            kz->pts.ensure(2 * count * sizeof(blst_p1));
-            hipStream_t st = kz->st;
-            ff::Fp* com = kz->pts.as<ff::Fp>();
-            ff::Fp* dif = com + 3 * count;
-            try {
-                KZ_TRY(hipMemcpyAsync(kz->r.p, ys, count * n * sizeof(Fr), hipMemcpyHostToDevice, st));
-                KZ_TRY(hipMemcpyAsync(com, commitments, count * sizeof(blst_p1), hipMemcpyHostToDevice, st));
-                const Fr* interp = kz->r.as<Fr>();
-                if (n > 1) {
-                    // interp = ifft(ys); interp[i] *= x^-i (kzg_settings.rs:248-258)
-                    KZ_TRY(hipMemcpyAsync(kz->xs.p, xs, count * sizeof(Fr), hipMemcpyHostToDevice, st));
-                    if (kzgamd_ntt_fr_device(kz->ntt, kz->r2.p, kz->r.p, n, count, 1, st) != 0) throw KzErr{hipErrorUnknown};
-                    hipLaunchKernelGGL(k_kzg_invert, dim3(blocks(count, 64)), dim3(64), 0, st, kz->xs.as<Fr>(), count);
-                    hipLaunchKernelGGL(k_kzg_unscale, dim3(blocks(count * n)), dim3(256), 0, st, kz->r2.as<Fr>(), kz->xs.as<Fr>(), n,
-                                       count * n);
-                    interp = kz->r2.as<Fr>();
-                }
-                msm_on_stream(kz, kz->out.p, interp, n, count);
-                hipLaunchKernelGGL(k_kzg_g1_sub, dim3(blocks(count, 64)), dim3(64), 0, st, dif, (const ff::Fp*)com,
-                                   (const ff::Fp*)kz->out.p, count);
-                KZ_TRY(hipGetLastError());
-                KZ_TRY(hipMemcpyAsync(lhs.data(), dif, count * sizeof(blst_p1), hipMemcpyDeviceToHost, st));
-                if (gpu) gpu = check_each_gpu(kz, gverdict, to_host, (const ff::Fp*)dif, proofs, commitments, hx, n, count);
-            } catch (...) {
-                (void)hipStreamSynchronize(st);
-                throw;
-            }
-            KZ_TRY(hipStreamSynchronize(st));
-        } catch (const KzErr& e) {
-            rc = -(int)e.e - 100;
-        } catch (...) {
-            rc = -2;
+    const int rc = kzgamd::run_call(kz, [&] {
+        kz->r.ensure(count * n * sizeof(Fr));
+        kz->r2.ensure(count * n * sizeof(Fr));
+        kz->xs.ensure(count * sizeof(Fr));
+        kz->out.ensure(count * sizeof(blst_p1));
+        kz->pts.ensure(2 * count * sizeof(blst_p1));
+        hipStream_t st = kz->st;
+        ff::Fp* com = kz->pts.as<ff::Fp>();
+        ff::Fp* dif = com + 3 * count;
+        DEV_TRY(hipMemcpyAsync(kz->r.p, ys, count * n * sizeof(Fr), hipMemcpyHostToDevice, st));
+        DEV_TRY(hipMemcpyAsync(com, commitments, count * sizeof(blst_p1), hipMemcpyHostToDevice, st));
+        const Fr* interp = kz->r.as<Fr>();
+        if (n > 1) {
+            // interp = ifft(ys); interp[i] *= x^-i (kzg_settings.rs:248-258)
+            DEV_TRY(hipMemcpyAsync(kz->xs.p, xs, count * sizeof(Fr), hipMemcpyHostToDevice, st));
+            if (kzgamd_ntt_fr_device(kz->ntt, kz->r2.p, kz->r.p, n, count, 1, st) != 0) throw DevErr{hipErrorUnknown};
+            hipLaunchKernelGGL(k_kzg_invert, dim3(blocks(count, 64)), dim3(64), 0, st, kz->xs.as<Fr>(), count);
+            hipLaunchKernelGGL(k_kzg_unscale, dim3(blocks(count * n)), dim3(256), 0, st, kz->r2.as<Fr>(), kz->xs.as<Fr>(), n,
+                               count * n);
+            interp = kz->r2.as<Fr>();
         }
-    }
+        msm_on_stream(kz, kz->out.p, interp, n, count);
+        hipLaunchKernelGGL(k_kzg_g1_sub, dim3(blocks(count, 64)), dim3(64), 0, st, dif, (const ff::Fp*)com,
+                           (const ff::Fp*)kz->out.p, count);
+        DEV_TRY(hipGetLastError());
+        DEV_TRY(hipMemcpyAsync(lhs.data(), dif, count * sizeof(blst_p1), hipMemcpyDeviceToHost, st));
+        if (gpu) gpu = check_each_gpu(kz, gverdict, to_host, (const ff::Fp*)dif, proofs, commitments, hx, n, count);
+    });
     if (rc) return rc;
     // the G2 side and the pairings, on the host like the reference's:  e(lhs, G2) == e(proof, [s^n]G2 - [x^n]G2)
     const pr::G2Jac gen = pr::g2_generator();
@@ -895,8 +745,8 @@ int check_each(KzgCtx* kz, bool* ok, const blst_p1* commitments, const blst_p1* 
         const pr::LineTable trhs = pr::g2_line_table(pr::g2_to_affine(rhs2));
         ff::Fp px[2], py[2];
         bool inf[2];
-        inf[0] = g1_affine(&lhs[i], px[0], py[0]);
-        inf[1] = g1_affine(&proofs[i], px[1], py[1]);
+        inf[0] = kzgamd::host_p1_to_affine(&lhs[i], px[0], py[0]);
+        inf[1] = kzgamd::host_p1_to_affine(&proofs[i], px[1], py[1]);
         if (!inf[0]) py[0] = hfp::neg(py[0]);  // e(-lhs, G2) e(proof, rhs2) == 1
         const pr::LineTable* tabs[2] = {tgen.get(), &trhs};
         ok[i] = pr::f12_is_one(pr::final_exponentiation(pr::miller_loop_multi(tabs, px, py, inf, 2)));
@@ -955,11 +805,7 @@ int batch_g1(KzgCtx* kz, blst_p1 lp[2], const blst_p1* commitments, const blst_p
              size_t n, size_t count, const Fr& r, std::shared_ptr<const kzgamd::pairing::LineTable>* tab_n) {
     namespace pr = kzgamd::pairing;
     const size_t np = 2 * count, nblocks = blocks(count, AGG_WAVE);
-    int rc = 0;
-    std::lock_guard<std::mutex> lk(kz->mu);
-    try {
-        kzgamd::DeviceGuard on_device(kz->device);
-        KZ_TRY(on_device.err);
+    return kzgamd::run_call(kz, [&]() -> int {
         kz->pts.ensure(np * sizeof(blst_p1));
         kz->aff.ensure(np * sizeof(AffPt));
         kz->pref.ensure(np * sizeof(fp28::Fe));
@@ -980,69 +826,55 @@ int batch_g1(KzgCtx* kz, blst_p1 lp[2], const blst_p1* commitments, const blst_p
         Fr* dx = kz->xs.as<Fr>();
         ff::Fp* out = kz->out.as<ff::Fp>();
         int hstat[2] = {1, 1};
-        try {
-            // points: [proofs | commitments] -> affine slots, on the curve, in G1
-            KZ_TRY(hipMemcpyAsync(jac, proofs, count * sizeof(blst_p1), hipMemcpyHostToDevice, st));
-            KZ_TRY(hipMemcpyAsync(jac + 3 * count, commitments, count * sizeof(blst_p1), hipMemcpyHostToDevice, st));
-            KZ_TRY(hipMemsetAsync(stat, 0, 2 * sizeof(int), st));
-            hipLaunchKernelGGL(k_kzg_points, dim3(blocks(blocks(np, PT_CHUNK), 64)), dim3(64), 0, st, aff, (const ff::Fp*)jac,
-                               kz->pref.as<fp28::Fe>(), np, stat);
-            hipLaunchKernelGGL(k_kzg_in_g1, dim3(blocks(np, 64)), dim3(64), 0, st, (const AffPt*)aff, np, stat);
-            // values: the inverse transforms and x^-1
-            KZ_TRY(hipMemcpyAsync(kz->r.p, ys, count * n * sizeof(Fr), hipMemcpyHostToDevice, st));
-            KZ_TRY(hipMemcpyAsync(dx, xs, count * sizeof(Fr), hipMemcpyHostToDevice, st));
-            const Fr* vals = kz->r.as<Fr>();
-            if (n > 1) {
-                if (kzgamd_ntt_fr_device(kz->ntt, kz->r2.p, kz->r.p, n, count, 1, st) != 0) throw KzErr{hipErrorUnknown};
-                KZ_TRY(hipMemcpyAsync(kz->xinv.p, dx, count * sizeof(Fr), hipMemcpyDeviceToDevice, st));
-                hipLaunchKernelGGL(k_kzg_invert, dim3(blocks(count, 64)), dim3(64), 0, st, kz->xinv.as<Fr>(), count);
-                vals = kz->r2.as<Fr>();
-            }
-            KZ_TRY(hipGetLastError());
-            KZ_TRY(hipMemcpyAsync(hstat, stat, 2 * sizeof(int), hipMemcpyDeviceToHost, st));
-            KZ_TRY(hipStreamSynchronize(st));
-            if (hstat[0] || hstat[1]) return 7;
-            // the checked points become the bases of the variable-base handle (all in G1: the GLV split holds)
-            if (!kz->vmsm) kz->vmsm = kzgamd::msm_create(aff, np, true, false, true, kzgamd::G1_TRUSTED, &kz->opt);
-            else kzgamd::msm_reset_points(kz->vmsm, aff, np);
-            KZ_TRY(hipMemcpyAsync(dx + count, &r, sizeof(Fr), hipMemcpyHostToDevice, st));
-            hipLaunchKernelGGL(k_kzg_batch_scalars, dim3(blocks(count, 64)), dim3(64), 0, st, kz->rho.as<Fr>(), kz->rows.as<Fr>(),
-                               (const Fr*)(dx + count), (const Fr*)dx, n, count);
-            Fr* part = nblocks > 1 ? kz->part.as<Fr>() : kz->agg.as<Fr>();
-            hipLaunchKernelGGL(k_kzg_batch_agg, dim3((unsigned)nblocks), dim3(AGG_WAVE), 0, st, part, vals, (const Fr*)kz->rho.as<Fr>(),
-                               n > 1 ? (const Fr*)kz->xinv.as<Fr>() : (const Fr*)nullptr, n, count);
-            if (nblocks > 1)
-                hipLaunchKernelGGL(k_kzg_batch_fold, dim3(blocks(n)), dim3(256), 0, st, kz->agg.as<Fr>(), (const Fr*)part, n, nblocks);
-            KZ_TRY(hipGetLastError());
-            msm_on_stream(kz, out + 9, kz->agg.p, n, 1);  // [A(s)]G
-            kzgamd::msm_lock(kz->vmsm);
-            try {
-                kzgamd::msm_enqueue(kz->vmsm, out + 3, kz->rows.p, np, 2, 1, st, kzgamd::OUT_JACOBIAN);  // P, row L
-            } catch (...) {
-                kzgamd::msm_unlock(kz->vmsm);
-                throw KzErr{hipErrorUnknown};
-            }
-            kzgamd::msm_unlock(kz->vmsm);
-            hipLaunchKernelGGL(k_kzg_g1_sub, dim3(1), dim3(64), 0, st, out, (const ff::Fp*)(out + 6), (const ff::Fp*)(out + 9), (size_t)1);
-            KZ_TRY(hipGetLastError());
-            KZ_TRY(hipMemcpyAsync(lp, out, 2 * sizeof(blst_p1), hipMemcpyDeviceToHost, st));
-        } catch (...) {
-            (void)hipStreamSynchronize(st);
-            throw;
+        // points: [proofs | commitments] -> affine slots, on the curve, in G1
+        DEV_TRY(hipMemcpyAsync(jac, proofs, count * sizeof(blst_p1), hipMemcpyHostToDevice, st));
+        DEV_TRY(hipMemcpyAsync(jac + 3 * count, commitments, count * sizeof(blst_p1), hipMemcpyHostToDevice, st));
+        DEV_TRY(hipMemsetAsync(stat, 0, 2 * sizeof(int), st));
+        hipLaunchKernelGGL(k_kzg_points, dim3(blocks(blocks(np, PT_CHUNK), 64)), dim3(64), 0, st, aff, (const ff::Fp*)jac,
+                           kz->pref.as<fp28::Fe>(), np, stat);
+        hipLaunchKernelGGL(k_kzg_in_g1, dim3(blocks(np, 64)), dim3(64), 0, st, (const AffPt*)aff, np, stat);
+        // values: the inverse transforms and x^-1
+        DEV_TRY(hipMemcpyAsync(kz->r.p, ys, count * n * sizeof(Fr), hipMemcpyHostToDevice, st));
+        DEV_TRY(hipMemcpyAsync(dx, xs, count * sizeof(Fr), hipMemcpyHostToDevice, st));
+        const Fr* vals = kz->r.as<Fr>();
+        if (n > 1) {
+            if (kzgamd_ntt_fr_device(kz->ntt, kz->r2.p, kz->r.p, n, count, 1, st) != 0) throw DevErr{hipErrorUnknown};
+            DEV_TRY(hipMemcpyAsync(kz->xinv.p, dx, count * sizeof(Fr), hipMemcpyDeviceToDevice, st));
+            hipLaunchKernelGGL(k_kzg_invert, dim3(blocks(count, 64)), dim3(64), 0, st, kz->xinv.as<Fr>(), count);
+            vals = kz->r2.as<Fr>();
         }
-        KZ_TRY(hipStreamSynchronize(st));
+        DEV_TRY(hipGetLastError());
+        DEV_TRY(hipMemcpyAsync(hstat, stat, 2 * sizeof(int), hipMemcpyDeviceToHost, st));
+        DEV_TRY(hipStreamSynchronize(st));
+        if (hstat[0] || hstat[1]) return 7;
+        // the checked points become the bases of the variable-base handle (all in G1: the GLV split holds)
+        if (!kz->vmsm) kz->vmsm = kzgamd::msm_create(aff, np, true, false, true, kzgamd::G1_TRUSTED, &kz->opt);
+        else kzgamd::msm_reset_points(kz->vmsm, aff, np);
+        DEV_TRY(hipMemcpyAsync(dx + count, &r, sizeof(Fr), hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(k_kzg_batch_scalars, dim3(blocks(count, 64)), dim3(64), 0, st, kz->rho.as<Fr>(), kz->rows.as<Fr>(),
+                           (const Fr*)(dx + count), (const Fr*)dx, n, count);
+        Fr* part = nblocks > 1 ? kz->part.as<Fr>() : kz->agg.as<Fr>();
+        hipLaunchKernelGGL(k_kzg_batch_agg, dim3((unsigned)nblocks), dim3(AGG_WAVE), 0, st, part, vals, (const Fr*)kz->rho.as<Fr>(),
+                           n > 1 ? (const Fr*)kz->xinv.as<Fr>() : (const Fr*)nullptr, n, count);
+        if (nblocks > 1)
+            hipLaunchKernelGGL(k_kzg_batch_fold, dim3(blocks(n)), dim3(256), 0, st, kz->agg.as<Fr>(), (const Fr*)part, n, nblocks);
+        DEV_TRY(hipGetLastError());
+        msm_on_stream(kz, out + 9, kz->agg.p, n, 1);  // [A(s)]G
+        kzgamd::foreign([&] {
+            kzgamd::MsmLock locked(kz->vmsm);
+            kzgamd::msm_enqueue(kz->vmsm, out + 3, kz->rows.p, np, 2, 1, st, kzgamd::OUT_JACOBIAN);  // P, row L
+        });
+        hipLaunchKernelGGL(k_kzg_g1_sub, dim3(1), dim3(64), 0, st, out, (const ff::Fp*)(out + 6), (const ff::Fp*)(out + 9), (size_t)1);
+        DEV_TRY(hipGetLastError());
+        DEV_TRY(hipMemcpyAsync(lp, out, 2 * sizeof(blst_p1), hipMemcpyDeviceToHost, st));
         if (tab_n) {
             auto it = kz->lines.find(n);
             if (it == kz->lines.end())
                 it = kz->lines.emplace(n, std::make_shared<const pr::LineTable>(pr::g2_line_table(pr::g2_to_affine(kz->g2[n])))).first;
             *tab_n = it->second;
         }
-    } catch (const KzErr& e) {
-        rc = -(int)e.e - 100;
-    } catch (...) {
-        rc = -2;
-    }
-    return rc;
+        return 0;
+    });
 }
 
 }  // namespace
@@ -1096,8 +928,8 @@ extern "C" int kzgamd_kzg_check_batch(void* vkz, bool* ok, bool* ok_each, const 
     // one pairing check, outside the handle's lock:  e(-L, G2) e(P, [s^n]G2) == 1
     ff::Fp px[2], py[2];
     bool inf[2];
-    inf[0] = g1_affine(&lp[0], px[0], py[0]);
-    inf[1] = g1_affine(&lp[1], px[1], py[1]);
+    inf[0] = kzgamd::host_p1_to_affine(&lp[0], px[0], py[0]);
+    inf[1] = kzgamd::host_p1_to_affine(&lp[1], px[1], py[1]);
     if (!inf[0]) py[0] = hfp::neg(py[0]);
     const pr::LineTable* tabs[2] = {tab_gen.get(), tab_n.get()};
     const bool pass = pr::f12_is_one(pr::final_exponentiation(pr::miller_loop_multi(tabs, px, py, inf, 2)));

@@ -38,6 +38,14 @@ int msm_device(MsmContext* ctx);
 void msm_run_host(MsmContext* ctx, void* out, const void* scalars, size_t npoints, size_t nbatch, size_t nseg = 0);
 void msm_lock(MsmContext* ctx);
 void msm_unlock(MsmContext* ctx);
+// the handle's lock for a scope: an enqueue happens under it, and it is released before the caller's next statement
+struct MsmLock {
+    MsmContext* ctx;
+    explicit MsmLock(MsmContext* c) : ctx(c) { msm_lock(ctx); }
+    ~MsmLock() { msm_unlock(ctx); }
+    MsmLock(const MsmLock&) = delete;
+    MsmLock& operator=(const MsmLock&) = delete;
+};
 // per-kernel timing of the last enqueue (events on the launch stream); ms < 0 when disabled
 void msm_set_profile(MsmContext* ctx, bool on);
 int msm_get_profile(MsmContext* ctx, float* accum_ms, float* total_ms);  // number of enqueues averaged

@@ -393,8 +393,8 @@ void upload_plan(NttCtx* ctx, int kind, int T) {
         pd.rd[r][5] = (u32)(pl.rounds[r].part | pl.rounds[r].unit << 1 | pl.rounds[r].twist << 2);
     }
     // tab[..][4] of u16 = {idxA, idxB, lds(idxA), lds(idxB)} is read as uint2 {idxA | idxB << 16, ldsA | ldsB << 16}
-    NTT_TRY(hipMalloc(&pd.d_tab, pl.tab.size() * sizeof(uint16_t)));
-    NTT_TRY(hipMemcpy(pd.d_tab, pl.tab.data(), pl.tab.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
+    DEV_TRY(hipMalloc(&pd.d_tab, pl.tab.size() * sizeof(uint16_t)));
+    DEV_TRY(hipMemcpy(pd.d_tab, pl.tab.data(), pl.tab.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
     ctx->plans[kind * 16 + T] = pd;
 }
 
@@ -473,7 +473,7 @@ void ntt_enqueue(NttCtx* ctx, Fr* d_out, const Fr* d_in, size_t n, size_t nbatch
             s0 += Ts[i];
         }
     }
-    NTT_TRY(hipGetLastError());
+    DEV_TRY(hipGetLastError());
 }
 
 }  // namespace
@@ -500,11 +500,11 @@ void* kzgamd::ntt_create(unsigned scale, const kzgamd::Options& opt) {
     auto* ctx = new NttCtx();
     try {
         int cur_dev = 0;
-        NTT_TRY(hipGetDevice(&cur_dev));
+        DEV_TRY(hipGetDevice(&cur_dev));
         kzgamd::DeviceGuard placed(opt.device >= 0 ? opt.device : cur_dev);  // the caller's device is restored on return
-        NTT_TRY(placed.err);
-        NTT_TRY(hipGetDevice(&ctx->device));
-        NTT_TRY(hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking));
+        DEV_TRY(placed.err);
+        DEV_TRY(hipGetDevice(&ctx->device));
+        DEV_TRY(hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking));
         ctx->scale = scale;
         ctx->W = (size_t)1 << scale;
         ctx->g1_wide_max = (size_t)opt.t[kzgamd::T_G1_WIDE_MAX];
@@ -516,8 +516,8 @@ void* kzgamd::ntt_create(unsigned scale, const kzgamd::Options& opt) {
         // the butterflies multiply with (36 bytes per root instead of 32, ~27 instructions less per butterfly)
         std::vector<Fe> tw(ctx->W + 1);
         for (size_t i = 0; i <= ctx->W; ++i) tw[i] = fr29::unpack(times32(ctx->roots[i]));
-        NTT_TRY(hipMalloc(&ctx->d_roots, (ctx->W + 1) * sizeof(Fe)));
-        NTT_TRY(hipMemcpy(ctx->d_roots, tw.data(), (ctx->W + 1) * sizeof(Fe), hipMemcpyHostToDevice));
+        DEV_TRY(hipMalloc(&ctx->d_roots, (ctx->W + 1) * sizeof(Fe)));
+        DEV_TRY(hipMemcpy(ctx->d_roots, tw.data(), (ctx->W + 1) * sizeof(Fe), hipMemcpyHostToDevice));
         // stage-major copies for the butterfly kernels: [(2^s - 1) + j] = w_{2^(s+1)}^j = roots[j * (W >> (s+1))],
         // s < scale, and the same with the inverse roots (roots[W - idx]); W - 1 entries each
         if (scale > 0) {
@@ -528,10 +528,10 @@ void* kzgamd::ntt_create(unsigned scale, const kzgamd::Options& opt) {
                     sm[((size_t)1 << s) - 1 + j] = tw[idx];
                     smi[((size_t)1 << s) - 1 + j] = tw[ctx->W - idx];
                 }
-            NTT_TRY(hipMalloc(&ctx->d_tw_fwd, ctx->W * sizeof(Fe)));
-            NTT_TRY(hipMalloc(&ctx->d_tw_inv, ctx->W * sizeof(Fe)));
-            NTT_TRY(hipMemcpy(ctx->d_tw_fwd, sm.data(), ctx->W * sizeof(Fe), hipMemcpyHostToDevice));
-            NTT_TRY(hipMemcpy(ctx->d_tw_inv, smi.data(), ctx->W * sizeof(Fe), hipMemcpyHostToDevice));
+            DEV_TRY(hipMalloc(&ctx->d_tw_fwd, ctx->W * sizeof(Fe)));
+            DEV_TRY(hipMalloc(&ctx->d_tw_inv, ctx->W * sizeof(Fe)));
+            DEV_TRY(hipMemcpy(ctx->d_tw_fwd, sm.data(), ctx->W * sizeof(Fe), hipMemcpyHostToDevice));
+            DEV_TRY(hipMemcpy(ctx->d_tw_inv, smi.data(), ctx->W * sizeof(Fe), hipMemcpyHostToDevice));
         }
         // every plan the passes can ask for (35 tables of <= 48 KiB), built once: launches never allocate
         for (int T = 0; T <= nttplan::LOGT; ++T) upload_plan(ctx, KIND_A1, T);
@@ -563,10 +563,10 @@ extern "C" int kzgamd_ntt_fr_device(void* vctx, void* d_out, const void* d_in, s
     if (d_out == d_in) return -3;
     try {
         kzgamd::DeviceGuard on_device(ctx->device);
-        NTT_TRY(on_device.err);
+        DEV_TRY(on_device.err);
         ntt_enqueue(ctx, (Fr*)d_out, (const Fr*)d_in, n, nbatch, inverse != 0, (hipStream_t)stream);
-    } catch (const NttErr& e) {
-        return -(int)e.e - 100;
+    } catch (const kzgamd::DevErr& e) {
+        return kzgamd::dev_code(e.e);
     }
     return 0;
 }
@@ -593,13 +593,13 @@ void run_combined_batch(NttCtx* ctx, NttCtx::CombLane& lane, const std::vector<N
     int rc = 0;
     try {
         kzgamd::DeviceGuard on_device(ctx->device);
-        NTT_TRY(on_device.err);
+        DEV_TRY(on_device.err);
         // each on its own test: an allocation that failed is tried again by the next batch, not taken for made
         const size_t cap = NttCtx::COMB_MAX * NttCtx::COMB_NMAX * sizeof(Fr);
-        if (!lane.st) NTT_TRY(hipStreamCreateWithFlags(&lane.st, hipStreamNonBlocking));
-        if (!lane.d_in) NTT_TRY(hipMalloc(&lane.d_in, cap));
-        if (!lane.d_out) NTT_TRY(hipMalloc(&lane.d_out, cap));
-        if (!lane.d_tmp) NTT_TRY(hipMalloc(&lane.d_tmp, cap));
+        if (!lane.st) DEV_TRY(hipStreamCreateWithFlags(&lane.st, hipStreamNonBlocking));
+        if (!lane.d_in) DEV_TRY(hipMalloc(&lane.d_in, cap));
+        if (!lane.d_out) DEV_TRY(hipMalloc(&lane.d_out, cap));
+        if (!lane.d_tmp) DEV_TRY(hipMalloc(&lane.d_tmp, cap));
         SlotPtrs sp;
         for (size_t j = 0; j < NttCtx::COMB_MAX; ++j) sp.p[j] = j < nb ? (uint4*)batch[j]->slot : nullptr;
         const size_t per = n * 2, total = nb * per;  // 16-byte words per request
@@ -608,11 +608,11 @@ void run_combined_batch(NttCtx* ctx, NttCtx::CombLane& lane, const std::vector<N
         if (kind == 2) das_enqueue(ctx, lane.d_out, lane.d_in, lane.d_tmp, n, nb, lane.st);
         else ntt_enqueue(ctx, lane.d_out, lane.d_in, n, nb, kind == 1, lane.st);
         hipLaunchKernelGGL(k_slots_scatter, dim3(grid), dim3(256), 0, lane.st, sp, (const uint4*)lane.d_out, per, nb);
-        NTT_TRY(hipGetLastError());
-        NTT_TRY(hipStreamSynchronize(lane.st));
-    } catch (const NttErr& e) {
+        DEV_TRY(hipGetLastError());
+        DEV_TRY(hipStreamSynchronize(lane.st));
+    } catch (const kzgamd::DevErr& e) {
         if (lane.st) (void)hipStreamSynchronize(lane.st);  // nothing may still read or write the callers' slots
-        rc = -(int)e.e - 100;
+        rc = kzgamd::dev_code(e.e);
     }
     for (auto* r : batch) r->rc = rc;
 }
@@ -704,14 +704,14 @@ extern "C" int ntt_fr(void* vctx, blst_fr* out, const blst_fr* in, size_t n, int
     std::lock_guard<std::mutex> lk(ctx->mu);
     try {
         kzgamd::DeviceGuard on_device(ctx->device);
-        NTT_TRY(on_device.err);
+        DEV_TRY(on_device.err);
         ctx->ensure(n);
-        NTT_TRY(hipMemcpyAsync(ctx->d_a, in, n * sizeof(Fr), hipMemcpyHostToDevice, ctx->stream));
+        DEV_TRY(hipMemcpyAsync(ctx->d_a, in, n * sizeof(Fr), hipMemcpyHostToDevice, ctx->stream));
         ntt_enqueue(ctx, ctx->d_b, ctx->d_a, n, 1, inverse != 0, ctx->stream);
-        NTT_TRY(hipMemcpyAsync(out, ctx->d_b, n * sizeof(Fr), hipMemcpyDeviceToHost, ctx->stream));
-        NTT_TRY(hipStreamSynchronize(ctx->stream));
-    } catch (const NttErr& e) {
-        return -(int)e.e - 100;
+        DEV_TRY(hipMemcpyAsync(out, ctx->d_b, n * sizeof(Fr), hipMemcpyDeviceToHost, ctx->stream));
+        DEV_TRY(hipStreamSynchronize(ctx->stream));
+    } catch (const kzgamd::DevErr& e) {
+        return kzgamd::dev_code(e.e);
     }
     return 0;
 }
@@ -738,7 +738,7 @@ void das_enqueue(NttCtx* ctx, Fr* d_odds, const Fr* d_evens, Fr* d_tmp, size_t n
         P.scale = times32(inv_len(n));
         P.last = 1;
         launch_pass(ctx, PLAN_DAS, ilog2(n), d_odds, d_evens, P, (unsigned)((P.total + TILE - 1) / TILE), stream);
-        NTT_TRY(hipGetLastError());
+        DEV_TRY(hipGetLastError());
         return;
     }
     ntt_enqueue(ctx, d_tmp, d_evens, n, nbatch, true, stream, SCALE_INV_TWIST);
@@ -759,14 +759,14 @@ extern "C" int das_fft_extension(void* vctx, blst_fr* odds, const blst_fr* evens
     std::lock_guard<std::mutex> lk(ctx->mu);
     try {
         kzgamd::DeviceGuard on_device(ctx->device);
-        NTT_TRY(on_device.err);
+        DEV_TRY(on_device.err);
         ctx->ensure(2 * n);
-        NTT_TRY(hipMemcpyAsync(ctx->d_a, evens, n * sizeof(Fr), hipMemcpyHostToDevice, ctx->stream));
+        DEV_TRY(hipMemcpyAsync(ctx->d_a, evens, n * sizeof(Fr), hipMemcpyHostToDevice, ctx->stream));
         das_enqueue(ctx, ctx->d_a + n, ctx->d_a, ctx->d_b, n, 1, ctx->stream);
-        NTT_TRY(hipMemcpyAsync(odds, ctx->d_a + n, n * sizeof(Fr), hipMemcpyDeviceToHost, ctx->stream));
-        NTT_TRY(hipStreamSynchronize(ctx->stream));
-    } catch (const NttErr& e) {
-        return -(int)e.e - 100;
+        DEV_TRY(hipMemcpyAsync(odds, ctx->d_a + n, n * sizeof(Fr), hipMemcpyDeviceToHost, ctx->stream));
+        DEV_TRY(hipStreamSynchronize(ctx->stream));
+    } catch (const kzgamd::DevErr& e) {
+        return kzgamd::dev_code(e.e);
     }
     return 0;
 }
@@ -783,10 +783,10 @@ extern "C" int kzgamd_das_fft_extension_device(void* vctx, void* d_odds, const v
     if (d_odds == d_evens || d_scratch == d_evens || d_scratch == d_odds) return -3;
     try {
         kzgamd::DeviceGuard on_device(ctx->device);
-        NTT_TRY(on_device.err);
+        DEV_TRY(on_device.err);
         das_enqueue(ctx, (Fr*)d_odds, (const Fr*)d_evens, (Fr*)d_scratch, n, nbatch, (hipStream_t)stream);
-    } catch (const NttErr& e) {
-        return -(int)e.e - 100;
+    } catch (const kzgamd::DevErr& e) {
+        return kzgamd::dev_code(e.e);
     }
     return 0;
 }

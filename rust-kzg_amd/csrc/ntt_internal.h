@@ -9,15 +9,7 @@
 #include <vector>
 
 #include "ff.hip.h"
-
-struct NttErr {
-    hipError_t e;
-};
-#define NTT_TRY(x)                              \
-    do {                                        \
-        hipError_t _e = (x);                    \
-        if (_e != hipSuccess) throw NttErr{_e}; \
-    } while (0)
+#include "host_call.h"
 
 // device copy of one tile plan (ntt_plan.h): the per-thread element table of every round + per-round constants
 struct NttPlanDev {
@@ -113,8 +105,8 @@ struct NttCtx {
         if (d_b) (void)hipFree(d_b);
         d_a = d_b = nullptr;
         cap = 0;
-        NTT_TRY(hipMalloc(&d_a, n * sizeof(Fr)));
-        NTT_TRY(hipMalloc(&d_b, n * sizeof(Fr)));
+        DEV_TRY(hipMalloc(&d_a, n * sizeof(Fr)));
+        DEV_TRY(hipMalloc(&d_b, n * sizeof(Fr)));
         cap = n;
     }
 };

@@ -287,13 +287,13 @@ void enqueue_mul(PolyCtx* pc, Fr* out, size_t out_len, int out_flip, const Opera
         hipLaunchKernelGGL(k_poly_cut, dim3(blocks(npoly * out_len)), dim3(256), 0, st, out, out_len, out_len, out_flip, (const Fr*)g, N,
                            npoly * out_len);
     }
-    PL_TRY(hipGetLastError());
+    DEV_TRY(hipGetLastError());
 }
 
 // c[poly L + i] = coefficient i of 1 / b_poly, i < L; a zero b_poly[0] raises pc->flag
 void enqueue_inverse(PolyCtx* pc, Fr* c, const Operand& b, size_t L, size_t npoly, const InvPlan& pl) {
     hipStream_t st = pc->st;
-    if (b.len == 1 && L > 1) PL_TRY(hipMemsetAsync(c, 0, npoly * L * sizeof(Fr), st));  // a constant: the rest of the series is zero
+    if (b.len == 1 && L > 1) DEV_TRY(hipMemsetAsync(c, 0, npoly * L * sizeof(Fr), st));  // a constant: the rest of the series is zero
     hipLaunchKernelGGL(k_poly_inv0, dim3(blocks(npoly, 64)), dim3(64), 0, st, c, L, b, pc->flag.as<int>(), npoly);
     if (pl.D0 > 1) hipLaunchKernelGGL(k_poly_inv_direct, dim3((unsigned)npoly), dim3(64), 0, st, c, L, b, pl.D0);
     Fr *f = pc->f.as<Fr>(), *g = pc->g.as<Fr>();
@@ -305,7 +305,7 @@ void enqueue_inverse(PolyCtx* pc, Fr* c, const Operand& b, size_t L, size_t npol
         ntt_on_stream(pc, g, f, s.N, npoly, 1);
         hipLaunchKernelGGL(k_poly_cut, dim3(blocks(npoly * s.n1)), dim3(256), 0, st, c, L, s.n1, 0, (const Fr*)g, s.N, npoly * s.n1);
     }
-    PL_TRY(hipGetLastError());
+    DEV_TRY(hipGetLastError());
 }
 
 }  // namespace
@@ -326,21 +326,11 @@ extern "C" void* kzgamd_poly_new(void* vntt, const KzgAmdConfig* cfg, int* err) 
         *err = -2;
         return nullptr;
     }
-    auto* pc = new PolyCtx();
-    try {
-        kzgamd::DeviceGuard on_device(ntt->device);  // the handle lives where its NTT handle lives
-        PL_TRY(on_device.err);
+    return kzgamd::create_handle<PolyCtx>(ntt->device, err, [&](PolyCtx* pc) {
         pc->ntt = ntt;
-        pc->device = ntt->device;
-        PL_TRY(hipStreamCreateWithFlags(&pc->st, hipStreamNonBlocking));
+        DEV_TRY(hipStreamCreateWithFlags(&pc->st, hipStreamNonBlocking));
         pc->flag.ensure(sizeof(int));
-    } catch (const PolyErr& e) {
-        *err = -(int)e.e - 100;
-        kzgamd::DeviceGuard on_device(ntt->device);
-        delete pc;
-        return nullptr;
-    }
-    return pc;
+    });
 }
 
 extern "C" void kzgamd_poly_free(void* vpc) {
@@ -402,7 +392,7 @@ extern "C" int kzgamd_poly_eval(void* vpc, blst_fr* ys, const blst_fr* polys, si
             if (s.wv > 1)
                 hipLaunchKernelGGL(k_poly_eval_carry, dim3((unsigned)s.nseq), dim3(64), 0, st, pc->out.as<Fr>(), pc->sums.as<Fr>(),
                                    pc->pw.as<Fr>(), s);
-            PL_TRY(hipGetLastError());
+            DEV_TRY(hipGetLastError());
             download(pc, ys + done * nx, pc->out.p, cnt * nx * sizeof(Fr));
         }
     });
@@ -424,7 +414,7 @@ extern "C" int kzgamd_poly_scale(void* vpc, blst_fr* out, const blst_fr* in, siz
             const size_t cnt = min_sz(per, npoly - done);
             upload(pc, pc->a.p, in + done * len, cnt * len * sizeof(Fr));
             hipLaunchKernelGGL(k_poly_scale, dim3(blocks(cnt * len)), dim3(256), 0, pc->st, pc->a.as<Fr>(), pc->a.as<Fr>(), f, len, cnt * len);
-            PL_TRY(hipGetLastError());
+            DEV_TRY(hipGetLastError());
             download(pc, out + done * len, pc->a.p, cnt * len * sizeof(Fr));
         }
     });
@@ -482,7 +472,7 @@ extern "C" int kzgamd_poly_inverse(void* vpc, blst_fr* out, const blst_fr* b, si
             pc->f.ensure(2 * per * pl.maxN * sizeof(Fr));
             pc->g.ensure(2 * per * pl.maxN * sizeof(Fr));
         }
-        PL_TRY(hipMemsetAsync(pc->flag.p, 0, sizeof(int), pc->st));
+        DEV_TRY(hipMemsetAsync(pc->flag.p, 0, sizeof(int), pc->st));
         for (size_t done = 0; done < npoly; done += per) {
             const size_t cnt = min_sz(per, npoly - done);
             upload(pc, pc->b.p, b + done * lb, cnt * lb * sizeof(Fr));
@@ -516,7 +506,7 @@ extern "C" int kzgamd_poly_div(void* vpc, blst_fr* q, const blst_fr* a, size_t l
             pc->g.ensure(2 * per * N * sizeof(Fr));
         }
         hipStream_t st = pc->st;
-        PL_TRY(hipMemsetAsync(pc->flag.p, 0, sizeof(int), st));
+        DEV_TRY(hipMemsetAsync(pc->flag.p, 0, sizeof(int), st));
         for (size_t done = 0; done < npoly; done += per) {
             const size_t cnt = min_sz(per, npoly - done);
             upload(pc, pc->a.p, a + done * la, cnt * la * sizeof(Fr));
@@ -527,7 +517,7 @@ extern "C" int kzgamd_poly_div(void* vpc, blst_fr* q, const blst_fr* a, size_t l
                                    Operand{pc->b.as<Fr>(), 1, 1, 0}, pc->flag.as<int>(), cnt);
                 hipLaunchKernelGGL(k_poly_mul_const, dim3(blocks(cnt * la)), dim3(256), 0, st, pc->out.as<Fr>(), pc->a.as<Fr>(),
                                    pc->c.as<Fr>(), la, cnt * la);
-                PL_TRY(hipGetLastError());
+                DEV_TRY(hipGetLastError());
             } else {
                 // fast_div (poly.rs:242-249): q = flip(flip(a) * (1 / flip(b) mod x^L) mod x^L)
                 enqueue_inverse(pc, pc->c.as<Fr>(), Operand{pc->b.as<Fr>(), lb, lb, 1}, L, cnt, pl);

@@ -1,6 +1,6 @@
 // Shared between poly.hip (Poly<Fr>) and zeropoly.hip (ZeroPoly, PolyRecover): the context object behind the opaque
-// handle of kzgamd_poly_new(), its workspace buffers, the frame every call runs in (lock, device, stream, one
-// synchronisation) and the wave-local exchange of field elements.  Nothing here launches a kernel of its own.
+// handle of kzgamd_poly_new(), its workspace buffers and the wave-local exchange of field elements; the frame every call
+// runs in (lock, device, stream, one synchronisation) is host_call.h's.  Nothing here launches a kernel of its own.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -12,6 +12,7 @@
 #include "../../include/kzg_mi355x.h"
 #include "device_guard.h"
 #include "ff.hip.h"
+#include "host_call.h"
 #include "ntt_internal.h"
 
 namespace kzgamd_poly {
@@ -38,36 +39,10 @@ __device__ __forceinline__ Fr shfl_up(const Fr& a, int d) {
     return r;
 }
 
-struct PolyErr {
-    hipError_t e;
-};
-#define PL_TRY(x)                                             \
-    do {                                                      \
-        hipError_t _e = (x);                                  \
-        if (_e != hipSuccess) throw kzgamd_poly::PolyErr{_e}; \
-    } while (0)
-
-struct DevBuf {
-    void* p = nullptr;
-    size_t cap = 0;
-    void ensure(size_t bytes) {
-        if (bytes <= cap) return;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-        PL_TRY(hipMalloc(&p, bytes));
-        cap = bytes;
-    }
-    void drop() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-    }
-    template <class T>
-    T* as() const {
-        return (T*)p;
-    }
-};
+using kzgamd::blocks;
+using kzgamd::DevBuf;
+using kzgamd::next_pow2;
+using kzgamd::run_call;
 
 struct PolyCtx {
     NttCtx* ntt = nullptr;
@@ -88,56 +63,27 @@ struct PolyCtx {
     }
 };
 
-inline unsigned blocks(size_t total, unsigned per = 256) { return (unsigned)((total + per - 1) / per); }
-inline size_t next_pow2(size_t v) {
-    size_t n = 1;
-    while (n < v) n <<= 1;
-    return n;
-}
 inline size_t min_sz(size_t a, size_t b) { return a < b ? a : b; }
 
 inline void ntt_on_stream(PolyCtx* pc, Fr* out, const Fr* in, size_t n, size_t nbatch, int inverse) {
-    if (kzgamd_ntt_fr_device(pc->ntt, out, in, n, nbatch, inverse, pc->st) != 0) throw PolyErr{hipErrorUnknown};
+    if (kzgamd_ntt_fr_device(pc->ntt, out, in, n, nbatch, inverse, pc->st) != 0) throw kzgamd::DevErr{hipErrorUnknown};
 }
 
 // polynomials per slice: the workspace of a slice stays within a share of the free HBM
 inline size_t slice_of(PolyCtx* pc, size_t npoly, size_t bytes_per_poly) {
     size_t free_b = 0, total_b = 0, held = 0;
-    PL_TRY(hipMemGetInfo(&free_b, &total_b));
+    DEV_TRY(hipMemGetInfo(&free_b, &total_b));
     for (DevBuf* d : pc->bufs()) held += d->cap;
     size_t per = (free_b + held) / 8 / (bytes_per_poly ? bytes_per_poly : 1);
     if (per == 0) per = 1;
     return per < npoly ? per : npoly;
 }
 
-// one call on the handle: its lock, its GPU, everything `body` enqueues, one synchronisation
-template <class F>
-int run_call(PolyCtx* pc, F&& body) {
-    std::lock_guard<std::mutex> lk(pc->mu);
-    int rc = 0;
-    try {
-        kzgamd::DeviceGuard on_device(pc->device);
-        PL_TRY(on_device.err);
-        try {
-            body();
-        } catch (...) {
-            (void)hipStreamSynchronize(pc->st);  // a copy into the caller's buffer may be in flight
-            throw;
-        }
-        PL_TRY(hipStreamSynchronize(pc->st));
-    } catch (const PolyErr& e) {
-        rc = -(int)e.e - 100;
-    } catch (...) {
-        rc = -2;
-    }
-    return rc;
-}
-
 inline void upload(PolyCtx* pc, void* dst, const void* src, size_t bytes) {
-    PL_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, pc->st));
+    DEV_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, pc->st));
 }
 inline void download(PolyCtx* pc, void* dst, const void* src, size_t bytes) {
-    PL_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, pc->st));
+    DEV_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, pc->st));
 }
 
 }  // namespace kzgamd_poly

@@ -266,7 +266,7 @@ void zero_plan_build(ZeroPlan& pl, size_t nprob, CountOf counts) {
 
 // a transform on the handle's stream; a list of one element is its own transform
 void zntt(PolyCtx* pc, Fr* out, const Fr* in, size_t n, size_t nbatch, int inverse) {
-    if (n == 1) PL_TRY(hipMemcpyAsync(out, in, nbatch * sizeof(Fr), hipMemcpyDeviceToDevice, pc->st));
+    if (n == 1) DEV_TRY(hipMemcpyAsync(out, in, nbatch * sizeof(Fr), hipMemcpyDeviceToDevice, pc->st));
     else ntt_on_stream(pc, out, in, n, nbatch, inverse);
 }
 
@@ -306,7 +306,7 @@ void enqueue_zero(PolyCtx* pc, Fr* zp, Fr* ze, size_t n, size_t rs, const ZeroPl
     const size_t total = pl.nprob * n;
     if (direct) {
         hipLaunchKernelGGL(k_zp_direct, dim3(blocks(total)), dim3(256), 0, st, ze, idx, tab, roots, rs, n, total);
-        PL_TRY(hipGetLastError());
+        DEV_TRY(hipGetLastError());
         if (want_zp) zntt(pc, zp, ze, n, pl.nprob, 1);
         return;
     }
@@ -323,7 +323,7 @@ void enqueue_zero(PolyCtx* pc, Fr* zp, Fr* ze, size_t n, size_t rs, const ZeroPl
         hipLaunchKernelGGL(k_zp_cut, dim3(blocks(np * N)), dim3(256), 0, st, c, (const Fr*)g, pairs, d, np * N);
     }
     hipLaunchKernelGGL(k_zp_expand, dim3(blocks(total)), dim3(256), 0, st, zp, (const Fr*)c, tab, n, total);
-    PL_TRY(hipGetLastError());
+    DEV_TRY(hipGetLastError());
     if (ze) zntt(pc, ze, zp, n, pl.nprob, 0);
 }
 
@@ -421,10 +421,10 @@ extern "C" int kzgamd_poly_reduce_partials(void* vpc, blst_fr* out, size_t domai
             zntt(pc, g, f, N, m, 0);
             for (size_t half = next_pow2(m) / 2; half >= 1; half >>= 1)
                 hipLaunchKernelGGL(k_rp_fold, dim3(blocks(half * N)), dim3(256), 0, st, g, min_sz(m, 2 * half), half, N, half * N);
-            if (done == 0) PL_TRY(hipMemcpyAsync(acc, g, N * sizeof(Fr), hipMemcpyDeviceToDevice, st));
+            if (done == 0) DEV_TRY(hipMemcpyAsync(acc, g, N * sizeof(Fr), hipMemcpyDeviceToDevice, st));
             else hipLaunchKernelGGL(k_rp_acc, dim3(blocks(N)), dim3(256), 0, st, acc, (const Fr*)g, N);
-            PL_TRY(hipGetLastError());
-            PL_TRY(hipStreamSynchronize(st));  // the next slice rewrites `spans`
+            DEV_TRY(hipGetLastError());
+            DEV_TRY(hipStreamSynchronize(st));  // the next slice rewrites `spans`
         }
         zntt(pc, pc->out.as<Fr>(), acc, N, 1, 1);
         download(pc, out, pc->out.p, out_len * sizeof(Fr));
@@ -469,7 +469,7 @@ extern "C" int kzgamd_poly_zero_poly(void* vpc, blst_fr* zero_eval, blst_fr* zer
                          !direct || zero_poly != nullptr);
             if (zero_poly) download(pc, zero_poly + done * n, zp, cnt * n * sizeof(Fr));
             if (zero_eval) download(pc, zero_eval + done * n, ze, cnt * n * sizeof(Fr));
-            PL_TRY(hipStreamSynchronize(pc->st));  // the next slice rewrites the plan
+            DEV_TRY(hipStreamSynchronize(pc->st));  // the next slice rewrites the plan
         }
     });
 }
@@ -526,14 +526,14 @@ extern "C" int kzgamd_poly_recover(void* vpc, blst_fr* out, const blst_fr* sampl
             hipLaunchKernelGGL(k_rc_div, dim3(blocks(tot)), dim3(256), 0, st, o, (const Fr*)g, n, tot);
             zntt(pc, a, o, n, cnt, 1);
             hipLaunchKernelGGL(k_rc_scale, dim3(blocks(tot)), dim3(256), 0, st, a, five, n, tot);
-            PL_TRY(hipGetLastError());
+            DEV_TRY(hipGetLastError());
             if (coeffs) {
                 download(pc, out + done * n, a, tot * sizeof(Fr));
             } else {
                 zntt(pc, o, a, n, cnt, 0);
                 download(pc, out + done * n, o, tot * sizeof(Fr));
             }
-            PL_TRY(hipStreamSynchronize(st));  // the next slice rewrites the plan
+            DEV_TRY(hipStreamSynchronize(st));  // the next slice rewrites the plan
         }
     });
 }

@@ -539,6 +539,354 @@ int main() {
         assert field in hdr
 
 
+def test_take_key_extracts_the_keys_of_one_entry_point_as_the_three_scanners_did(tmp_path):
+    """csrc/config.h, kzgamd::take_key: the extractor of the keys that belong to one entry point (pairing_gpu_min of
+    kzgamd_kzg_new, fk20_table of kzgamd_fk20_new, mul_slice of the group multiplications).  The three scanners it
+    replaced are kept in this program as the reference: on a table of strings — the key alone, first, last, in the
+    middle and twice, every separator, the empty string, prefixes of other keys, malformed values, lo, hi and one beyond
+    each — old and new give the same verdict, the same value and the same rest, and `Options::parse` makes the same of
+    that rest.  The one difference is pinned: of two mul_slice tokens the old scanner tested both for a power of two,
+    read_config tests the one that wins."""
+    import shutil
+
+    cxx = shutil.which("g++") or shutil.which("clang++") or "/opt/rocm/lib/llvm/bin/clang++"
+    src = tmp_path / "takekey.cpp"
+    src.write_text(r'''
+#include <cstdio>
+#include <cstdlib>
+#include <vector>
+#include "config.h"
+using kzgamd::Options;
+using kzgamd::take_key;
+static int fails = 0;
+#define EXPECT(c) do { if (!(c)) { printf("FAILED line %d: %s\n", __LINE__, #c); ++fails; } } while (0)
+
+// ---- the three scanners that kzg.hip, fk20.hip and groupmul.hip had before take_key, kept here as the reference
+namespace old {
+constexpr size_t SLICE_MIN = 64;
+bool take_pairing_gpu_min(const char* str, long* value, std::string* rest) {
+    static const char key[] = "pairing_gpu_min";
+    auto is_sep = [](char c) { return c == ';' || c == ',' || c == ' ' || c == '\t' || c == '\n'; };
+    const char* p = str;
+    while (*p) {
+        while (*p && is_sep(*p)) ++p;
+        const char* e = p;
+        while (*e && !is_sep(*e)) ++e;
+        if (e == p) break;
+        if ((size_t)(e - p) > sizeof key - 1 && !strncmp(p, key, sizeof key - 1) && p[sizeof key - 1] == '=') {
+            char* end = nullptr;
+            const long v = strtol(p + sizeof key, &end, 10);
+            if (end != e || end == p + sizeof key || v < -1 || v > (1 << 20)) return false;
+            *value = v;
+        } else {
+            if (!rest->empty()) *rest += ';';
+            rest->append(p, e);
+        }
+        p = e;
+    }
+    return true;
+}
+bool take_fk20_table(const char* str, long* value, std::string* rest) {
+    static const char key[] = "fk20_table";
+    auto is_sep = [](char c) { return c == ';' || c == ',' || c == ' ' || c == '\t' || c == '\n'; };
+    const char* p = str;
+    while (*p) {
+        while (*p && is_sep(*p)) ++p;
+        const char* e = p;
+        while (*e && !is_sep(*e)) ++e;
+        if (e == p) break;
+        if ((size_t)(e - p) > sizeof key - 1 && !strncmp(p, key, sizeof key - 1) && p[sizeof key - 1] == '=') {
+            char* end = nullptr;
+            const long v = strtol(p + sizeof key, &end, 10);
+            if (end != e || end == p + sizeof key || v < -1 || v > 1) return false;
+            *value = v;
+        } else {
+            if (!rest->empty()) *rest += ';';
+            rest->append(p, e);
+        }
+        p = e;
+    }
+    return true;
+}
+bool take_mul_slice(const char* str, size_t* value) {
+    static const char key[] = "mul_slice";
+    auto is_sep = [](char c) { return c == ';' || c == ',' || c == ' ' || c == '\t' || c == '\n'; };
+    const char* p = str;
+    while (*p) {
+        while (*p && is_sep(*p)) ++p;
+        const char* e = p;
+        while (*e && !is_sep(*e)) ++e;
+        if (e == p) break;
+        if ((size_t)(e - p) <= sizeof key - 1 || strncmp(p, key, sizeof key - 1) || p[sizeof key - 1] != '=') return false;
+        char* end = nullptr;
+        const long long v = strtoll(p + sizeof key, &end, 10);
+        if (end != e || end == p + sizeof key || v < (long long)SLICE_MIN || v > (1ll << 30) || (v & (v - 1))) return false;
+        *value = (size_t)v;
+        p = e;
+    }
+    return true;
+}
+}  // namespace old
+
+// what groupmul.hip's read_config makes of take_key: the one key of its calls, a power of two from SLICE_MIN
+static bool new_mul_slice(const char* str, size_t* value) {
+    long long v = 1 << 18;  // SLICE_DEFAULT: what stays when the key is not there
+    std::string rest;
+    if (!take_key(str, "mul_slice", (long long)old::SLICE_MIN, 1ll << 30, &v, &rest) || !rest.empty() || (v & (v - 1))) return false;
+    *value = (size_t)v;
+    return true;
+}
+static bool parses(const std::string& s) {
+    Options o;
+    std::string err;
+    return o.parse(s.c_str(), &err);
+}
+struct Got {
+    bool ok;
+    long long v;
+    std::string rest;
+};
+static Got take(const char* s, const char* key, long long lo, long long hi) {
+    Got g{false, -77, ""};
+    g.ok = take_key(s, key, lo, hi, &g.v, &g.rest);
+    return g;
+}
+
+int main() {
+    std::vector<std::string> table = {
+        // the strings whose verdicts the entry points must keep
+        "mul_slices=64", "mul_slice=", "mul_slice=96", "mul_slice=64;spl=1", "fk20_table=", "fk20_table=2", "fk20_table=0;nonsense=1",
+        "combine=0;fk20_table=0,g1_wide_max=4096",
+        // the empty string, separators alone
+        "", ";", " ; ,\t\n",
+        // prefixes of other keys, keys without a value, text after the number
+        "fk20_tables=1", "fk20_table", "fk20_table=1x", "fk20_table=x", "fk20_table=-", "fk20_table==1", "xfk20_table=1", "pairing_gpu_min", "pairing_gpu_mins=3",
+        "pairing_gpu_min=4x", "mul_slice", "mul_slice=64x", "mul_slice=0x40", "fk20_table= 1", "fk20_table=+1", "fk20_table=01",
+        // numbers no long holds
+        "pairing_gpu_min=99999999999999999999999", "mul_slice=99999999999999999999999", "fk20_table=-99999999999999999999999"};
+    // each key alone, first, last, in the middle, twice (the last one wins), with every separator
+    const char* seps[] = {";", ",", " ", "\t", "\n", ";;", " ; "};
+    struct K { const char* key; std::vector<const char*> vals; };
+    const K keys[] = {
+        {"pairing_gpu_min", {"-2", "-1", "0", "4", "1048576", "1048577"}},      // lo - 1, lo, ..., hi, hi + 1
+        {"fk20_table", {"-2", "-1", "0", "1", "2"}},
+        {"mul_slice", {"32", "63", "64", "65", "128", "262144", "1073741824", "1073741825", "2147483648"}},
+    };
+    for (const K& k : keys)
+        for (const char* v : k.vals) {
+            const std::string kv = std::string(k.key) + "=" + v;
+            table.push_back(kv);
+            for (const char* sep : seps) {
+                table.push_back(kv + sep + "spl=4");
+                table.push_back("spl=4" + std::string(sep) + kv);
+                table.push_back("glv=0" + std::string(sep) + kv + sep + "spl=4");
+                table.push_back(kv + sep);
+                table.push_back(sep + kv);
+                table.push_back(kv + sep + k.key + "=" + k.vals[2]);
+                table.push_back(std::string(k.key) + "=" + k.vals[2] + sep + kv);
+                table.push_back(kv + sep + "nonsense=1");
+                table.push_back(kv + sep + "spl=3");
+            }
+        }
+    size_t last_wins = 0;
+    // old and new agree on every string of the table: verdict, value and the rest handed to Options::parse
+    for (const std::string& s : table) {
+        long ov = -77;
+        std::string orest;
+        bool ook = old::take_pairing_gpu_min(s.c_str(), &ov, &orest);
+        Got g = take(s.c_str(), "pairing_gpu_min", -1, 1 << 20);
+        if (ook != g.ok || (ook && (ov != g.v || orest != g.rest || parses(orest) != parses(g.rest)))) {
+            printf("pairing_gpu_min differs on '%s'\n", s.c_str());
+            ++fails;
+        }
+        ov = -77;
+        orest.clear();
+        ook = old::take_fk20_table(s.c_str(), &ov, &orest);
+        g = take(s.c_str(), "fk20_table", -1, 1);
+        if (ook != g.ok || (ook && (ov != g.v || orest != g.rest || parses(orest) != parses(g.rest)))) {
+            printf("fk20_table differs on '%s'\n", s.c_str());
+            ++fails;
+        }
+        size_t os = 12345, ns = 12345;
+        ook = old::take_mul_slice(s.c_str(), &os);
+        const bool nok = new_mul_slice(s.c_str(), &ns);
+        if (ook && os == 12345) os = 1 << 18;  // the old scanner left the caller's default alone
+        // The one difference, pinned: the old scanner tested "a power of two" on every mul_slice token, read_config
+        // tests it on the value take_key hands back, the last one.  "mul_slice=65;mul_slice=64" was refused and is
+        // now a slice of 64 (65 is inside the range; a first value outside it is refused by both).
+        const size_t first = s.find("mul_slice=65"), last = s.rfind("mul_slice=");
+        if (!ook && nok && first != std::string::npos && last > first) {
+            EXPECT(ns == 64);
+            ++last_wins;
+            continue;
+        }
+        if (ook != nok || (ook && os != ns)) {
+            printf("mul_slice differs on '%s'\n", s.c_str());
+            ++fails;
+        }
+    }
+    printf("table %zu\n", table.size());
+    EXPECT(last_wins == sizeof seps / sizeof seps[0]);
+    // the verdicts themselves
+    size_t sl = 1;
+    EXPECT(!new_mul_slice("mul_slices=64", &sl) && !new_mul_slice("mul_slice=", &sl) && !new_mul_slice("mul_slice=96", &sl));
+    EXPECT(!new_mul_slice("mul_slice=64;spl=1", &sl) && !new_mul_slice("mul_slice=32", &sl) && !new_mul_slice("mul_slice=2147483648", &sl) && sl == 1);
+    EXPECT(new_mul_slice("", &sl) && sl == (1u << 18) && new_mul_slice("mul_slice=64", &sl) && sl == 64);
+    EXPECT(new_mul_slice(" mul_slice=128\n", &sl) && sl == 128 && new_mul_slice("mul_slice=64,mul_slice=1073741824", &sl) && sl == (1u << 30));
+    EXPECT(!take("fk20_table=", "fk20_table", -1, 1).ok && !take("fk20_table=2", "fk20_table", -1, 1).ok);
+    EXPECT(!take("fk20_table=-2", "fk20_table", -1, 1).ok && !take("spl=4;fk20_table=1x", "fk20_table", -1, 1).ok);
+    Got g = take("fk20_table=0;nonsense=1", "fk20_table", -1, 1);
+    EXPECT(g.ok && g.v == 0 && g.rest == "nonsense=1" && !parses(g.rest));
+    g = take("combine=0;fk20_table=0,g1_wide_max=4096", "fk20_table", -1, 1);
+    EXPECT(g.ok && g.v == 0 && g.rest == "combine=0;g1_wide_max=4096" && parses(g.rest));
+    {
+        Options o;
+        std::string err;
+        EXPECT(o.parse(g.rest.c_str(), &err) && o.t[kzgamd::T_COMBINE] == 0 && o.t[kzgamd::T_G1_WIDE_MAX] == 4096);
+    }
+    g = take("", "fk20_table", -1, 1);
+    EXPECT(g.ok && g.v == -77 && g.rest.empty());  // no key: the caller's default stays
+    g = take("fk20_tables=1 fk20_table\tfk20_tabl=1", "fk20_table", -1, 1);
+    EXPECT(g.ok && g.v == -77 && g.rest == "fk20_tables=1;fk20_table;fk20_tabl=1" && !parses(g.rest));
+    g = take("fk20_table=1", "fk20_table", -1, 1);
+    EXPECT(g.ok && g.v == 1 && g.rest.empty());
+    g = take("fk20_table=-1;spl=4", "fk20_table", -1, 1);
+    EXPECT(g.ok && g.v == -1 && g.rest == "spl=4");
+    g = take("spl=4,glv=0 window=13\tfk20=-1\npairing_gpu_min=1048576", "pairing_gpu_min", -1, 1 << 20);
+    EXPECT(g.ok && g.v == (1 << 20) && g.rest == "spl=4;glv=0;window=13;fk20=-1" && parses(g.rest));
+    g = take("pairing_gpu_min=0;spl=4;pairing_gpu_min=9", "pairing_gpu_min", -1, 1 << 20);
+    EXPECT(g.ok && g.v == 9 && g.rest == "spl=4");  // the last one wins
+    EXPECT(!take("pairing_gpu_min=1048577", "pairing_gpu_min", -1, 1 << 20).ok && !take("pairing_gpu_min=-2", "pairing_gpu_min", -1, 1 << 20).ok);
+    EXPECT(take("pairing_gpu_min=-1", "pairing_gpu_min", -1, 1 << 20).v == -1);
+    printf("fails %d\n", fails);
+    return fails != 0;
+}
+''')
+    exe = tmp_path / "takekey"
+    subprocess.check_call([cxx, "-O1", "-std=c++17", "-I", os.path.join(ROOT, "rust-kzg_amd", "csrc"), str(src), "-o", str(exe)])
+    res = subprocess.run([str(exe)], capture_output=True, text=True)
+    assert res.returncode == 0 and "fails 0" in res.stdout, res.stdout + res.stderr
+    assert int(re.search(r"^table (\d+)$", res.stdout, flags=re.M).group(1)) > 1000
+    # the three keys stay out of the library's table of keys and of the rows DESIGN.md §9 generates from it
+    cfg = open(os.path.join(ROOT, "rust-kzg_amd", "csrc", "config.h")).read()
+    table = cfg[cfg.index("inline const TuneKey* tune_keys()"):cfg.index("inline bool tune_value_allowed")]
+    design = open(os.path.join(ROOT, "DESIGN.md"), encoding="utf-8").read()
+    sec = design[design.index("## 9. Configuration and tuning keys"):]
+    sec = sec[:sec.index("\n## 10.")]
+    rows = re.findall(r"^\| `([a-z0-9_]+)` \| (-?\d+) \| (-?\d+) … (-?\d+) \|", sec, flags=re.M)  # the rows of the library's table
+    for key in ("pairing_gpu_min", "fk20_table", "mul_slice"):
+        assert '{"%s"' % key not in table and key not in [r[0] for r in rows]
+
+
+def test_host_call_frame_maps_errors_and_releases_the_handle(tmp_path):
+    """csrc/host_call.h without a device (the HIP calls it makes are this program's own, counted): the status of a
+    body that returns one, of a void body, of DevErr{hipErrorOutOfMemory} (-102), of std::bad_alloc (-2) and of an int
+    thrown through kzgamd::foreign (-1099); run_call runs the body on the handle's device with its lock held,
+    synchronises once on either way out and leaves the lock free after every throwing body; DevBuf grows and drops,
+    ScopedBuf frees; create_handle gives dev_code or -4 and deletes what did not make it."""
+    import shutil
+
+    cxx = shutil.which("g++") or shutil.which("clang++") or "/opt/rocm/lib/llvm/bin/clang++"
+    rocm = os.environ.get("ROCM_PATH", "/opt/rocm")
+    src = tmp_path / "hostcall.cpp"
+    src.write_text(r'''
+#include <cstdio>
+#include <new>
+#include "host_call.h"
+// the HIP runtime of this program: every call succeeds and is counted, no device anywhere
+static int syncs = 0, frees = 0, mallocs = 0, device = 0;
+extern "C" {
+hipError_t hipGetDevice(int* d) { *d = device; return hipSuccess; }
+hipError_t hipSetDevice(int d) { device = d; return hipSuccess; }
+hipError_t hipGetLastError(void) { return hipSuccess; }
+hipError_t hipStreamSynchronize(hipStream_t) { ++syncs; return hipSuccess; }
+hipError_t hipMalloc(void** p, size_t n) { ++mallocs; *p = ::operator new(n); return hipSuccess; }
+hipError_t hipFree(void* p) { ++frees; ::operator delete(p); return hipSuccess; }
+}
+static int fails = 0;
+#define EXPECT(c) do { if (!(c)) { printf("FAILED line %d: %s\n", __LINE__, #c); ++fails; } } while (0)
+struct Handle {
+    std::mutex mu;
+    int device = 3;
+    hipStream_t st = nullptr;
+    kzgamd::DevBuf buf;
+    bool made = false;
+    static int live;
+    Handle() { ++live; }
+    ~Handle() { --live; buf.drop(); }
+};
+int Handle::live = 0;
+// the handle's lock is free again: a second call would not block
+static bool unlocked(Handle& h) {
+    if (!h.mu.try_lock()) return false;
+    h.mu.unlock();
+    return true;
+}
+int main() {
+    using namespace kzgamd;
+    EXPECT(dev_code(hipErrorOutOfMemory) == -102 && dev_code(hipErrorUnknown) == -1099);
+    // the pure mapping
+    EXPECT(status_of([] { return 7; }) == 7);
+    EXPECT(status_of([] {}) == 0);
+    EXPECT(status_of([] { DEV_TRY(hipErrorOutOfMemory); }) == -102);
+    EXPECT(status_of([]() -> int { throw std::bad_alloc(); }) == -2);
+    EXPECT(status_of([] { foreign([] { throw 5; }); }) == -1099);
+    EXPECT(status_of([] { foreign([] { throw DevErr{hipErrorOutOfMemory}; }); }) == -102);  // a DevErr passes through it
+    EXPECT(status_of([] { foreign([] {}); }) == 0);
+    // the frame of a call: one synchronisation when the body returns, one more before unwinding when it throws
+    Handle h;
+    int seen_device = -1;
+    syncs = 0;
+    EXPECT(run_call(&h, [&] { seen_device = device; return 7; }) == 7 && syncs == 1 && unlocked(h));
+    EXPECT(seen_device == 3 && device == 0);  // the body ran on the handle's device, the caller's is back
+    syncs = 0;
+    EXPECT(run_call(&h, [&] { EXPECT(!h.mu.try_lock()); }) == 0 && syncs == 1 && unlocked(h));
+    syncs = 0;
+    EXPECT(run_call(&h, [] { throw DevErr{hipErrorOutOfMemory}; }) == -102 && syncs == 1 && unlocked(h));
+    syncs = 0;
+    EXPECT(run_call(&h, []() -> int { throw std::bad_alloc(); }) == -2 && syncs == 1 && unlocked(h));
+    syncs = 0;
+    EXPECT(run_call(&h, [] { foreign([] { throw 5; }); }) == -1099 && syncs == 1 && unlocked(h));
+    EXPECT(run_call(&h, [] { return 0; }) == 0 && device == 0);
+    // buffers
+    {
+        DevBuf b;
+        b.ensure(100);
+        void* first = b.p;
+        b.ensure(50);
+        EXPECT(b.p == first && b.cap == 100 && mallocs == 1 && frees == 0);
+        b.ensure(200);
+        EXPECT(b.cap == 200 && mallocs == 2 && frees == 1);
+        b.drop();
+        EXPECT(!b.p && b.cap == 0 && frees == 2);
+        ScopedBuf s;
+        s.alloc(0);
+        EXPECT(s.p && mallocs == 3);
+    }
+    EXPECT(frees == 3);
+    EXPECT(blocks(0) == 0 && blocks(1) == 1 && blocks(256) == 1 && blocks(257) == 2 && blocks(65, 64) == 2);
+    EXPECT(next_pow2(0) == 1 && next_pow2(1) == 1 && next_pow2(3) == 4 && next_pow2(4096) == 4096 && next_pow2(4097) == 8192);
+    // the frame of a creation
+    int err = 0;
+    Handle* made = create_handle<Handle>(5, &err, [&](Handle* c) { c->made = device == 5 && c->device == 5; c->buf.ensure(8); });
+    EXPECT(made && made->made && err == 0 && device == 0 && Handle::live == 2);
+    delete made;
+    err = 0;
+    EXPECT(!create_handle<Handle>(5, &err, [](Handle* c) { c->buf.ensure(8); DEV_TRY(hipErrorOutOfMemory); }) && err == -102);
+    err = 0;
+    EXPECT(!create_handle<Handle>(5, &err, [](Handle*) { throw std::bad_alloc(); }) && err == -4);
+    EXPECT(Handle::live == 1 && device == 0 && mallocs == frees);  // what did not make it was deleted
+    printf("fails %d\n", fails);
+    return fails != 0;
+}
+''')
+    exe = tmp_path / "hostcall"
+    subprocess.check_call([cxx, "-O1", "-std=c++17", "-D__HIP_PLATFORM_AMD__", "-I", os.path.join(ROOT, "rust-kzg_amd", "csrc"),
+                           "-I", os.path.join(rocm, "include"), str(src), "-o", str(exe), "-lpthread"])
+    res = subprocess.run([str(exe)], capture_output=True, text=True)
+    assert res.returncode == 0 and "fails 0" in res.stdout, res.stdout + res.stderr
+
+
 @pytest.mark.parametrize("portable", [False, True])
 def test_host_sha256_both_code_paths_against_hashlib(tmp_path, portable):
     """csrc/sha256.h hashes the Fiat-Shamir transcripts of host-buffer calls (kzg/src/eip_4844.rs:236-238, :920-945): its
@@ -757,6 +1105,133 @@ def test_host_g1_serialisation_and_subgroup_test_against_the_oracle(tmp_path, or
         L.og1_mul(C.byref(m), C.byref(a), C.byref(kf))
         want = [comp(d).hex(), comp(s).hex(), comp(d).hex(), comp(O.G1()).hex(), comp(m).hex()]
         assert sums[5 * i:5 * i + 5] == want, i
+
+
+def test_host_p1_to_affine_and_its_batch_against_the_oracle(tmp_path, oracle):
+    """csrc/host_g1.h, host_p1_to_affine and host_p1_to_affine_batch (the setup points of kzgamd_kzg_new, the table
+    points of kzgamd_fk20_new and of the EIP-7594 cell proofs, the base of kzgamd_g1_mul_batch): n = 0, 1 (the identity,
+    a point), 2, and 65 with the identity first, last, in the middle, in every slot in turn and everywhere; points with
+    Z = 1 and with Z != 1; the same points through a strided, reversed `point_at`.  The batch is bit-equal to the
+    single-point function (checked in the program), and both to the oracle's affine coordinates; the identity is (0, 0)
+    in the batch and leaves x, y alone in the single form."""
+    import random
+    import shutil
+
+    import oracle_ffi as O
+
+    L = oracle.lib()
+    rnd = random.Random(1729)
+    g = O.G1()
+    L.og1_generator(C.byref(g))
+    pool = [O.G1()]  # index 0: the identity (Z == 0)
+    for i in range(65):
+        p, kf = O.G1(), O.fr_from_int(rnd.randrange(1, O.R))
+        L.og1_mul(C.byref(p), C.byref(g), C.byref(kf))
+        if i % 8 == 0:  # Z = 1
+            a = O.G1Affine()
+            L.og1_to_affine(C.byref(a), C.byref(p))
+            p = O.G1()
+            L.og1_from_affine(C.byref(p), C.byref(a))
+        elif i % 8 == 1:  # another Z of the same point
+            d = O.G1()
+            L.og1_add_or_dbl(C.byref(d), C.byref(p), C.byref(g))
+            p = d
+        pool.append(p)
+    one = bytes(g.z)
+    assert sum(1 for p in pool[1:] if bytes(p.z) == one) >= 8 and sum(1 for p in pool[1:] if bytes(p.z) != one) >= 40
+    full = list(range(1, 66))
+    cases = [[], [0], [5], [1, 2], [0, 3], [3, 0], [0, 0], full, [0] * 65]
+    for slot in range(65):  # the identity in every slot in turn: first, middle and last among them
+        cases.append(full[:slot] + [0] + full[slot + 1:])
+    cases.append([0] + full[1:32] + [0] + full[33:64] + [0])
+    text = "".join("pt %s\n" % bytes(p).hex() for p in pool) + "".join("case %s\n" % " ".join(map(str, c)) for c in cases)
+
+    cxx = shutil.which("g++") or shutil.which("clang++") or "/opt/rocm/lib/llvm/bin/clang++"
+    src = tmp_path / "affine.cpp"
+    src.write_text(r'''
+#include <cstdio>
+#include <cstdlib>
+#include <string>
+#include <vector>
+#include "host_g1.h"
+using namespace kzgamd;
+static void hex(const void* p, size_t n) { for (size_t i = 0; i < n; ++i) printf("%02x", ((const uint8_t*)p)[i]); }
+int main() {
+    std::vector<blst_p1> pool;
+    std::string line;
+    int c, bad = 0;
+    while (true) {
+        line.clear();
+        while ((c = getchar()) != EOF && c != '\n') line.push_back((char)c);
+        if (line.empty() && c == EOF) break;
+        if (line.rfind("pt ", 0) == 0) {  // a Jacobian point, the bytes of a blst_p1
+            blst_p1 p;
+            for (size_t i = 0; i < sizeof p; ++i) { unsigned v; sscanf(line.c_str() + 3 + 2 * i, "%2x", &v); ((uint8_t*)&p)[i] = (uint8_t)v; }
+            ff::Fp xy[2];
+            memset(xy, 0xa5, sizeof xy);
+            const ff::Fp before = xy[0];
+            const bool inf = host_p1_to_affine(&p, xy[0], xy[1]);
+            if (inf && (xy[0] != before || xy[1] != before)) ++bad;  // the identity leaves x and y alone
+            printf("one %d ", inf ? 1 : 0);
+            hex(xy, sizeof xy);
+            printf("\n");
+            pool.push_back(p);
+        } else if (line.rfind("case", 0) == 0) {  // indices into the pool
+            std::vector<blst_p1> pts;
+            char* q = &line[4];
+            while (*q) {
+                char* e;
+                const long v = strtol(q, &e, 10);
+                if (e == q) break;
+                pts.push_back(pool[(size_t)v]);
+                q = e;
+            }
+            const size_t n = pts.size();
+            std::vector<ff::Fp> aff(2 * n + 1), strided(2 * n + 1);
+            memset(aff.data(), 0x5a, aff.size() * sizeof(ff::Fp));
+            memset(strided.data(), 0x5a, strided.size() * sizeof(ff::Fp));
+            const ff::Fp guard = aff[2 * n];
+            host_p1_to_affine_batch(aff.data(), n, [&](size_t i) { return &pts[i]; });
+            // the same points at every third slot of a longer array, in reverse order
+            std::vector<blst_p1> wide(3 * n + 1);
+            memset(wide.data(), 0x33, wide.size() * sizeof(blst_p1));
+            for (size_t i = 0; i < n; ++i) wide[3 * (n - 1 - i) + 1] = pts[i];
+            host_p1_to_affine_batch(strided.data(), n, [&](size_t i) { return &wide[3 * (n - 1 - i) + 1]; });
+            if (memcmp(aff.data(), strided.data(), aff.size() * sizeof(ff::Fp)) || aff[2 * n] != guard) ++bad;  // nothing past 2n written
+            for (size_t i = 0; i < n; ++i) {  // bit-equal to the single-point function
+                ff::Fp x = ff::Fp::zero(), y = ff::Fp::zero();
+                host_p1_to_affine(&pts[i], x, y);
+                if (x != aff[2 * i] || y != aff[2 * i + 1]) ++bad;
+            }
+            printf("aff ");
+            hex(aff.data(), 2 * n * sizeof(ff::Fp));
+            printf("\n");
+        }
+    }
+    printf("bad %d\n", bad);
+    return bad != 0;
+}
+''')
+    exe = tmp_path / "affine"
+    subprocess.check_call([cxx, "-O2", "-std=c++17", "-I", os.path.join(ROOT, "rust-kzg_amd", "csrc"), str(src), "-o", str(exe)])
+    res = subprocess.run([str(exe)], input=text, capture_output=True, text=True)
+    assert res.returncode == 0 and "bad 0" in res.stdout, res.stdout[-2000:] + res.stderr
+    out = res.stdout.split("\n")
+    ones, affs = [ln.split() for ln in out if ln.startswith("one ")], [ln[4:] for ln in out if ln.startswith("aff ")]
+    assert len(ones) == len(pool) and len(affs) == len(cases)
+    want = []
+    for i, p in enumerate(pool):
+        if i == 0:
+            want.append(bytes(96).hex())
+            assert ones[i][1] == "1" and ones[i][2] == "a5" * 96
+            continue
+        a = O.G1Affine()
+        L.og1_to_affine(C.byref(a), C.byref(p))
+        assert L.og1_affine_on_curve(C.byref(a))
+        want.append(bytes(a).hex())
+        assert ones[i][1] == "0" and ones[i][2] == want[i], i
+    for c, got in zip(cases, affs):
+        assert got == "".join(want[i] for i in c), c
 
 
 def test_glv_split_identity_and_bounds_on_the_host(tmp_path):
