@@ -318,4 +318,18 @@ FF_HD fp28::Fe to28(const Fe& a) {
     return r;
 }
 
+// the same for "unsigned" limbs (from28 of a normalized value: a table slot), where the carry pass above has nothing to
+// carry: bit re-slicing only, the exact inverse of from28, with no chain of dependent additions in front of it
+FF_HD fp28::Fe to28_unsigned(const Fe& a) {
+    fp28::Fe r;
+#pragma unroll
+    for (int j = 0; j < fp28::L; ++j) {
+        const int bit = 28 * j, i = bit / 30, s = bit - 30 * i;
+        u32 w = (u32)a.v[i] >> s;
+        if (i + 1 < L && 30 - s < 28) w |= (u32)a.v[i + 1] << (30 - s);
+        r.v[j] = j < fp28::L - 1 ? (w & fp28::MASK) : w;
+    }
+    return r;
+}
+
 }  // namespace fp30s

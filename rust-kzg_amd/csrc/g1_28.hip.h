@@ -30,7 +30,9 @@ struct alignas(16) AffPt {
 };
 static_assert(sizeof(AffPt) == 128, "AffPt slot");
 
-// wide-table slot: x and y in fp28 form (canonical residues) in a 128-byte, cache-line-aligned slot.
+// The wide table's former slot: x and y in fp28 form (canonical residues) in a 128-byte, cache-line-aligned slot.  The
+// table is made of g1s::WidePt30 now (g1_30s.hip.h: the same integers in the limbs of the accumulation chain); this
+// type stays for the stand-alone kernel tests/test_fp30s_codegen_cpu.py compiles against it.
 // A valid curve point never has x = y = 0 (y^2 = x^3 + 4), so all-zero encodes infinity.
 // Measured alternatives on MI355X (accumulation kernel, c = 14): 96-byte bit-packed slots +6 % (unpacking),
 // 112-byte unpadded slots +2 % (gathers straddle cache lines); the padded slot is the fastest.

@@ -42,7 +42,7 @@
 using ff::u32;
 using ff::u64;
 using g1::AffPt;
-using g1::WidePt;
+using WidePt = g1s::WidePt30;  // the wide table's slot: x, y in the limbs of the accumulation chain (g1_30s.hip.h)
 using g1::Xyzz;
 
 namespace {
@@ -1551,7 +1551,8 @@ __global__ void __launch_bounds__(128) k_fbw_chain(Xyzz* __restrict__ tmp, const
     }
 }
 
-// XYZZ -> affine table slots, one Montgomery batch inversion per FBW_INV consecutive entries
+// XYZZ -> affine table slots, one Montgomery batch inversion per FBW_INV consecutive entries.  A slot holds the canonical
+// x and y re-sliced into 13 x 30-bit limbs (g1s::WidePt30): once per entry here instead of once per read in k_fbw_accum.
 constexpr int FBW_INV = 32;
 __global__ void __launch_bounds__(128) k_fbw_affine(WidePt* __restrict__ wide, const Xyzz* __restrict__ tmp,
                                                     fp28::Fe* __restrict__ pref, size_t count) {
@@ -1568,19 +1569,16 @@ __global__ void __launch_bounds__(128) k_fbw_affine(WidePt* __restrict__ wide, c
     fp28::Fe inv = g1io::inverse(p);
     for (size_t k = hi; k-- > lo;) {
         Xyzz q = tmp[k];
-        WidePt o;
-        o.pad[0] = o.pad[1] = o.pad[2] = o.pad[3] = 0;
-        if (g1::is_inf(q)) {
-            o.x = fp28::zero();
-            o.y = fp28::zero();
-            o.pad[0] = 1;  // infinity flag
-        } else {
+        fp28::Fe x = fp28::zero(), y = fp28::zero();
+        u32 flags = 1;  // infinity flag
+        if (!g1::is_inf(q)) {
             fp28::Fe zi = fp28::mul(inv, pref[k]);                  // 1 / (ZZ*ZZZ)
             inv = fp28::mul(inv, fp28::mul(q.zz, q.zzz));
-            o.x = fp28::canon(fp28::mul(q.x, fp28::mul(zi, q.zzz)));  // X / ZZ
-            o.y = fp28::canon(fp28::mul(q.y, fp28::mul(zi, q.zz)));   // Y / ZZZ
+            x = fp28::canon(fp28::mul(q.x, fp28::mul(zi, q.zzz)));  // X / ZZ
+            y = fp28::canon(fp28::mul(q.y, fp28::mul(zi, q.zz)));   // Y / ZZZ
+            flags = 0;
         }
-        wide[k] = o;
+        wide[k] = g1s::pack_slot(x, y, flags);
     }
 }
 
@@ -1706,8 +1704,9 @@ __global__ void __launch_bounds__(256) k_fbw_accum(DigitParams P, const u32* __r
                 for (int q = 0; q < 4; ++q) {
                     const u32 e = e4[q];
                     if (e == FBW_SKIP) continue;
-                    const WidePt pk = wide[(((size_t)(w4 + q) * P.row_stride + seg0 + i) << sh) + (e & 0x7fffffffu)];
-                    if (pk.pad[0]) continue;  // multiple of a base at infinity
+                    WidePt pk = wide[(((size_t)(w4 + q) * P.row_stride + seg0 + i) << sh) + (e & 0x7fffffffu)];
+                    if (pk.flags) continue;  // multiple of a base at infinity
+                    g1s::hold(pk);
                     g1s::chain_add(acc, st, pk.x, pk.y, 0u - (e >> 31), sd);
                 }
             }
@@ -1725,18 +1724,17 @@ __global__ void __launch_bounds__(256) k_fbw_accum(DigitParams P, const u32* __r
                     carry = 1;
                 }
                 if (d == 0) continue;
-                const WidePt pk = wide[(((size_t)w * P.row_stride + seg0 + i) << sh) + (d - 1)];
-                if (pk.pad[0]) continue;  // multiple of a base at infinity
+                WidePt pk = wide[(((size_t)w * P.row_stride + seg0 + i) << sh) + (d - 1)];
+                if (pk.flags) continue;  // multiple of a base at infinity
+                g1s::hold(pk);
                 g1s::chain_add(acc, st, pk.x, pk.y, 0u - neg, sd);
             }
         }
     }
     Xyzz sum;
-    g1s::to_xyzz28(sum, acc, st, sd);
-    if (GLV && part && st != g1::CHAIN_EMPTY) {
-        sum.x = fp28::mul(sum.x, beta28());                     // psi(X, Y, ZZ, ZZZ) = (beta X, -Y, ZZ, ZZZ)
-        sum.y = fp28::mul(fp28::neg<8>(sum.y), fp28::one());    // -Y, back under the 2p bound
-    }
+    // GLV: the k2 lanes owe their sum psi(X, Y, ZZ, ZZZ) = (beta X, -Y, ZZ, ZZZ); it rides in the constants of the way back
+    if (GLV) g1s::to_xyzz28(sum, acc, st, part, sd);
+    else g1s::to_xyzz28(sum, acc, st, sd);
     partial[t] = sum;
 }
 
@@ -1769,8 +1767,8 @@ __global__ void __launch_bounds__(256) k_fbw_accum_quad(DigitParams P, const u32
         const u32 e = k == 0 ? v.x : k == 1 ? v.y : k == 2 ? v.z : v.w;
         if (e == FBW_SKIP) continue;
         const WidePt pk = wide[(((size_t)w * P.row_stride + seg0 + i) << sh) + (e & 0x7fffffffu)];
-        if (pk.pad[0]) continue;  // multiple of a base at infinity
-        fp28::Fe x = pk.x, y = pk.y;
+        if (pk.flags) continue;  // multiple of a base at infinity
+        fp28::Fe x = fp30s::to28_unsigned(pk.x), y = fp30s::to28_unsigned(pk.y);  // bits only: the inverse of the table's from28
         if (e >> 31) y = fp28::neg<2>(y);
         grp::madd_body4(acc, x, y, r);
     }
