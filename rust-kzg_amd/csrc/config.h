@@ -22,7 +22,7 @@ enum TuneId {
     // wide-table (fixed-base) path of the MSM
     T_SPL, T_NO_WIDE_TAIL, T_NO_HYBRID_FOLD, T_NO_WIDE_TREE, T_QUAD_ACCUM_MAX, T_HYBRID_MAX, T_WIDE_FOLD_MAX, T_SPL1_MAX, T_BLOCKSUM_THREADS,
     // bucket engine
-    T_LGC, T_GROUPS, T_TAIL_PIECES, T_SUB_STREAMS, T_SUB_PRIO, T_SUB_LARGE, T_SORT_AHEAD, T_TILE_ROWS, T_TILE_QUAD, T_DIGIT_MIN_LOG, T_FINE_BITS, T_ONE_LEVEL_SORT, T_TREE_TAIL, T_FLAT_DIGITS, T_DIRECT_SCATTER, T_SCATTER_ATOMICS,
+    T_LGC, T_SUB_STREAMS, T_SUB_PRIO, T_SUB_LARGE, T_TILE_ROWS, T_TILE_QUAD, T_DIGIT_MIN_LOG, T_FINE_BITS, T_ONE_LEVEL_SORT, T_TREE_TAIL, T_FLAT_DIGITS, T_DIRECT_SCATTER, T_SCATTER_ATOMICS,
     // shape of a handle
     T_WINDOW, T_WINDOW_PREPARED, T_FIXED_AS_VARIABLE_MIN, T_GLV, T_FBW_GLV,
     // concurrent host-buffer callers of one prepared handle (B1)
@@ -53,12 +53,9 @@ inline const TuneKey* tune_keys() {
         {"spl1_max", 0, 0, 1 << 20, "MSMs per call that get a lane per (scalar, half) (0 = 8)"},
         {"blocksum_threads", 0, 0, 256, "threads of k_blocksum: 64, 128 or 256 (0 = by batch size)"},
         {"lgc", 0, 0, 8, "log2 of the accumulation chunk of the bucket engine (0 = by size; 2 ... 8)"},
-        {"groups", 0, 0, 4, "window groups of the bucket engine on their own streams (0 = one)"},
-        {"tail_pieces", 0, 0, 4, "a single large MSM accumulates its window sets in this many pieces, the reduction of a piece beside the accumulation of the next (0, 1 = one piece; measured: nothing gained)"},
         {"sub_streams", 6, 0, 6, "a batch of large MSMs runs as sub-batches whose accumulations stay on the caller's stream while the sort and the reduction chains of each run on one of this many high-priority side streams (own workspaces) beside another sub-batch's accumulation (0 = one stream, one workspace); MSMs below 2^18 points unless sub_large = 1"},
         {"sub_prio", 1, 0, 1, "1: the side streams of sub_streams are created with the device's highest stream priority, 0: with the default priority"},
         {"sub_large", 0, 0, 1, "1: the side streams of sub_streams also for batches of MSMs of 2^18 points and more (measured slower: nothing runs well beside a chip-filling accumulation)"},
-        {"sort_ahead", 0, 0, 1, "1: a batch of MSMs of 2^18 points and more runs as sub-batches whose SORT runs on one of two side streams beside the limb-parallel chains of the previous sub-batch's reduction (after its tile sums; nothing beside an accumulation); measured +-1 %: off"},
         {"tile_rows", 0, 0, 32, "rows of 32 buckets per tile of the tiled bucket reduction: 32 (a 512-lane workgroup, a CU each) or 16 (256 lanes, a wave per SIMD); 0 = 32"},
         {"tile_quad", 1, 0, 1, "1: the tree levels of the tiled bucket reduction that keep at most a quarter of the lanes busy run four lanes per addition (an addition 4 multiplications deep instead of 14); 0: one lane per addition throughout"},
         {"digit_min_log", 14, 10, 30, "log2 of the smallest bucket count per set that takes the digit-decomposed (tiled) bucket reduction instead of the (sum, weighted sum) tree (round 6 measured 10 ... 13 on 2^10 ... 2^18 points: the tree is faster below 2^14 buckets)"},
@@ -186,21 +183,12 @@ struct Options {
         }
         return true;
     }
-    // keys that do not combine: each is a form of the same stretch of the engine (how a batch, or a lone MSM, is cut)
-    bool consistent(std::string* err) const {
-        if (t[T_SORT_AHEAD] && (t[T_GROUPS] > 1 || t[T_TAIL_PIECES] > 1 || t[T_SUB_LARGE])) {
-            if (err) *err = "tuning: sort_ahead does not combine with groups, tail_pieces or sub_large";
-            return false;
-        }
-        return true;
-    }
-    // defaults < environment < cfg; false (with *err) when a string does not parse, the keys contradict each other or cfg
-    // is malformed
+    // defaults < environment < cfg; false (with *err) when a string does not parse or cfg is malformed
     static bool resolve(Options& o, const KzgAmdConfig* cfg, std::string* err) {
         o = Options();
         if (!o.parse(getenv("KZGAMD_TUNING"), err)) return false;
         if (const char* e = getenv("KZGAMD_FBW_MAX_GB")) o.table_budget_gb = atof(e);
-        if (!cfg) return o.consistent(err);
+        if (!cfg) return true;
         if (cfg->struct_size < offsetof(KzgAmdConfig, tuning) + sizeof(cfg->tuning)) {
             if (err) *err = "KzgAmdConfig.struct_size is not that of any version of the struct";
             return false;
@@ -208,7 +196,7 @@ struct Options {
         o.device = cfg->device;
         if (cfg->table_budget_bytes == KZGAMD_NO_TABLES) o.table_budget_gb = 0;
         else if (cfg->table_budget_bytes) o.table_budget_gb = (double)cfg->table_budget_bytes / 1e9;
-        return o.parse(cfg->tuning, err) && o.consistent(err);
+        return o.parse(cfg->tuning, err);
     }
 };
 

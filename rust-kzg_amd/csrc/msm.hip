@@ -2060,13 +2060,13 @@ struct Workspace {
 // The tuning keys of config.h this engine reads, copied ONCE when a handle is created (an enqueue never looks anything
 // up); every variant computes the same result a different way.
 struct MsmTuning {
-    int spl = 0, hybrid_max = 0, wide_fold_max = 0, spl1_max = 0, blocksum_threads = 0, lgc = 0, groups = 0, fine_bits = 0;
+    int spl = 0, hybrid_max = 0, wide_fold_max = 0, spl1_max = 0, blocksum_threads = 0, lgc = 0, fine_bits = 0;
     bool no_wide_tail = false, no_hybrid_fold = false, no_wide_tree = false;
     int quad_accum_max = 4;
     bool one_level_sort = false, tree_tail = false, flat_digits = false, direct_scatter = false, scatter_atomics = false;
     bool combine = true;
     int combine_lanes = 3, combine_gather_min = 6, combine_gather_us = 60;
-    int tail_pieces = 0, sub_streams = 6, tile_rows = 0, tile_quad = 1, digit_min_log = 14, sub_prio = 1, sub_large = 0, sort_ahead = 0;
+    int sub_streams = 6, tile_rows = 0, tile_quad = 1, digit_min_log = 14, sub_prio = 1, sub_large = 0;
     static MsmTuning from(const kzgamd::Options& o) {
         using namespace kzgamd;
         MsmTuning t;
@@ -2080,7 +2080,6 @@ struct MsmTuning {
         t.spl1_max = (int)o.t[T_SPL1_MAX];
         t.blocksum_threads = (int)o.t[T_BLOCKSUM_THREADS];
         t.lgc = (int)o.t[T_LGC];
-        t.groups = (int)o.t[T_GROUPS];
         t.fine_bits = (int)o.t[T_FINE_BITS];
         t.one_level_sort = o.t[T_ONE_LEVEL_SORT] != 0;
         t.tree_tail = o.t[T_TREE_TAIL] != 0;
@@ -2091,14 +2090,12 @@ struct MsmTuning {
         t.combine_lanes = (int)o.t[T_COMBINE_LANES];
         t.combine_gather_min = (int)o.t[T_COMBINE_GATHER_MIN];
         t.combine_gather_us = (int)o.t[T_COMBINE_GATHER_US];
-        t.tail_pieces = (int)o.t[T_TAIL_PIECES];
         t.sub_streams = (int)o.t[T_SUB_STREAMS];
         t.tile_rows = (int)o.t[T_TILE_ROWS];
         t.tile_quad = (int)o.t[T_TILE_QUAD];
         t.digit_min_log = (int)o.t[T_DIGIT_MIN_LOG];
         t.sub_prio = (int)o.t[T_SUB_PRIO];
         t.sub_large = (int)o.t[T_SUB_LARGE];
-        t.sort_ahead = (int)o.t[T_SORT_AHEAD];
         return t;
     }
 };
@@ -2147,7 +2144,7 @@ struct kzgamd::MsmContext {
         if (st == ws_owner) return ws;
         for (auto& e : ws_extra)
             if (e.first == st) return *e.second;
-        if (ws_extra.size() >= 23) return ws;  // more streams than workspaces: shared, see WsUse in msm_enqueue
+        if (ws_extra.size() >= 23) return ws;  // more streams than workspaces: shared, see WsUse
         ws_extra.emplace_back(st, new Workspace());
         return *ws_extra.back().second;
     }
@@ -2158,22 +2155,10 @@ struct kzgamd::MsmContext {
     // which rotate over the sub-batches, each with its own workspace.  The side streams have the highest priority the
     // device offers: at equal priority the accumulation's waves hold every register of every SIMD and a reduction
     // kernel launched beside it waits for slots (traced in round 6: k_tile_sums_loop 2.8 ms instead of 0.32, the next
-    // sub-batch's accumulation waiting behind it).  accum_on / ev_sorted / ev_accd are what msm_enqueue's k_accum launch
-    // site reads.
+    // sub-batch's accumulation waiting behind it).  ev_sorted / ev_accd reach the k_accum launch site in a SubLink.
     static constexpr int MAXSUB = 6;
     hipStream_t sub_stream[MAXSUB] = {};
-    hipEvent_t ev_sub_fork = nullptr, ev_sub_join[MAXSUB] = {}, ev_sorted[MAXSUB] = {}, ev_accd[MAXSUB] = {}, ev_gate[MAXSUB] = {};
-    bool accum_redirect = false;     // set by the sub-batch loop: this enqueue's k_accum goes to accum_on ...
-    bool tail_on_accum = false;      // ... and so does everything after it (sort-ahead form: only the SORT stays on the side stream)
-    hipStream_t accum_on = nullptr;  // ... the caller's stream (which may be the null stream)
-    hipEvent_t accum_ready = nullptr, accum_done = nullptr;
-    hipEvent_t sort_gate = nullptr;  // sort-ahead form: recorded where the NEXT sub-batch's sort may start (after this one's tile sums)
-    bool in_sub_batch = false;  // the enqueue in progress is a sub-batch: it is not cut again
-    // window-group pipeline of the variable-base engine: one auxiliary stream per group, events to fork from /
-    // join into the caller's stream and to order the digit and accumulation kernels across groups
-    static constexpr int MAXG = 4;
-    hipStream_t aux[MAXG] = {nullptr, nullptr, nullptr, nullptr};
-    hipEvent_t ev_fork = nullptr, ev_dig[MAXG] = {}, ev_acc[MAXG] = {}, ev_done[MAXG] = {};
+    hipEvent_t ev_sub_fork = nullptr, ev_sub_join[MAXSUB] = {}, ev_sorted[MAXSUB] = {}, ev_accd[MAXSUB] = {};
     bool profile = false;
     // per enqueue: start, accum-begin, accum-end, end (events on the launch stream)
     std::vector<hipEvent_t> ev;
@@ -2246,20 +2231,12 @@ struct kzgamd::MsmContext {
         }
         for (auto& e : ev)
             if (e) (void)hipEventDestroy(e);
-        if (ev_fork) (void)hipEventDestroy(ev_fork);
         if (ev_sub_fork) (void)hipEventDestroy(ev_sub_fork);
         for (int k = 0; k < MAXSUB; ++k) {
             if (ev_sub_join[k]) (void)hipEventDestroy(ev_sub_join[k]);
             if (ev_sorted[k]) (void)hipEventDestroy(ev_sorted[k]);
             if (ev_accd[k]) (void)hipEventDestroy(ev_accd[k]);
-            if (ev_gate[k]) (void)hipEventDestroy(ev_gate[k]);
             if (sub_stream[k]) (void)hipStreamDestroy(sub_stream[k]);
-        }
-        for (int g = 0; g < MAXG; ++g) {
-            if (ev_dig[g]) (void)hipEventDestroy(ev_dig[g]);
-            if (ev_acc[g]) (void)hipEventDestroy(ev_acc[g]);
-            if (ev_done[g]) (void)hipEventDestroy(ev_done[g]);
-            if (aux[g]) (void)hipStreamDestroy(aux[g]);
         }
         if (stream) (void)hipStreamDestroy(stream);
     }
@@ -2303,6 +2280,19 @@ static void build_wide_table(MsmContext* ctx) {
     tmp.release();
     pref.release();
     ctx->fbw = true;
+}
+
+// whether every one of the n bases at d_bases lies in the r-torsion subgroup (one launch on the handle's stream, awaited)
+static bool bases_in_g1(MsmContext* ctx, const AffPt* d_bases, size_t n) {
+    DevBuf<int> bad;
+    bad.ensure(1);
+    HIP_TRY(hipMemsetAsync(bad.p, 0, sizeof(int), ctx->stream));
+    hipLaunchKernelGGL(k_bases_in_g1, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, ctx->stream, d_bases, n, bad.p);
+    int nbad = 1;
+    HIP_TRY(hipMemcpyAsync(&nbad, bad.p, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    bad.release();
+    return nbad == 0;
 }
 
 // uploads points (host or device pointer), builds the fixed-base rows when `prepare`
@@ -2370,16 +2360,7 @@ MsmContext* msm_create(const void* points, size_t n, bool points_on_device, bool
         };
         if (ctx->glv && g1_policy == G1_CHECK) {
             bases_in(0);
-            DevBuf<int> bad;
-            bad.ensure(1);
-            HIP_TRY(hipMemsetAsync(bad.p, 0, sizeof(int), ctx->stream));
-            hipLaunchKernelGGL(k_bases_in_g1, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, ctx->stream, (const AffPt*)row0.p, n,
-                               bad.p);
-            int nbad = 1;
-            HIP_TRY(hipMemcpyAsync(&nbad, bad.p, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-            HIP_TRY(hipStreamSynchronize(ctx->stream));
-            bad.release();
-            if (nbad != 0) ctx->glv = false;  // a base outside G1: no split (row0 keeps its 2n slots, n are used)
+            if (!bases_in_g1(ctx, row0.p, n)) ctx->glv = false;  // a base outside G1: no split (row0 keeps its 2n slots, n are used)
         }
         if (as_variable && ctx->glv) {
             prepare = false;
@@ -2397,19 +2378,7 @@ MsmContext* msm_create(const void* points, size_t n, bool points_on_device, bool
             if (choose_wide_window(n, true, &dummy, ctx->opt.table_budget_gb) != 0) {
                 // a wide table fits: its GLV form needs every base in the r-torsion subgroup (psi(P) = [x^2]P holds only
                 // there; FsG1::from_bytes does not check it, blst/src/types/g1.rs:65-87) — test the bases, once
-                bool in_g1 = false;
-                if (ctx->opt.t[T_FBW_GLV] != 0) {
-                    DevBuf<int> bad;
-                    bad.ensure(1);
-                    HIP_TRY(hipMemsetAsync(bad.p, 0, sizeof(int), ctx->stream));
-                    hipLaunchKernelGGL(k_bases_in_g1, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, ctx->stream,
-                                       (const AffPt*)row0.p, n, bad.p);
-                    int nbad = 1;
-                    HIP_TRY(hipMemcpyAsync(&nbad, bad.p, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-                    HIP_TRY(hipStreamSynchronize(ctx->stream));
-                    bad.release();
-                    in_g1 = nbad == 0;
-                }
+                const bool in_g1 = ctx->opt.t[T_FBW_GLV] != 0 && bases_in_g1(ctx, row0.p, n);
                 cw = choose_wide_window(n, in_g1, &wide_glv, ctx->opt.table_budget_gb);
             }
         }
@@ -2491,299 +2460,196 @@ void g1_compress_xyzz(void* d_out48, const void* d_xyzz, size_t count, hipStream
     HIP_TRY(hipGetLastError());
 }
 
-// enqueue nbatch MSMs over the first npoints bases; d_scalars / d_out device pointers
-// reserve_only: size and allocate the workspace `stream` will use for this shape, launch nothing (hipMalloc
-// synchronises the device, so callers that must not stall a running pipeline reserve during set-up)
-void msm_enqueue(MsmContext* ctx, void* d_out, const void* d_scalars, size_t npoints, size_t nbatch, int mont,
-                 hipStream_t stream, int out_mode, bool reserve_only, size_t nseg) {
-    if (npoints * (nseg ? nseg : 1) > ctx->n) throw HipErr{hipErrorInvalidValue, "npoints exceeds the prepared size"};
-    if ((nseg || out_mode == OUT_XYZZ) && !ctx->fbw)
-        throw HipErr{hipErrorInvalidValue, "segmented / XYZZ-output MSMs need the wide-table path"};
-    if (nbatch == 0) return;
+// Workspaces are per stream, but streams can outnumber them (and the handle's own stream shares the first one):
+// whoever gets a workspace last used on another stream first waits for that use to finish on the GPU.
+// a workspace that only one stream ever uses (every entry of ws_extra) is ordered by that stream: no events —
+// two runtime calls less per enqueue, and such an enqueue can be captured into a graph
+struct WsUse {
+    Workspace& w;
+    hipStream_t st;
+    bool shared;
+    WsUse(Workspace& w_, hipStream_t st_, bool shared_) : w(w_), st(st_), shared(shared_) {
+        if (shared && w.last_done && w.last_stream != st) (void)hipStreamWaitEvent(st, w.last_done, 0);
+    }
+    ~WsUse() {
+        if (!shared) return;
+        if (!w.last_done && hipEventCreateWithFlags(&w.last_done, hipEventDisableTiming) != hipSuccess) w.last_done = nullptr;
+        if (w.last_done) (void)hipEventRecord(w.last_done, st);
+        w.last_stream = st;
+    }
+};
+
+// the four profile events of one enqueue (MsmContext::ev), the first recorded on `stream`; null when not profiling
+static hipEvent_t* profile_begin(MsmContext* ctx, hipStream_t stream) {
+    if (!ctx->profile || ctx->ev_used + 4 > MsmContext::EV_MAX) return nullptr;
+    while (ctx->ev.size() < ctx->ev_used + 4) {
+        hipEvent_t e;
+        HIP_TRY(hipEventCreate(&e));
+        ctx->ev.push_back(e);
+    }
+    hipEvent_t* pev = &ctx->ev[ctx->ev_used];
+    HIP_TRY(hipEventRecord(pev[0], stream));
+    return pev;
+}
+
+// wide-table path: gather + add, then one block-sum per MSM
+static void enqueue_wide(MsmContext* ctx, Workspace& ws, void* d_out, const void* d_scalars, size_t npoints, size_t nbatch,
+                         int mont, hipStream_t stream, int out_mode, bool reserve_only, size_t nseg) {
+    const int c = ctx->c;
+    const int nwin = ctx->nwin;
+    const size_t nb = ctx->nb;
+    // scalars per lane: 4 for large batches — a quarter of the partial sums for k_blocksum to fold against one
+    // more real addition per lane (the first addition into an empty accumulator is free): +1.0 % at 1024 blobs
+    // (87.1 k -> 88.0 k commitments/s, three alternating runs on one box); 1 for small batches, where the lanes
+    // are needed for latency
+    int spl = nbatch >= 256 ? 4 : 1;
+    // segment MSMs (FK20: 128 MSMs of 64 scalars per blob): from 128 blobs on, 16 scalars per lane — 320 additions
+    // per lane instead of 80 and four partial sums per MSM instead of 16 for k_lane_sum (0.23 -> 0.05 ms at 256
+    // blobs); the accumulation itself takes the same 6.2 - 6.4 ms either way (measured, profiles/NOTES.md §16)
+    if (nseg && ctx->fbw_glv && npoints % 32 == 0) {
+        if (nbatch * npoints >= ((size_t)1 << 21)) spl = 16;       // 256 blobs: 131 072 lanes, two waves per SIMD
+        else if (nbatch * npoints >= ((size_t)1 << 20)) spl = 8;  // 128 blobs: the same
+    }
+    if (ctx->tune.spl) spl = ctx->tune.spl;
+    if (spl == 3 || (spl > 4 && spl != 8 && spl != 16)) spl = 4;
+    if (!ctx->fbw_glv && spl > 4) spl = 4;
+    if (ctx->fbw_glv) spl *= 2;  // two lanes (k1 / k2 digits) per scalar group: the same number of partial sums
+    // a few MSMs over the 4096-point setup: a lane per (scalar, half) — 8 additions per lane instead of 16, twice the
+    // partial sums for the fold (limb-parallel up to WIDE_FOLD_MAX MSMs, k_blocksum above)
+    // (up to 8 MSMs: 8 commitments 0.79 -> 0.71 ms; 16 the same either way, 32 and 64 slower)
+    const size_t spl1_max = ctx->tune.spl1_max > 0 ? (size_t)ctx->tune.spl1_max : 8;
+    if (ctx->fbw_glv && nbatch <= spl1_max && npoints == 4096 && !ctx->tune.spl && !ctx->tune.no_wide_tail) spl = 1;
+    const size_t lanes = (npoints + spl - 1) / spl * (ctx->fbw_glv ? 2 : 1);
+    ws.buckets.ensure(nbatch * lanes);
+    ws.lvlM[0].ensure(nbatch);
+    if (nbatch <= 16 && lanes % 16 == 0 && lanes >= 1024) ws.lvlA[0].ensure(nbatch * 128);
+    const size_t hybrid_max = ctx->tune.hybrid_max > 0 ? (size_t)ctx->tune.hybrid_max : BSH_MAX;
+    const bool hybrid_fold = nbatch <= hybrid_max && nbatch <= BSH_CAP && lanes % (16 * 256) == 0 &&
+                             !ctx->tune.no_wide_tail && !ctx->tune.no_hybrid_fold;
+    bool bcount_new = false;
+    if (hybrid_fold) {
+        ws.bpart.ensure(BSH_CAP * (size_t)BSH_PARTS);
+        if (ws.bcount.cap < BSH_CAP) {
+            ws.bcount.ensure(BSH_CAP);
+            bcount_new = true;
+        }
+    }
+    const size_t wf_max = ctx->tune.wide_fold_max > 0 ? (size_t)ctx->tune.wide_fold_max : WIDE_FOLD_MAX;
+    const bool wide_fold = nbatch <= wf_max && (lanes == 4096 || lanes == 8192) && !ctx->tune.no_wide_tail;
+    bool wcount_new = false;
+    if (wide_fold) {
+        // k_wide_tree: lanes / 32 workgroup sums + lanes / 512 group sums per MSM, a counter per group and one per MSM
+        // (zeroed when allocated, left at zero by every launch); k_wide_fold64 (tuning key no_wide_tree): 129 cells x
+        // WFOLD parts, a counter per cell — which is more of both
+        const size_t need_p = (nbatch * 128 + nbatch) * (size_t)WFOLD, need_c = nbatch * 128 + nbatch;
+        ws.wpart.ensure(need_p);
+        if (ws.wcount.cap < need_c) {
+            ws.wcount.ensure(need_c);
+            wcount_new = true;
+        }
+    }
+    if (ctx->fbw_glv) ws.digits.ensure(nbatch * npoints * 2 * (size_t)((nwin + 3) & ~3));
+    if (bcount_new) HIP_TRY(hipMemsetAsync(ws.bcount.p, 0, BSH_CAP * sizeof(u32), stream));
+    if (wcount_new) HIP_TRY(hipMemsetAsync(ws.wcount.p, 0, ws.wcount.cap * sizeof(u32), stream));
+    if (reserve_only) return;
+    WsUse ws_use(ws, stream, &ws == &ctx->ws);
+    DigitParams P{npoints, nbatch, c, nwin, 1, mont, nb, ctx->n, 0, 0, nwin, (u32)nseg};
+    hipEvent_t* const pev = profile_begin(ctx, stream);
+    const u32* acc_in = (const u32*)d_scalars;
+    if (ctx->fbw_glv) {
+        hipLaunchKernelGGL(k_fbw_digits, dim3((unsigned)((npoints * nbatch + 255) / 256)), dim3(256), 0, stream, P,
+                           (const u32*)d_scalars, ws.digits.p);
+        acc_in = ws.digits.p;
+    }
+    if (pev) HIP_TRY(hipEventRecord(pev[1], stream));
+    const dim3 grid((unsigned)((lanes * nbatch + 255) / 256));
+#define KZG_FBW_LAUNCH(SPL_, GLV_)                                                                           \
+    hipLaunchKernelGGL((k_fbw_accum<SPL_, GLV_>), grid, dim3(256), 0, stream, P, acc_in,                         \
+                       (const WidePt*)ctx->wide.p, ws.buckets.p, lanes)
+    if (ctx->fbw_glv && spl == 1 && nbatch <= (size_t)ctx->tune.quad_accum_max) {
+        // a lane per (scalar, half) AND four lanes per chain: the few-commitments form
+        hipLaunchKernelGGL(k_fbw_accum_quad, dim3((unsigned)((lanes * nbatch * 4 + 255) / 256)), dim3(256), 0, stream, P, acc_in,
+                           (const WidePt*)ctx->wide.p, ws.buckets.p, lanes);
+    } else if (ctx->fbw_glv) {
+        if (spl == 1) KZG_FBW_LAUNCH(1, true);
+        else if (spl == 2) KZG_FBW_LAUNCH(2, true);
+        else if (spl == 4) KZG_FBW_LAUNCH(4, true);
+        else if (spl == 8) KZG_FBW_LAUNCH(8, true);
+        else if (spl == 16) KZG_FBW_LAUNCH(16, true);
+        else KZG_FBW_LAUNCH(32, true);
+    } else {
+        if (spl == 1) KZG_FBW_LAUNCH(1, false);
+        else if (spl == 2) KZG_FBW_LAUNCH(2, false);
+        else KZG_FBW_LAUNCH(4, false);
+    }
+#undef KZG_FBW_LAUNCH
+    if (pev) HIP_TRY(hipEventRecord(pev[2], stream));
+    Xyzz* sums = out_mode == OUT_XYZZ ? (Xyzz*)d_out : ws.lvlM[0].p;
+    if (lanes <= 64) {
+        // many small MSMs (segments of a table): one lane adds the few partial sums of an MSM
+        hipLaunchKernelGGL(k_lane_sum, dim3((unsigned)((nbatch + 63) / 64)), dim3(64), 0, stream, (const Xyzz*)ws.buckets.p,
+                           sums, lanes, nbatch);
+    } else if (wide_fold && !ctx->tune.no_wide_tree) {
+        // a few commitments (wide_fold_max): one launch of limb-parallel additions, 32 partial sums per workgroup
+        const u32 nwg = (u32)(lanes / WTREE_PER_WG);
+        hipLaunchKernelGGL(k_wide_tree, dim3((unsigned)(nbatch * nwg)), dim3(256), 0, stream, (const Xyzz*)ws.buckets.p, sums,
+                           ws.wpart.p, ws.wcount.p, lanes, nwg);
+    } else if (wide_fold) {
+        // one or two commitments: the partial sums folded 64 : 1, then 64 : 1 or 128 : 1, with limb-parallel additions
+        const int pw2 = (int)(lanes / 64 / WFOLD);  // 8 or 16 points per wave in the second launch
+        const size_t c1 = nbatch * (lanes / 64), c2 = nbatch;
+        HIP_TRY(hipMemsetAsync(ws.wcount.p, 0, (c1 + c2) * sizeof(u32), stream));
+        hipLaunchKernelGGL(k_wide_fold64, dim3((unsigned)(c1 * WFOLD)), dim3(64), 0, stream, (const Xyzz*)ws.buckets.p,
+                           ws.lvlA[0].p, ws.wpart.p, ws.wcount.p, 8);
+        hipLaunchKernelGGL(k_wide_fold64, dim3((unsigned)(c2 * WFOLD)), dim3(64), 0, stream, (const Xyzz*)ws.lvlA[0].p, sums,
+                           ws.wpart.p + c1 * WFOLD, ws.wcount.p + c1, pw2);
+    } else if (hybrid_fold) {
+        hipLaunchKernelGGL(k_blocksum_hybrid, dim3((unsigned)(nbatch * BSH_PARTS)), dim3(256), 256 * sizeof(Xyzz), stream,
+                           (const Xyzz*)ws.buckets.p, sums, ws.bpart.p, ws.bcount.p, lanes);
+    } else if (nbatch <= 16 && lanes % 16 == 0 && lanes >= 1024) {
+        // a few MSMs: the one-workgroup-per-MSM fold is a latency chain (16 strided additions + 8 tree rounds);
+        // 16 workgroups per MSM and a second small fold take 9 + 6 rounds instead (single commitment call
+        // 0.83 -> 0.71 ms).  Splitting the windows of a scalar over 3 lanes as well was measured: no gain.
+        hipLaunchKernelGGL(k_blocksum, dim3((unsigned)(nbatch * 16)), dim3(256), 256 * sizeof(Xyzz), stream,
+                           (const Xyzz*)ws.buckets.p, ws.lvlA[0].p, lanes / 16);
+        hipLaunchKernelGGL(k_blocksum, dim3((unsigned)nbatch), dim3(64), 64 * sizeof(Xyzz), stream,
+                           (const Xyzz*)ws.lvlA[0].p, sums, (size_t)16);
+    } else {
+        // many MSMs: two waves per MSM instead of four — fewer mostly-idle tree rounds per partial sum
+        // (256 / 128 / 64 threads: 87.7 k / 88.9 k / 87.6 k commitments/s at 1024 blobs, same box)
+        int bs = 256;
+        if (nbatch >= 256) bs = 128;
+        if (const int v = ctx->tune.blocksum_threads) bs = v == 64 || v == 128 || v == 256 ? v : bs;
+        hipLaunchKernelGGL(k_blocksum, dim3((unsigned)nbatch), dim3(bs), bs * sizeof(Xyzz), stream,
+                           (const Xyzz*)ws.buckets.p, sums, lanes);
+    }
+    if (out_mode != OUT_XYZZ)
+        hipLaunchKernelGGL(k_final, dim3((unsigned)((nbatch + 63) / 64)), dim3(64), 0, stream, (const Xyzz*)nullptr,
+                           (const Xyzz*)ws.lvlM[0].p, d_out, nbatch, nwin, c, 1, out_mode);
+    if (pev) {
+        HIP_TRY(hipEventRecord(pev[3], stream));
+        ctx->ev_used += 4;
+    }
+    HIP_TRY(hipGetLastError());
+}
+
+// How a sub-batch of a batch of large MSMs is tied to the caller's stream (see MsmContext::sub_stream): sorted and
+// reduced on its side stream, accumulated on the caller's stream behind the previous sub-batch's accumulation.
+struct SubLink {
+    hipStream_t accum_on;    // the caller's stream (which may be the null stream)
+    hipEvent_t sorted;       // recorded on the side stream after the sort; accum_on waits for it
+    hipEvent_t accumulated;  // recorded on accum_on after k_accum; the side stream waits for it
+};
+
+// One launch of the bucket engine: sort -> accumulate -> heavy buckets -> reduction -> window sums -> final, all on
+// `stream` and in `ws` — except that with a link (a sub-batch) the accumulation goes to link->accum_on.
+static void enqueue_buckets(MsmContext* ctx, Workspace& ws, void* d_out, const void* d_scalars, size_t npoints, size_t nbatch,
+                            int mont, hipStream_t stream, int out_mode, bool reserve_only, const SubLink* link) {
     const int c = ctx->c;
     const int nwin = ctx->nwin;
     const size_t nb = ctx->nb;
     const size_t nsets = ctx->prepared ? nbatch : nbatch * (size_t)nwin;
     const size_t set_cap = ctx->prepared ? npoints * (size_t)nwin : (ctx->glv ? 2 * npoints : npoints);
-    if (npoints == 0) {
-        if (reserve_only) return;
-        if (out_mode == OUT_COMPRESSED) throw HipErr{hipErrorInvalidValue, "empty MSM in compressed mode"};
-        HIP_TRY(hipMemsetAsync(d_out, 0, nbatch * 144, stream));
-        return;
-    }
-    if (set_cap >= ((size_t)1 << 31) || nsets * nb >= ((size_t)1 << 40)) throw HipErr{hipErrorInvalidValue, "MSM too large"};
-    Workspace& ws = ctx->workspace_for(stream);
-    // Workspaces are per stream, but streams can outnumber them (and the handle's own stream shares the first one):
-    // whoever gets a workspace last used on another stream first waits for that use to finish on the GPU.
-    // a workspace that only one stream ever uses (every entry of ws_extra) is ordered by that stream: no events —
-    // two runtime calls less per enqueue, and such an enqueue can be captured into a graph
-    struct WsUse {
-        Workspace& w;
-        hipStream_t st;
-        bool shared;
-        WsUse(Workspace& w_, hipStream_t st_, bool shared_) : w(w_), st(st_), shared(shared_) {
-            if (shared && w.last_done && w.last_stream != st) (void)hipStreamWaitEvent(st, w.last_done, 0);
-        }
-        ~WsUse() {
-            if (!shared) return;
-            if (!w.last_done && hipEventCreateWithFlags(&w.last_done, hipEventDisableTiming) != hipSuccess) w.last_done = nullptr;
-            if (w.last_done) (void)hipEventRecord(w.last_done, st);
-            w.last_stream = st;
-        }
-    };
-    if (ctx->fbw) {
-        // wide-table path: gather + add, then one block-sum per MSM
-        // scalars per lane: 4 for large batches — a quarter of the partial sums for k_blocksum to fold against one
-        // more real addition per lane (the first addition into an empty accumulator is free): +1.0 % at 1024 blobs
-        // (87.1 k -> 88.0 k commitments/s, three alternating runs on one box); 1 for small batches, where the lanes
-        // are needed for latency
-        int spl = nbatch >= 256 ? 4 : 1;
-        // segment MSMs (FK20: 128 MSMs of 64 scalars per blob): from 128 blobs on, 16 scalars per lane — 320 additions
-        // per lane instead of 80 and four partial sums per MSM instead of 16 for k_lane_sum (0.23 -> 0.05 ms at 256
-        // blobs); the accumulation itself takes the same 6.2 - 6.4 ms either way (measured, profiles/NOTES.md §16)
-        if (nseg && ctx->fbw_glv && npoints % 32 == 0) {
-            if (nbatch * npoints >= ((size_t)1 << 21)) spl = 16;       // 256 blobs: 131 072 lanes, two waves per SIMD
-            else if (nbatch * npoints >= ((size_t)1 << 20)) spl = 8;  // 128 blobs: the same
-        }
-        if (ctx->tune.spl) spl = ctx->tune.spl;
-        if (spl == 3 || (spl > 4 && spl != 8 && spl != 16)) spl = 4;
-        if (!ctx->fbw_glv && spl > 4) spl = 4;
-        if (ctx->fbw_glv) spl *= 2;  // two lanes (k1 / k2 digits) per scalar group: the same number of partial sums
-        // a few MSMs over the 4096-point setup: a lane per (scalar, half) — 8 additions per lane instead of 16, twice the
-        // partial sums for the fold (limb-parallel up to WIDE_FOLD_MAX MSMs, k_blocksum above)
-        // (up to 8 MSMs: 8 commitments 0.79 -> 0.71 ms; 16 the same either way, 32 and 64 slower)
-        const size_t spl1_max = ctx->tune.spl1_max > 0 ? (size_t)ctx->tune.spl1_max : 8;
-        if (ctx->fbw_glv && nbatch <= spl1_max && npoints == 4096 && !ctx->tune.spl && !ctx->tune.no_wide_tail) spl = 1;
-        const size_t lanes = (npoints + spl - 1) / spl * (ctx->fbw_glv ? 2 : 1);
-        ws.buckets.ensure(nbatch * lanes);
-        ws.lvlM[0].ensure(nbatch);
-        if (nbatch <= 16 && lanes % 16 == 0 && lanes >= 1024) ws.lvlA[0].ensure(nbatch * 128);
-        const size_t hybrid_max = ctx->tune.hybrid_max > 0 ? (size_t)ctx->tune.hybrid_max : BSH_MAX;
-        const bool hybrid_fold = nbatch <= hybrid_max && nbatch <= BSH_CAP && lanes % (16 * 256) == 0 &&
-                                 !ctx->tune.no_wide_tail && !ctx->tune.no_hybrid_fold;
-        bool bcount_new = false;
-        if (hybrid_fold) {
-            ws.bpart.ensure(BSH_CAP * (size_t)BSH_PARTS);
-            if (ws.bcount.cap < BSH_CAP) {
-                ws.bcount.ensure(BSH_CAP);
-                bcount_new = true;
-            }
-        }
-        const size_t wf_max = ctx->tune.wide_fold_max > 0 ? (size_t)ctx->tune.wide_fold_max : WIDE_FOLD_MAX;
-        const bool wide_fold = nbatch <= wf_max && (lanes == 4096 || lanes == 8192) && !ctx->tune.no_wide_tail;
-        bool wcount_new = false;
-        if (wide_fold) {
-            // k_wide_tree: lanes / 32 workgroup sums + lanes / 512 group sums per MSM, a counter per group and one per MSM
-            // (zeroed when allocated, left at zero by every launch); k_wide_fold64 (tuning key no_wide_tree): 129 cells x
-            // WFOLD parts, a counter per cell — which is more of both
-            const size_t need_p = (nbatch * 128 + nbatch) * (size_t)WFOLD, need_c = nbatch * 128 + nbatch;
-            ws.wpart.ensure(need_p);
-            if (ws.wcount.cap < need_c) {
-                ws.wcount.ensure(need_c);
-                wcount_new = true;
-            }
-        }
-        if (ctx->fbw_glv) ws.digits.ensure(nbatch * npoints * 2 * (size_t)((nwin + 3) & ~3));
-        if (bcount_new) HIP_TRY(hipMemsetAsync(ws.bcount.p, 0, BSH_CAP * sizeof(u32), stream));
-        if (wcount_new) HIP_TRY(hipMemsetAsync(ws.wcount.p, 0, ws.wcount.cap * sizeof(u32), stream));
-        if (reserve_only) return;
-        WsUse ws_use(ws, stream, &ws == &ctx->ws);
-        DigitParams P{npoints, nbatch, c, nwin, 1, mont, nb, ctx->n, 0, 0, nwin, (u32)nseg};
-        hipEvent_t* pev = nullptr;
-        if (ctx->profile && ctx->ev_used + 4 <= MsmContext::EV_MAX) {
-            while (ctx->ev.size() < ctx->ev_used + 4) {
-                hipEvent_t e;
-                HIP_TRY(hipEventCreate(&e));
-                ctx->ev.push_back(e);
-            }
-            pev = &ctx->ev[ctx->ev_used];
-            HIP_TRY(hipEventRecord(pev[0], stream));
-        }
-        const u32* acc_in = (const u32*)d_scalars;
-        if (ctx->fbw_glv) {
-            hipLaunchKernelGGL(k_fbw_digits, dim3((unsigned)((npoints * nbatch + 255) / 256)), dim3(256), 0, stream, P,
-                               (const u32*)d_scalars, ws.digits.p);
-            acc_in = ws.digits.p;
-        }
-        if (pev) HIP_TRY(hipEventRecord(pev[1], stream));
-        const dim3 grid((unsigned)((lanes * nbatch + 255) / 256));
-#define KZG_FBW_LAUNCH(SPL_, GLV_)                                                                           \
-    hipLaunchKernelGGL((k_fbw_accum<SPL_, GLV_>), grid, dim3(256), 0, stream, P, acc_in,                         \
-                       (const WidePt*)ctx->wide.p, ws.buckets.p, lanes)
-        if (ctx->fbw_glv && spl == 1 && nbatch <= (size_t)ctx->tune.quad_accum_max) {
-            // a lane per (scalar, half) AND four lanes per chain: the few-commitments form
-            hipLaunchKernelGGL(k_fbw_accum_quad, dim3((unsigned)((lanes * nbatch * 4 + 255) / 256)), dim3(256), 0, stream, P, acc_in,
-                               (const WidePt*)ctx->wide.p, ws.buckets.p, lanes);
-        } else if (ctx->fbw_glv) {
-            if (spl == 1) KZG_FBW_LAUNCH(1, true);
-            else if (spl == 2) KZG_FBW_LAUNCH(2, true);
-            else if (spl == 4) KZG_FBW_LAUNCH(4, true);
-            else if (spl == 8) KZG_FBW_LAUNCH(8, true);
-            else if (spl == 16) KZG_FBW_LAUNCH(16, true);
-            else KZG_FBW_LAUNCH(32, true);
-        } else {
-            if (spl == 1) KZG_FBW_LAUNCH(1, false);
-            else if (spl == 2) KZG_FBW_LAUNCH(2, false);
-            else KZG_FBW_LAUNCH(4, false);
-        }
-#undef KZG_FBW_LAUNCH
-        if (pev) HIP_TRY(hipEventRecord(pev[2], stream));
-        Xyzz* sums = out_mode == OUT_XYZZ ? (Xyzz*)d_out : ws.lvlM[0].p;
-        if (lanes <= 64) {
-            // many small MSMs (segments of a table): one lane adds the few partial sums of an MSM
-            hipLaunchKernelGGL(k_lane_sum, dim3((unsigned)((nbatch + 63) / 64)), dim3(64), 0, stream, (const Xyzz*)ws.buckets.p,
-                               sums, lanes, nbatch);
-        } else if (wide_fold && !ctx->tune.no_wide_tree) {
-            // a few commitments (wide_fold_max): one launch of limb-parallel additions, 32 partial sums per workgroup
-            const u32 nwg = (u32)(lanes / WTREE_PER_WG);
-            hipLaunchKernelGGL(k_wide_tree, dim3((unsigned)(nbatch * nwg)), dim3(256), 0, stream, (const Xyzz*)ws.buckets.p, sums,
-                               ws.wpart.p, ws.wcount.p, lanes, nwg);
-        } else if (wide_fold) {
-            // one or two commitments: the partial sums folded 64 : 1, then 64 : 1 or 128 : 1, with limb-parallel additions
-            const int pw2 = (int)(lanes / 64 / WFOLD);  // 8 or 16 points per wave in the second launch
-            const size_t c1 = nbatch * (lanes / 64), c2 = nbatch;
-            HIP_TRY(hipMemsetAsync(ws.wcount.p, 0, (c1 + c2) * sizeof(u32), stream));
-            hipLaunchKernelGGL(k_wide_fold64, dim3((unsigned)(c1 * WFOLD)), dim3(64), 0, stream, (const Xyzz*)ws.buckets.p,
-                               ws.lvlA[0].p, ws.wpart.p, ws.wcount.p, 8);
-            hipLaunchKernelGGL(k_wide_fold64, dim3((unsigned)(c2 * WFOLD)), dim3(64), 0, stream, (const Xyzz*)ws.lvlA[0].p, sums,
-                               ws.wpart.p + c1 * WFOLD, ws.wcount.p + c1, pw2);
-        } else if (hybrid_fold) {
-            hipLaunchKernelGGL(k_blocksum_hybrid, dim3((unsigned)(nbatch * BSH_PARTS)), dim3(256), 256 * sizeof(Xyzz), stream,
-                               (const Xyzz*)ws.buckets.p, sums, ws.bpart.p, ws.bcount.p, lanes);
-        } else if (nbatch <= 16 && lanes % 16 == 0 && lanes >= 1024) {
-            // a few MSMs: the one-workgroup-per-MSM fold is a latency chain (16 strided additions + 8 tree rounds);
-            // 16 workgroups per MSM and a second small fold take 9 + 6 rounds instead (single commitment call
-            // 0.83 -> 0.71 ms).  Splitting the windows of a scalar over 3 lanes as well was measured: no gain.
-            hipLaunchKernelGGL(k_blocksum, dim3((unsigned)(nbatch * 16)), dim3(256), 256 * sizeof(Xyzz), stream,
-                               (const Xyzz*)ws.buckets.p, ws.lvlA[0].p, lanes / 16);
-            hipLaunchKernelGGL(k_blocksum, dim3((unsigned)nbatch), dim3(64), 64 * sizeof(Xyzz), stream,
-                               (const Xyzz*)ws.lvlA[0].p, sums, (size_t)16);
-        } else {
-            // many MSMs: two waves per MSM instead of four — fewer mostly-idle tree rounds per partial sum
-            // (256 / 128 / 64 threads: 87.7 k / 88.9 k / 87.6 k commitments/s at 1024 blobs, same box)
-            int bs = 256;
-            if (nbatch >= 256) bs = 128;
-            if (const int v = ctx->tune.blocksum_threads) bs = v == 64 || v == 128 || v == 256 ? v : bs;
-            hipLaunchKernelGGL(k_blocksum, dim3((unsigned)nbatch), dim3(bs), bs * sizeof(Xyzz), stream,
-                               (const Xyzz*)ws.buckets.p, sums, lanes);
-        }
-        if (out_mode != OUT_XYZZ)
-            hipLaunchKernelGGL(k_final, dim3((unsigned)((nbatch + 63) / 64)), dim3(64), 0, stream, (const Xyzz*)nullptr,
-                               (const Xyzz*)ws.lvlM[0].p, d_out, nbatch, nwin, c, 1, out_mode);
-        if (pev) {
-            HIP_TRY(hipEventRecord(pev[3], stream));
-            ctx->ev_used += 4;
-        }
-        HIP_TRY(hipGetLastError());
-        return;
-    }
-    // A batch of large MSMs whose sets together have more coarse bins than the two-level sort's LDS counters hold
-    // (MAX_BINS) would take the one-level sort — 1.2 ms instead of 0.3 per 2^20-point MSM (measured: 4 x 2^20 in one call
-    // 4.2 ms per MSM against 3.4 for one).  Such a batch runs as sub-batches that fit.  Round 6: ANY batch of large MSMs is
-    // cut into sub-batches, and only their accumulations stay on the caller's stream; the sort and the reduction of a
-    // sub-batch run on a high-priority side stream beside another sub-batch's accumulation (MsmContext::sub_stream;
-    // tuning key sub_streams = how many rotate, 0 = everything on the caller's stream and workspace as in round 5).
-    if (nbatch > 1 && !ctx->in_sub_batch && !ctx->tune.one_level_sort && npoints >= ((size_t)1 << 15)) {
-        const int fb0 = ctx->tune.fine_bits >= FINE_BITS_MIN && ctx->tune.fine_bits <= FINE_BITS_MAX ? ctx->tune.fine_bits : FINE_BITS_MIN;
-        const size_t bins_per_msm = (nb >> fb0) * (ctx->prepared ? (size_t)1 : (size_t)nwin);
-        size_t per = bins_per_msm ? MAX_BINS / bins_per_msm : 0;
-        // Measured (tools/ab_batched.py, profiles/NOTES.md §20): 4 or 8 x 2^16 in one call 0.70 -> 0.645 ms per MSM with six side
-        // streams (three: 0.70), 4 x 2^17 0.87 -> 0.82 — there the reduction chains of the sub-batches (0.7 ms each, a
-        // fraction of the chip) overlap each other.  From
-        // 2^18 points on an accumulation fills every register of every SIMD for milliseconds and whatever is launched
-        // beside it, at any stream priority, crawls (k_tile_sums_loop 2.9 ms instead of 0.32, k_digit_sums_wide 1.6 instead
-        // of 0.09) and delays the next sub-batch: 4 x 2^20 3.26 ms per MSM on one stream, 3.3 - 3.5 with side streams.
-        // So the side streams serve batches of MSMs below 2^18 points; tuning key sub_large = 1 lifts the limit.
-        int nside = ctx->tune.sub_streams < 0 ? 0 : ctx->tune.sub_streams > MsmContext::MAXSUB ? MsmContext::MAXSUB : ctx->tune.sub_streams;
-        // Sort ahead (round 6, second form; key sort_ahead): from 2^18 points on NOTHING runs beside an accumulation, but
-        // the sort of sub-batch k + 1 — scattered 4-byte traffic and LDS histograms, 40-odd registers — runs on a side
-        // stream beside the REDUCTION of sub-batch k, whose chains leave most of the chip idle:
-        //     caller's stream:  accumulate(0)  reduce(0)  accumulate(1)  reduce(1) ...
-        //     side streams:     sort(0)        sort(1) [after accumulate(0)]       sort(2) [after accumulate(1)] ...
-        // Two side streams / workspaces alternate (sort(k + 2) starts after accumulate(k + 1), i.e. after reduce(k) is done
-        // with the workspace they share).
-        // Measured (tools/ab_batched.py, one box, ms per MSM; off / on with high-priority side streams / on with default
-        // priority): 4 x 2^20 3.296 / 3.312 / 3.281, 8 x 2^20 3.318 / 3.376 / 3.283, 8 x 2^18 1.194 / 1.283 / 1.179.  A first
-        // form that let the sort start right after the accumulation — beside the tile sums — lost 2.5 % (3.42 vs 3.34): the
-        // tile sums of two MSMs are 512 workgroups on every register of the chip, and k_part_scan (ONE workgroup) waited
-        // 250 us for a slot.  +-1 % is not a reason for two more streams in a call: off by default.
-        const bool sort_ahead = npoints >= ((size_t)1 << 18) && !ctx->tune.sub_large && ctx->tune.sort_ahead && nside >= 2;
-        if (npoints >= ((size_t)1 << 18) && !ctx->tune.sub_large) nside = sort_ahead ? 2 : 0;
-        if (nside > 0 && per >= 1 && !sort_ahead) {
-            // at least two sub-batches; from 2^18 points an MSM's accumulation alone fills the chip for a millisecond
-            const size_t cap = npoints >= ((size_t)1 << 18) ? (size_t)1 : (nbatch + 1) / 2;
-            if (per > cap) per = cap;
-        }
-        if (nb >= ((size_t)1 << fb0) && per >= 1 && per < nbatch) {
-            const size_t out_stride = out_mode == OUT_COMPRESSED ? 48 : out_mode == OUT_WINDOWS ? (size_t)nwin * 144 : 144;
-            const size_t nsub = (nbatch + per - 1) / per;
-            const int lanes = nside > 0 ? (int)(nsub < (size_t)nside ? nsub : (size_t)nside) : 0;  // side streams in use
-            if (lanes > 0 && !ctx->sub_stream[lanes - 1]) {
-                int least = 0, greatest = 0;
-                HIP_TRY(hipDeviceGetStreamPriorityRange(&least, &greatest));
-                const int prio = ctx->tune.sub_prio ? greatest : 0;
-                for (int k = 0; k < lanes; ++k) {
-                    if (!ctx->sub_stream[k]) HIP_TRY(hipStreamCreateWithPriority(&ctx->sub_stream[k], hipStreamNonBlocking, prio));
-                    if (!ctx->ev_sub_join[k]) HIP_TRY(hipEventCreateWithFlags(&ctx->ev_sub_join[k], hipEventDisableTiming));
-                    if (!ctx->ev_sorted[k]) HIP_TRY(hipEventCreateWithFlags(&ctx->ev_sorted[k], hipEventDisableTiming));
-                    if (!ctx->ev_accd[k]) HIP_TRY(hipEventCreateWithFlags(&ctx->ev_accd[k], hipEventDisableTiming));
-                    if (!ctx->ev_gate[k]) HIP_TRY(hipEventCreateWithFlags(&ctx->ev_gate[k], hipEventDisableTiming));
-                }
-            }
-            struct SubReset {  // an exception below must not leave the next enqueue in sub-batch mode
-                MsmContext* c;
-                ~SubReset() {
-                    c->accum_redirect = false;
-                    c->tail_on_accum = false;
-                    c->accum_on = nullptr;
-                    c->accum_ready = c->accum_done = c->sort_gate = nullptr;
-                    c->in_sub_batch = false;
-                }
-            } sub_reset{ctx};
-            ctx->in_sub_batch = true;
-            if (reserve_only) {  // the first sub-batch is the largest; every stream of the rotation gets its workspace
-                if (lanes == 0) msm_enqueue(ctx, nullptr, nullptr, npoints, per, mont, stream, out_mode, true, nseg);
-                for (int k = 0; k < lanes; ++k)
-                    msm_enqueue(ctx, nullptr, nullptr, npoints, per, mont, ctx->sub_stream[k], out_mode, true, nseg);
-                return;
-            }
-            if (lanes > 0) {
-                if (!ctx->ev_sub_fork) HIP_TRY(hipEventCreateWithFlags(&ctx->ev_sub_fork, hipEventDisableTiming));
-                // whatever produced the scalars (and last used the outputs) on the caller's stream comes first
-                HIP_TRY(hipEventRecord(ctx->ev_sub_fork, stream));
-                for (int k = 0; k < lanes; ++k) HIP_TRY(hipStreamWaitEvent(ctx->sub_stream[k], ctx->ev_sub_fork, 0));
-            }
-            size_t k = 0;
-            for (size_t b0 = 0; b0 < nbatch; b0 += per, ++k) {
-                const size_t nbp = b0 + per <= nbatch ? per : nbatch - b0;
-                hipStream_t st = stream;
-                if (lanes > 0) {
-                    const int lane = (int)(k % (size_t)lanes);
-                    st = ctx->sub_stream[lane];
-                    ctx->accum_redirect = true;
-                    ctx->tail_on_accum = sort_ahead;
-                    ctx->accum_on = stream;
-                    ctx->accum_ready = ctx->ev_sorted[lane];
-                    ctx->accum_done = ctx->ev_accd[lane];
-                    // sort ahead: this sub-batch's sort waits for the previous sub-batch's accumulation (recorded on the
-                    // caller's stream by that enqueue) and for its tile sums — throughput work on every register of the chip, like the
-                    // accumulation — so that it runs beside the limb-parallel chains of the reduction only
-                    ctx->sort_gate = sort_ahead ? ctx->ev_gate[lane] : nullptr;
-                    if (sort_ahead && k > 0) HIP_TRY(hipStreamWaitEvent(st, ctx->ev_gate[(int)((k - 1) % (size_t)lanes)], 0));
-                }
-                msm_enqueue(ctx, d_out ? (unsigned char*)d_out + b0 * out_stride : nullptr,
-                            d_scalars ? (const unsigned char*)d_scalars + b0 * npoints * 32 : nullptr, npoints, nbp, mont, st,
-                            out_mode, false, nseg);
-            }
-            ctx->accum_redirect = false;
-            ctx->tail_on_accum = false;
-            for (int j = 0; j < lanes; ++j) {
-                HIP_TRY(hipEventRecord(ctx->ev_sub_join[j], ctx->sub_stream[j]));
-                HIP_TRY(hipStreamWaitEvent(stream, ctx->ev_sub_join[j], 0));
-            }
-            return;
-        }
-    }
     ws.offsets.ensure(nsets * (nb + 1));
     ws.sorted.ensure(nsets * set_cap);
     // entries per accumulation lane, 2^lgc: longer chunks leave fewer pieces per bucket to fold, shorter ones more lanes
@@ -2805,22 +2671,8 @@ void msm_enqueue(MsmContext* ctx, void* d_out, const void* d_scalars, size_t npo
     ws.lvlA[1].ensure(nsets * n2);
     ws.lvlM[1].ensure(nsets * n2);
     ws.heavy.ensure(nsets * nb);
-    // Window groups (tuning key groups = 2..4, off by default).  The sort is bound by atomics / scattered writes, the
-    // accumulation by the integer VALUs and the reduction tail by latency, so a single large MSM can be cut into
-    // groups of windows that run as a pipeline on their own streams: the sort of group g+1 overlaps the accumulation
-    // of group g, whose tail overlaps the accumulation of g+1; only the Horner over the window sums joins them.
-    // With the one-level sort (1.2 ms at n = 2^20) two groups gained 6 % (5.83 -> 5.47 ms; four were slower: every
-    // group pays the scalar load + split again); with the two-level sort (0.5 ms) there is nothing left to hide:
-    // 6.17 vs 6.22 ms on the same box.
-    int G = 1;
-    if (!ctx->prepared && nbatch == 1 && !ctx->profile && npoints >= 4096 && nwin >= 4) {
-        if (const int v = ctx->tune.groups) {
-            if (v >= 1 && v <= MsmContext::MAXG && v <= nwin) G = v;
-        }
-    }
-    const size_t sets_per_group = (nsets + G - 1) / G;
     // lanes the accumulation wants per set: 90 % of two waves per SIMD over the sets of a launch
-    const ChunkSel csel{lgc_lo, lgc, (u32)(118000 / sets_per_group)};
+    const ChunkSel csel{lgc_lo, lgc, (u32)(118000 / nsets)};
     // two-level sort: coarse bins must fit the LDS counters and a point index 24 bits
     const size_t max_pidx = ctx->prepared ? (size_t)ctx->rows * ctx->n : (ctx->glv ? 2 * ctx->n : ctx->n);
     int pbits = 1;  // bits of a point index
@@ -2830,20 +2682,20 @@ void msm_enqueue(MsmContext* ctx, void* d_out, const void* d_scalars, size_t npo
         if (v >= FINE_BITS_MIN && v <= FINE_BITS_MAX && v <= 31 - pbits) fb = v;
     }
     const bool two_level = !ctx->tune.one_level_sort && nb >= ((size_t)1 << fb) && fb + 1 + pbits <= 32 &&
-                           (nb >> fb) * sets_per_group <= MAX_BINS &&
+                           (nb >> fb) * nsets <= MAX_BINS &&
                            npoints * nbatch >= ((size_t)1 << 15);  // below: four more launches than they save
     if (two_level) {
         ws.tmp.ensure(nsets * set_cap);
-        ws.bins.ensure((size_t)G * (3 * MAX_BINS + 8));
-        if (G == 1)  // per-workgroup histograms and run starts of the partition pass (1024 scalars per workgroup)
-            ws.wghist.ensure(2 * ((npoints * nbatch + 1023) / 1024) * ((nb >> fb) * sets_per_group));
+        ws.bins.ensure(3 * MAX_BINS + 8);
+        // per-workgroup histograms and run starts of the partition pass (1024 scalars per workgroup)
+        ws.wghist.ensure(2 * ((npoints * nbatch + 1023) / 1024) * ((nb >> fb) * nsets));
     } else {
         ws.counts.ensure(nsets * nb);
         ws.ranks.ensure((size_t)(ctx->glv ? 2 : 1) * nwin * nbatch * npoints);
     }
-    const size_t heavy_cap = sets_per_group * set_cap / HEAVY + 1;  // a heavy bucket holds > HEAVY entries
-    ws.heavy_list.ensure(2 * heavy_cap * G);
-    ws.nheavy.ensure(G);
+    const size_t heavy_cap = nsets * set_cap / HEAVY + 1;  // a heavy bucket holds > HEAVY entries
+    ws.heavy_list.ensure(2 * heavy_cap);
+    ws.nheavy.ensure(1);
     const bool use_top = nsets <= 64;  // many independent sets (batched MSMs) keep plain tree levels busy on their own
     // few chains: run the serial tails limb-parallel, one point operation per wave
     const bool wide_tail = use_top && !ctx->tune.no_wide_tail;
@@ -2855,7 +2707,7 @@ void msm_enqueue(MsmContext* ctx, void* d_out, const void* d_scalars, size_t npo
     const int tile_rows = ctx->tune.tile_rows ? ctx->tune.tile_rows : 32;  // 16: measured slower alone (3.52 vs 3.42 ms at 2^20) and no help beside an accumulation
     const bool tiled_digits = digit_tail && nb % ((size_t)tile_rows * 32) == 0 && !ctx->tune.flat_digits;
     const size_t ntiles = nb / ((size_t)tile_rows * 32);
-    // shape of the tree (the same for every group: level 0 folds by the group size): k_top stride B + 2
+    // shape of the tree (level 0 folds by the group size): k_top stride B + 2
     size_t top_stride = 0;
     {
         size_t nin = nb;
@@ -2863,7 +2715,7 @@ void msm_enqueue(MsmContext* ctx, void* d_out, const void* d_scalars, size_t npo
         do {
             int grp = GRP;
             if (lvl == 0)
-                while (grp > 2 && sets_per_group * ((nin + grp - 1) / grp) < ((size_t)1 << 17)) grp >>= 1;
+                while (grp > 2 && nsets * ((nin + grp - 1) / grp) < ((size_t)1 << 17)) grp >>= 1;
             nin = (nin + grp - 1) / grp;
             ++lvl;
         } while (nin > (use_top ? TOP_MAX : (size_t)1));
@@ -2890,227 +2742,159 @@ void msm_enqueue(MsmContext* ctx, void* d_out, const void* d_scalars, size_t npo
         }
     }
     if (reserve_only) return;
-    // sub-batch of a batch of large MSMs: the accumulation goes to the caller's stream (see MsmContext::sub_stream)
-    const bool accum_redirect = ctx->accum_redirect;
-    const hipEvent_t sort_gate = ctx->sort_gate;
-    bool gate_recorded = false;
-    const bool tail_on_accum = accum_redirect && ctx->tail_on_accum;  // sort-ahead form: the reduction follows its accumulation on the caller's stream
-    const hipStream_t accum_on = ctx->accum_on;
-    const hipEvent_t accum_ready = ctx->accum_ready, accum_done = ctx->accum_done;
     WsUse ws_use(ws, stream, &ws == &ctx->ws);
-    hipEvent_t* pev = nullptr;
-    if (ctx->profile && ctx->ev_used + 4 <= MsmContext::EV_MAX) {
-        while (ctx->ev.size() < ctx->ev_used + 4) {
-            hipEvent_t e;
-            HIP_TRY(hipEventCreate(&e));
-            ctx->ev.push_back(e);
-        }
-        pev = &ctx->ev[ctx->ev_used];
-        HIP_TRY(hipEventRecord(pev[0], stream));
-    }
-    if (G > 1) {
-        if (!ctx->ev_fork) HIP_TRY(hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming));
-        for (int g = 0; g < G; ++g) {
-            if (!ctx->aux[g]) HIP_TRY(hipStreamCreateWithFlags(&ctx->aux[g], hipStreamNonBlocking));
-            if (!ctx->ev_dig[g]) HIP_TRY(hipEventCreateWithFlags(&ctx->ev_dig[g], hipEventDisableTiming));
-            if (!ctx->ev_acc[g]) HIP_TRY(hipEventCreateWithFlags(&ctx->ev_acc[g], hipEventDisableTiming));
-            if (!ctx->ev_done[g]) HIP_TRY(hipEventCreateWithFlags(&ctx->ev_done[g], hipEventDisableTiming));
-        }
-        HIP_TRY(hipEventRecord(ctx->ev_fork, stream));
-    }
+    hipEvent_t* const pev = profile_begin(ctx, stream);
     const Xyzz *finA = nullptr, *finM = nullptr;
-    for (int g = 0; g < G; ++g) {
-        const size_t set0 = (size_t)g * sets_per_group;
-        if (set0 >= nsets) break;
-        const size_t ns = set0 + sets_per_group <= nsets ? sets_per_group : nsets - set0;
-        hipStream_t st = G > 1 ? ctx->aux[g] : stream;
-        if (G > 1) {
-            HIP_TRY(hipStreamWaitEvent(st, ctx->ev_fork, 0));
-            if (g > 0) HIP_TRY(hipStreamWaitEvent(st, ctx->ev_dig[g - 1], 0));
+    DigitParams P{npoints, nbatch, c, nwin, ctx->prepared ? 1 : 0, mont, nb, ctx->n, ctx->glv ? 1 : 0, 0, nwin, 0u};
+    u32* const offsets = ws.offsets.p;
+    unsigned char* const heavy = ws.heavy.p;
+    u32* const heavy_list = ws.heavy_list.p;
+    u32* const nheavy = ws.nheavy.p;
+    Xyzz* const buckets = ws.buckets.p;
+    if (two_level) {
+        const u32 cb = (u32)(nb >> fb), nbins = (u32)nsets * cb;
+        u32* bin_count = ws.bins.p;
+        u32* bin_start = bin_count + MAX_BINS;
+        u32* bin_cursor = bin_start + MAX_BINS + 8;
+        u32* tmp = ws.tmp.p;
+        const unsigned gpart = (unsigned)((npoints * nbatch + 256 * PART_SCALARS - 1) / (256 * PART_SCALARS));
+        HIP_TRY(hipMemsetAsync(bin_count, 0, nbins * sizeof(u32), stream));
+        // entries per scalar (windows x halves): the staged scatter holds 16 per scalar
+        const size_t per_scalar = (size_t)nwin * (ctx->glv ? 2 : 1);
+        const bool staged = per_scalar * STAGE_T * STAGE_SCALARS <= STAGE_CAP && !ctx->tune.direct_scatter;
+        // per-workgroup histograms kept by the count pass (tuning key scatter_atomics=1: recount + one atomic per run)
+        const bool keep_hist = staged && !ctx->tune.scatter_atomics;
+        u32 *wg_hist = nullptr, *wg_off = nullptr;
+        if (keep_hist) {
+            ws.wghist.ensure(2 * (size_t)gpart * nbins);
+            wg_hist = ws.wghist.p;
+            wg_off = wg_hist + (size_t)gpart * nbins;
         }
-        // with groups, sets are windows (nbatch == 1): group g emits windows [set0, set0 + ns)
-        DigitParams P{npoints, nbatch, c, nwin, ctx->prepared ? 1 : 0, mont, nb, ctx->n, ctx->glv ? 1 : 0,
-                      G > 1 ? (int)set0 : 0, G > 1 ? (int)(set0 + ns) : nwin, 0u};
-        u32* counts = two_level ? nullptr : ws.counts.p + set0 * nb;
-        u32* offsets = ws.offsets.p + set0 * (nb + 1);
-        unsigned char* heavy = ws.heavy.p + set0 * nb;
-        u32* heavy_list = ws.heavy_list.p + 2 * heavy_cap * g;
-        u32* nheavy = ws.nheavy.p + g;
-        Xyzz* buckets = ws.buckets.p + set0 * (nb + nchunk);
-        if (two_level) {
-            const u32 cb = (u32)(nb >> fb), nbins = (u32)ns * cb;
-            u32* bin_count = ws.bins.p + (size_t)g * (3 * MAX_BINS + 8);
-            u32* bin_start = bin_count + MAX_BINS;
-            u32* bin_cursor = bin_start + MAX_BINS + 8;
-            u32* tmp = ws.tmp.p + set0 * set_cap;
-            const unsigned gpart = (unsigned)((npoints * nbatch + 256 * PART_SCALARS - 1) / (256 * PART_SCALARS));
-            HIP_TRY(hipMemsetAsync(bin_count, 0, nbins * sizeof(u32), st));
-            // entries per scalar (windows of this launch's group x halves): the staged scatter holds 16 per scalar
-            const size_t per_scalar = (size_t)(G > 1 ? ns : (size_t)nwin) * (ctx->glv ? 2 : 1);
-            const bool staged = per_scalar * STAGE_T * STAGE_SCALARS <= STAGE_CAP && !ctx->tune.direct_scatter;
-            // per-workgroup histograms kept by the count pass (tuning key scatter_atomics=1: recount + one atomic per run)
-            const bool keep_hist = staged && G == 1 && !ctx->tune.scatter_atomics;
-            u32 *wg_hist = nullptr, *wg_off = nullptr;
-            if (keep_hist) {
-                ws.wghist.ensure(2 * (size_t)gpart * nbins);
-                wg_hist = ws.wghist.p;
-                wg_off = wg_hist + (size_t)gpart * nbins;
-            }
-            hipLaunchKernelGGL(k_part_count, dim3(gpart), dim3(256), nbins * sizeof(u32), st, P, (const u32*)d_scalars,
-                               (const AffPt*)ctx->table.p, bin_count, (u32)set0, cb, nbins, fb, wg_hist);
-            hipLaunchKernelGGL(k_part_scan, dim3(1), dim3(1024), 0, st, (const u32*)bin_count, bin_start, bin_cursor, nbins);
-            if (staged) {
-                const unsigned gst = (unsigned)((npoints * nbatch + STAGE_T * STAGE_SCALARS - 1) / (STAGE_T * STAGE_SCALARS));
-                const size_t lds = (3 * (size_t)nbins + STAGE_CAP) * sizeof(u32) + STAGE_CAP * sizeof(unsigned short);
-                if (keep_hist)
-                    hipLaunchKernelGGL(k_part_offsets, dim3((nbins + 63) / 64), dim3(64 * OFF_SEGS), 0, st, (const u32*)wg_hist,
-                                       wg_off, (const u32*)bin_start, gpart, nbins);
-                hipLaunchKernelGGL(k_part_scatter_staged, dim3(gst), dim3(STAGE_T), lds, st, P, (const u32*)d_scalars,
-                                   (const AffPt*)ctx->table.p, (const u32*)bin_start, bin_cursor, tmp, (u32)set0, cb, nbins, fb,
-                                   (const u32*)wg_hist, (const u32*)wg_off);
-            } else {
-                hipLaunchKernelGGL(k_part_scatter, dim3(gpart), dim3(256), 2 * nbins * sizeof(u32), st, P,
-                                   (const u32*)d_scalars, (const AffPt*)ctx->table.p, (const u32*)bin_start, bin_cursor, tmp,
-                                   (u32)set0, cb, nbins, fb);
-            }
-            HIP_TRY(hipMemsetAsync(nheavy, 0, sizeof(u32), st));
-            hipLaunchKernelGGL(k_bin_sort, dim3(nbins), dim3(256), 0, st, (const u32*)tmp, (const u32*)bin_start, offsets,
-                               ws.sorted.p + set0 * set_cap, heavy, heavy_list, nheavy, (u32)heavy_cap, cb, nb, set_cap, fb);
+        hipLaunchKernelGGL(k_part_count, dim3(gpart), dim3(256), nbins * sizeof(u32), stream, P, (const u32*)d_scalars,
+                           (const AffPt*)ctx->table.p, bin_count, 0u, cb, nbins, fb, wg_hist);
+        hipLaunchKernelGGL(k_part_scan, dim3(1), dim3(1024), 0, stream, (const u32*)bin_count, bin_start, bin_cursor, nbins);
+        if (staged) {
+            const unsigned gst = (unsigned)((npoints * nbatch + STAGE_T * STAGE_SCALARS - 1) / (STAGE_T * STAGE_SCALARS));
+            const size_t lds = (3 * (size_t)nbins + STAGE_CAP) * sizeof(u32) + STAGE_CAP * sizeof(unsigned short);
+            if (keep_hist)
+                hipLaunchKernelGGL(k_part_offsets, dim3((nbins + 63) / 64), dim3(64 * OFF_SEGS), 0, stream, (const u32*)wg_hist,
+                                   wg_off, (const u32*)bin_start, gpart, nbins);
+            hipLaunchKernelGGL(k_part_scatter_staged, dim3(gst), dim3(STAGE_T), lds, stream, P, (const u32*)d_scalars,
+                               (const AffPt*)ctx->table.p, (const u32*)bin_start, bin_cursor, tmp, 0u, cb, nbins, fb,
+                               (const u32*)wg_hist, (const u32*)wg_off);
         } else {
-        HIP_TRY(hipMemsetAsync(counts, 0, ns * nb * sizeof(u32), st));
+            hipLaunchKernelGGL(k_part_scatter, dim3(gpart), dim3(256), 2 * nbins * sizeof(u32), stream, P,
+                               (const u32*)d_scalars, (const AffPt*)ctx->table.p, (const u32*)bin_start, bin_cursor, tmp,
+                               0u, cb, nbins, fb);
+        }
+        HIP_TRY(hipMemsetAsync(nheavy, 0, sizeof(u32), stream));
+        hipLaunchKernelGGL(k_bin_sort, dim3(nbins), dim3(256), 0, stream, (const u32*)tmp, (const u32*)bin_start, offsets,
+                           ws.sorted.p, heavy, heavy_list, nheavy, (u32)heavy_cap, cb, nb, set_cap, fb);
+    } else {
+        HIP_TRY(hipMemsetAsync(ws.counts.p, 0, nsets * nb * sizeof(u32), stream));
         const unsigned gdig = (unsigned)((npoints * nbatch + 255) / 256);
-        // k_digits indexes sets globally (b * nwin + w): it gets the unshifted arrays
-        hipLaunchKernelGGL(k_digits<0>, dim3(gdig), dim3(256), 0, st, P, (const u32*)d_scalars, ctx->table.p, ws.counts.p,
+        hipLaunchKernelGGL(k_digits<0>, dim3(gdig), dim3(256), 0, stream, P, (const u32*)d_scalars, ctx->table.p, ws.counts.p,
                            (const u32*)nullptr, (u32*)nullptr, set_cap, ws.ranks.p);
-        HIP_TRY(hipMemsetAsync(nheavy, 0, sizeof(u32), st));
-        hipLaunchKernelGGL(k_scan, dim3((unsigned)ns), dim3(1024), 0, st, counts, offsets, nb, heavy, heavy_list, nheavy,
-                           (u32)heavy_cap);
-        hipLaunchKernelGGL(k_digits<1>, dim3(gdig), dim3(256), 0, st, P, (const u32*)d_scalars, ctx->table.p, ws.counts.p,
+        HIP_TRY(hipMemsetAsync(nheavy, 0, sizeof(u32), stream));
+        hipLaunchKernelGGL(k_scan, dim3((unsigned)nsets), dim3(1024), 0, stream, ws.counts.p, offsets, nb, heavy, heavy_list,
+                           nheavy, (u32)heavy_cap);
+        hipLaunchKernelGGL(k_digits<1>, dim3(gdig), dim3(256), 0, stream, P, (const u32*)d_scalars, ctx->table.p, ws.counts.p,
                            (const u32*)ws.offsets.p, ws.sorted.p, set_cap, ws.ranks.p);
-        }
-        if (G > 1) {
-            HIP_TRY(hipEventRecord(ctx->ev_dig[g], st));
-            if (g > 0) HIP_TRY(hipStreamWaitEvent(st, ctx->ev_acc[g - 1], 0));
-        }
-        // One PIECE of this group's sets: accumulation on `ast`, everything after it (heavy buckets, bucket reduction,
-        // window sums) on `tst`.  With tst != ast the tail of a piece runs beside the accumulation of the next one: the
-        // reductions are latency chains on a fraction of the chip (0.7 ms of 3.4 at n = 2^20), the accumulation is VALU
-        // throughput — tuning key tail_pieces.
-        auto run_piece = [&](size_t ps0, size_t pns, int piece, hipStream_t ast, hipStream_t tst) {
-        // lanes per set so that THIS launch's sets fill the chip (every kernel below derives the chunk length from it)
-        const ChunkSel pcs{csel.lo, csel.hi, pns == ns ? csel.target : (u32)(118000 / pns)};
-        // (offsets, buckets, heavy are this GROUP's arrays: k_heavy's list indexes sets within the group)
-        const u32* p_off = offsets + (ps0 - set0) * (nb + 1);
-        Xyzz* p_buckets = buckets + (ps0 - set0) * (nb + nchunk);
-        const unsigned char* p_heavy = heavy + (ps0 - set0) * nb;
-        hipStream_t kst = ast;
-        if (accum_redirect) {  // sorted on ast; accumulated on accum_on, behind the previous sub-batch's accumulation
-            HIP_TRY(hipEventRecord(accum_ready, ast));
-            HIP_TRY(hipStreamWaitEvent(accum_on, accum_ready, 0));
-            kst = accum_on;
-        }
-        hipLaunchKernelGGL(k_accum, dim3((unsigned)((pns * nchunk + 255) / 256)), dim3(256), 0, kst, p_off,
-                           (const u32*)(ws.sorted.p + ps0 * set_cap), (const AffPt*)ctx->table.p, p_buckets, nb, pns, set_cap,
-                           nchunk, pcs);
-        if (accum_redirect) {
-            HIP_TRY(hipEventRecord(accum_done, accum_on));
-            if (!tail_on_accum) HIP_TRY(hipStreamWaitEvent(ast, accum_done, 0));
-        }
-        if (tail_on_accum) tst = accum_on;  // (pieces and groups are forms of a lone MSM: never together with sub-batches)
-        else if (tst != ast) {
-            HIP_TRY(hipEventRecord(ctx->ev_acc[piece], ast));
-            HIP_TRY(hipStreamWaitEvent(tst, ctx->ev_acc[piece], 0));
-        } else if (G > 1) {
-            HIP_TRY(hipEventRecord(ctx->ev_acc[g], ast));  // the next group's accumulation may start
-        }
-        hipStream_t st = tst;
-        hipLaunchKernelGGL(k_heavy, dim3(256, 64), dim3(64), 0, st, buckets, (const u32*)offsets, (const u32*)heavy_list,
-                           (const u32*)nheavy, (u32)heavy_cap, nb, nchunk, 1u, HSEG, pcs, (u32)(ps0 - set0), (u32)(ps0 - set0 + pns));
-        hipLaunchKernelGGL(k_heavy, dim3(1024, 1), dim3(64), 0, st, buckets, (const u32*)offsets, (const u32*)heavy_list,
-                           (const u32*)nheavy, (u32)heavy_cap, nb, nchunk, HSEG, 0u, pcs, (u32)(ps0 - set0), (u32)(ps0 - set0 + pns));
-        if (digit_tail) {
-            // few sets: digit-decomposed reduction (k_digit_sums / k_digit_bits), then the Horner over the bit sums
-            int logNb = 0;
-            while (((size_t)1 << logNb) < nb) ++logNb;
-            const int J = (logNb + DIGIT_BITS - 1) / DIGIT_BITS;
-            Xyzz* S = ws.lvlA[0].p + ps0 * (size_t)(J * 32);
-            Xyzz* top = ws.top.p + ps0 * top_stride;
-            Xyzz* dense = ws.dense.p + ps0 * nb;
-            if (tiled_digits) {
-                Xyzz* Gs = ws.lvlA[1].p + ps0 * (nb >> 5);
-                Xyzz* Cp = ws.lvlM[1].p + ps0 * (ntiles * 32);
-#define KZG_TILE_SUMS(R, Q)                                                                                                          \
-    hipLaunchKernelGGL((k_tile_sums_loop<R, Q>), dim3((unsigned)(pns * ntiles)), dim3(R * 16), (R * 16) * sizeof(Xyzz), st, \
-                       (const Xyzz*)p_buckets, p_off, p_heavy, dense, Gs, Cp, nb, nchunk, pcs)
-                if (tile_rows == 16) {
-                    if (ctx->tune.tile_quad) KZG_TILE_SUMS(16, true);
-                    else KZG_TILE_SUMS(16, false);
-                } else {
-                    if (ctx->tune.tile_quad) KZG_TILE_SUMS(32, true);
-                    else KZG_TILE_SUMS(32, false);
-                }
-#undef KZG_TILE_SUMS
-                if (tail_on_accum && sort_gate && !gate_recorded) {
-                    HIP_TRY(hipEventRecord(sort_gate, st));
-                    gate_recorded = true;
-                }
-                if (wide_tail) {
-                    // cells of this group: [0, pns * J * 32) digit sums, then pns * (logNb + 2) bit sums
-                    const size_t c1 = pns * (size_t)(J * 32), c2 = pns * (size_t)(logNb + 2);
-                    const size_t cbase = ps0 * (size_t)(J * 32 + logNb + 2);
-                    u32* cnt = ws.wcount.p + cbase;
-                    Xyzz* part = ws.wpart.p + cbase * WSPLIT;  // WSPLIT >= WSPLIT_S slots per cell
-                    HIP_TRY(hipMemsetAsync(cnt, 0, (c1 + c2) * sizeof(u32), st));
-                    hipLaunchKernelGGL(k_digit_sums_wide, dim3((unsigned)(c1 * WSPLIT_S)), dim3(64), 0, st, (const Xyzz*)Gs,
-                                       (const Xyzz*)Cp, S, part, cnt, nb, logNb, J, ntiles);
-                    hipLaunchKernelGGL(k_digit_bits_wide, dim3((unsigned)(c2 * WSPLIT)), dim3(64), 0, st, (const Xyzz*)S, top,
-                                       part + c1 * WSPLIT, cnt + c1, logNb, J);
-                } else {
-                    hipLaunchKernelGGL(k_digit_sums2, dim3((unsigned)(pns * (size_t)(J * 32))), dim3(64), 0, st, (const Xyzz*)Gs,
-                                       (const Xyzz*)Cp, S, nb, logNb, J, ntiles);
-                }
+    }
+    if (pev) HIP_TRY(hipEventRecord(pev[1], stream));
+    // The accumulation: VALU throughput, the chip full.  Everything after it (heavy buckets, bucket reduction, window
+    // sums) is latency chains on a fraction of the chip (0.7 ms of 3.4 at n = 2^20).
+    hipStream_t kst = stream;
+    if (link) {  // sorted on stream; accumulated on accum_on, behind the previous sub-batch's accumulation
+        HIP_TRY(hipEventRecord(link->sorted, stream));
+        HIP_TRY(hipStreamWaitEvent(link->accum_on, link->sorted, 0));
+        kst = link->accum_on;
+    }
+    hipLaunchKernelGGL(k_accum, dim3((unsigned)((nsets * nchunk + 255) / 256)), dim3(256), 0, kst, (const u32*)offsets,
+                       (const u32*)ws.sorted.p, (const AffPt*)ctx->table.p, buckets, nb, nsets, set_cap, nchunk, csel);
+    if (link) {
+        HIP_TRY(hipEventRecord(link->accumulated, link->accum_on));
+        HIP_TRY(hipStreamWaitEvent(stream, link->accumulated, 0));
+    }
+    hipLaunchKernelGGL(k_heavy, dim3(256, 64), dim3(64), 0, stream, buckets, (const u32*)offsets, (const u32*)heavy_list,
+                       (const u32*)nheavy, (u32)heavy_cap, nb, nchunk, 1u, HSEG, csel, 0u, (u32)nsets);
+    hipLaunchKernelGGL(k_heavy, dim3(1024, 1), dim3(64), 0, stream, buckets, (const u32*)offsets, (const u32*)heavy_list,
+                       (const u32*)nheavy, (u32)heavy_cap, nb, nchunk, HSEG, 0u, csel, 0u, (u32)nsets);
+    if (digit_tail) {
+        // few sets: digit-decomposed reduction (k_digit_sums / k_digit_bits), then the Horner over the bit sums
+        int logNb = 0;
+        while (((size_t)1 << logNb) < nb) ++logNb;
+        const int J = (logNb + DIGIT_BITS - 1) / DIGIT_BITS;
+        Xyzz* S = ws.lvlA[0].p;
+        Xyzz* top = ws.top.p;
+        Xyzz* dense = ws.dense.p;
+        if (tiled_digits) {
+            Xyzz* Gs = ws.lvlA[1].p;
+            Xyzz* Cp = ws.lvlM[1].p;
+#define KZG_TILE_SUMS(R, Q)                                                                                                       \
+    hipLaunchKernelGGL((k_tile_sums_loop<R, Q>), dim3((unsigned)(nsets * ntiles)), dim3(R * 16), (R * 16) * sizeof(Xyzz), stream, \
+                       (const Xyzz*)buckets, (const u32*)offsets, (const unsigned char*)heavy, dense, Gs, Cp, nb, nchunk, csel)
+            if (tile_rows == 16) {
+                if (ctx->tune.tile_quad) KZG_TILE_SUMS(16, true);
+                else KZG_TILE_SUMS(16, false);
             } else {
-                hipLaunchKernelGGL(k_fold_buckets, dim3((unsigned)((pns * nb + 127) / 128)), dim3(128), 0, st,
-                                   (const Xyzz*)p_buckets, p_off, p_heavy, dense, nb, pns, nchunk,
-                                   pcs);
-                hipLaunchKernelGGL(k_digit_sums, dim3((unsigned)(pns * (size_t)(J * 32))), dim3(DIGIT_T), DIGIT_T * sizeof(Xyzz),
-                                   st, (const Xyzz*)dense, S, nb, logNb, J);
+                if (ctx->tune.tile_quad) KZG_TILE_SUMS(32, true);
+                else KZG_TILE_SUMS(32, false);
             }
-            if (!(tiled_digits && wide_tail))
-                hipLaunchKernelGGL(k_digit_bits, dim3((unsigned)(pns * (size_t)(logNb + 2))), dim3(64), 0, st, (const Xyzz*)S,
-                                   top, logNb, J);
-            if (wide_tail)
-                hipLaunchKernelGGL(k_winsum_wide, dim3((unsigned)pns), dim3(64), 0, st, (const Xyzz*)top, ws.win.p + ps0,
-                                   logNb, 0);
-            else
-                hipLaunchKernelGGL(k_winsum, dim3((unsigned)((pns + 63) / 64)), dim3(64), 0, st, (const Xyzz*)top,
-                                   ws.win.p + ps0, pns, logNb, 0);
-            finA = nullptr;
-            finM = ws.win.p;
-            return;
+#undef KZG_TILE_SUMS
+            if (wide_tail) {
+                // cells: [0, nsets * J * 32) digit sums, then nsets * (logNb + 2) bit sums
+                const size_t c1 = nsets * (size_t)(J * 32), c2 = nsets * (size_t)(logNb + 2);
+                u32* cnt = ws.wcount.p;
+                Xyzz* part = ws.wpart.p;  // WSPLIT >= WSPLIT_S slots per cell
+                HIP_TRY(hipMemsetAsync(cnt, 0, (c1 + c2) * sizeof(u32), stream));
+                hipLaunchKernelGGL(k_digit_sums_wide, dim3((unsigned)(c1 * WSPLIT_S)), dim3(64), 0, stream, (const Xyzz*)Gs,
+                                   (const Xyzz*)Cp, S, part, cnt, nb, logNb, J, ntiles);
+                hipLaunchKernelGGL(k_digit_bits_wide, dim3((unsigned)(c2 * WSPLIT)), dim3(64), 0, stream, (const Xyzz*)S, top,
+                                   part + c1 * WSPLIT, cnt + c1, logNb, J);
+            } else {
+                hipLaunchKernelGGL(k_digit_sums2, dim3((unsigned)(nsets * (size_t)(J * 32))), dim3(64), 0, stream, (const Xyzz*)Gs,
+                                   (const Xyzz*)Cp, S, nb, logNb, J, ntiles);
+            }
+        } else {
+            hipLaunchKernelGGL(k_fold_buckets, dim3((unsigned)((nsets * nb + 127) / 128)), dim3(128), 0, stream,
+                               (const Xyzz*)buckets, (const u32*)offsets, (const unsigned char*)heavy, dense, nb, nsets,
+                               nchunk, csel);
+            hipLaunchKernelGGL(k_digit_sums, dim3((unsigned)(nsets * (size_t)(J * 32))), dim3(DIGIT_T), DIGIT_T * sizeof(Xyzz),
+                               stream, (const Xyzz*)dense, S, nb, logNb, J);
         }
+        if (!(tiled_digits && wide_tail))
+            hipLaunchKernelGGL(k_digit_bits, dim3((unsigned)(nsets * (size_t)(logNb + 2))), dim3(64), 0, stream, (const Xyzz*)S,
+                               top, logNb, J);
+        if (wide_tail)
+            hipLaunchKernelGGL(k_winsum_wide, dim3((unsigned)nsets), dim3(64), 0, stream, (const Xyzz*)top, ws.win.p, logNb, 0);
+        else
+            hipLaunchKernelGGL(k_winsum, dim3((unsigned)((nsets + 63) / 64)), dim3(64), 0, stream, (const Xyzz*)top, ws.win.p,
+                               nsets, logNb, 0);
+        finM = ws.win.p;
+    } else {
         // bucket-reduction tree: GRP-ary levels while they are throughput work (nb -> nb/GRP -> ...), then the
         // B + 2 concurrent plain sums of k_top and the short per-window Horner of k_winsum
         size_t nin = nb;
         int logS = 0, lvl = 0;
-        const Xyzz *inA = p_buckets, *inM = nullptr;
+        const Xyzz *inA = buckets, *inM = nullptr;
         do {
             // level 0 also folds each bucket's pieces (entries/chunk + 1 of them): keep >= ~128k lanes in flight
             int grp = GRP, lg = 3;
             if (lvl == 0)
-                while (grp > 2 && sets_per_group * ((nin + grp - 1) / grp) < ((size_t)1 << 17)) {
+                while (grp > 2 && nsets * ((nin + grp - 1) / grp) < ((size_t)1 << 17)) {
                     grp >>= 1;
                     --lg;
                 }
             const size_t nout = (nin + grp - 1) / grp;
-            Xyzz *oA = ws.lvlA[lvl & 1].p + ps0 * nout, *oM = ws.lvlM[lvl & 1].p + ps0 * nout;
-            const unsigned grid = (unsigned)((pns * nout + 127) / 128);
+            Xyzz *oA = ws.lvlA[lvl & 1].p, *oM = ws.lvlM[lvl & 1].p;
+            const unsigned grid = (unsigned)((nsets * nout + 127) / 128);
             if (lvl == 0)
-                hipLaunchKernelGGL(k_level<true>, dim3(grid), dim3(128), 0, st, inA, inM, oA, oM, nin, pns, logS,
-                                   (const u32*)offsets, p_heavy, nb, nchunk, grp, pcs);
+                hipLaunchKernelGGL(k_level<true>, dim3(grid), dim3(128), 0, stream, inA, inM, oA, oM, nin, nsets, logS,
+                                   (const u32*)offsets, (const unsigned char*)heavy, nb, nchunk, grp, csel);
             else
-                hipLaunchKernelGGL(k_level<false>, dim3(grid), dim3(128), 0, st, inA, inM, oA, oM, nin, pns, logS,
-                                   (const u32*)nullptr, (const unsigned char*)nullptr, nb, nchunk, grp, pcs);
+                hipLaunchKernelGGL(k_level<false>, dim3(grid), dim3(128), 0, stream, inA, inM, oA, oM, nin, nsets, logS,
+                                   (const u32*)nullptr, (const unsigned char*)nullptr, nb, nchunk, grp, csel);
             inA = oA;
             inM = oM;
             nin = nout;
@@ -3120,68 +2904,28 @@ void msm_enqueue(MsmContext* ctx, void* d_out, const void* d_scalars, size_t npo
         if (use_top) {
             int B = 0;
             while (((size_t)1 << B) < nin) ++B;
-            Xyzz* top = ws.top.p + ps0 * top_stride;
-            hipLaunchKernelGGL(k_top, dim3((unsigned)(pns * (size_t)(B + 2))), dim3(TOPT), TOPT * sizeof(Xyzz), st, inA, inM,
+            Xyzz* top = ws.top.p;
+            hipLaunchKernelGGL(k_top, dim3((unsigned)(nsets * (size_t)(B + 2))), dim3(TOPT), TOPT * sizeof(Xyzz), stream, inA, inM,
                                top, nin, B);
             if (wide_tail)
-                hipLaunchKernelGGL(k_winsum_wide, dim3((unsigned)pns), dim3(64), 0, st, (const Xyzz*)top, ws.win.p + ps0, B,
-                                   logS);
+                hipLaunchKernelGGL(k_winsum_wide, dim3((unsigned)nsets), dim3(64), 0, stream, (const Xyzz*)top, ws.win.p, B, logS);
             else
-                hipLaunchKernelGGL(k_winsum, dim3((unsigned)((pns + 63) / 64)), dim3(64), 0, st, (const Xyzz*)top,
-                                   ws.win.p + ps0, pns, B, logS);
-            finA = nullptr;
+                hipLaunchKernelGGL(k_winsum, dim3((unsigned)((nsets + 63) / 64)), dim3(64), 0, stream, (const Xyzz*)top, ws.win.p,
+                                   nsets, B, logS);
             finM = ws.win.p;
         } else {
             // plain tree: one (A, M) node per set, in the level buffers written last
             finA = ws.lvlA[(lvl - 1) & 1].p;
             finM = ws.lvlM[(lvl - 1) & 1].p;
         }
-            };
-        {
-            // pieces: only for one group of few large sets (a single large MSM) in the digit-tail form
-            int pieces = 1;
-            // Measured (tools/time_pieces.py, profiles/NOTES.md): n = 2^20 in 1 / 2 / 3 / 4 pieces 3.50 / 3.54 / 4.00 / 3.92 ms.
-            // The side tail does run inside the next accumulation (the trace shows it there, three times slower than
-            // alone, the accumulation none the slower), but two accumulation launches with the shorter chunks a piece needs
-            // to fill the chip cost 0.25 ms more than one, and the LAST piece's tail — latency chains that do not shrink
-            // with the number of sets — stays exposed.  One piece is the default; the key stays for the measurement.
-            if (G == 1 && nbatch == 1 && digit_tail && tiled_digits && wide_tail && ns >= 4 && ctx->tune.tail_pieces > 1) {
-                pieces = ctx->tune.tail_pieces;
-                if (pieces > MsmContext::MAXG) pieces = MsmContext::MAXG;
-                if ((size_t)pieces > ns) pieces = (int)ns;
-            }
-            if (pev) HIP_TRY(hipEventRecord(pev[1], st));
-            size_t done = 0;
-            for (int p = 0; p < pieces; ++p) {
-                const size_t pns = (ns - done) / (size_t)(pieces - p);
-                hipStream_t tst = st;
-                if (p + 1 < pieces) {  // the last piece's tail stays on the launch stream
-                    if (!ctx->aux[p]) HIP_TRY(hipStreamCreateWithFlags(&ctx->aux[p], hipStreamNonBlocking));
-                    if (!ctx->ev_acc[p]) HIP_TRY(hipEventCreateWithFlags(&ctx->ev_acc[p], hipEventDisableTiming));
-                    if (!ctx->ev_done[p]) HIP_TRY(hipEventCreateWithFlags(&ctx->ev_done[p], hipEventDisableTiming));
-                    tst = ctx->aux[p];
-                }
-                run_piece(set0 + done, pns, p, st, tst);
-                if (tst != st) HIP_TRY(hipEventRecord(ctx->ev_done[p], tst));
-                done += pns;
-            }
-            // the launch stream joins the side tails only now: a wait placed earlier would hold the next piece's accumulation
-            for (int p = 0; p + 1 < pieces; ++p) HIP_TRY(hipStreamWaitEvent(stream, ctx->ev_done[p], 0));
-            if (pev) HIP_TRY(hipEventRecord(pev[2], st));
-            if (G > 1) {
-                HIP_TRY(hipEventRecord(ctx->ev_done[g], st));
-                HIP_TRY(hipStreamWaitEvent(stream, ctx->ev_done[g], 0));
-            }
-        }
     }
-    const hipStream_t fin_stream = tail_on_accum ? accum_on : stream;
-    if (tail_on_accum && sort_gate && !gate_recorded) HIP_TRY(hipEventRecord(sort_gate, fin_stream));  // reduction forms without tiles
+    if (pev) HIP_TRY(hipEventRecord(pev[2], stream));
     if (wide_tail && !ctx->prepared && out_mode == OUT_JACOBIAN && nwin > 1) {
         // few independent Horner chains: one wave each, limb-parallel doublings
-        hipLaunchKernelGGL(k_final_wide, dim3((unsigned)nbatch), dim3(64), 0, fin_stream, finM, d_out, nwin, c);
+        hipLaunchKernelGGL(k_final_wide, dim3((unsigned)nbatch), dim3(64), 0, stream, finM, d_out, nwin, c);
     } else {
         const size_t nfinal = out_mode == OUT_WINDOWS ? nbatch * (size_t)nwin : nbatch;
-        hipLaunchKernelGGL(k_final, dim3((unsigned)((nfinal + 63) / 64)), dim3(64), 0, fin_stream, finA, finM, d_out, nbatch, nwin,
+        hipLaunchKernelGGL(k_final, dim3((unsigned)((nfinal + 63) / 64)), dim3(64), 0, stream, finA, finM, d_out, nbatch, nwin,
                            c, ctx->prepared ? 1 : 0, out_mode);
     }
     if (pev) {
@@ -3189,6 +2933,122 @@ void msm_enqueue(MsmContext* ctx, void* d_out, const void* d_scalars, size_t npo
         ctx->ev_used += 4;
     }
     HIP_TRY(hipGetLastError());
+}
+
+// A batch of large MSMs whose sets together have more coarse bins than the two-level sort's LDS counters hold
+// (MAX_BINS) would take the one-level sort — 1.2 ms instead of 0.3 per 2^20-point MSM (measured: 4 x 2^20 in one call
+// 4.2 ms per MSM against 3.4 for one).  Such a batch runs as sub-batches that fit.  Round 6: ANY batch of large MSMs is
+// cut into sub-batches, and only their accumulations stay on the caller's stream; the sort and the reduction of a
+// sub-batch run on a high-priority side stream beside another sub-batch's accumulation (MsmContext::sub_stream;
+// tuning key sub_streams = how many rotate, 0 = everything on the caller's stream and workspace as in round 5).
+// false: this batch is not cut (nothing was done; the caller launches it whole).
+static bool enqueue_sub_batches(MsmContext* ctx, void* d_out, const void* d_scalars, size_t npoints, size_t nbatch, int mont,
+                                hipStream_t stream, int out_mode, bool reserve_only) {
+    if (nbatch <= 1 || ctx->tune.one_level_sort || npoints < ((size_t)1 << 15)) return false;
+    const int nwin = ctx->nwin;
+    const size_t nb = ctx->nb;
+    const int fb0 = ctx->tune.fine_bits >= FINE_BITS_MIN && ctx->tune.fine_bits <= FINE_BITS_MAX ? ctx->tune.fine_bits : FINE_BITS_MIN;
+    const size_t bins_per_msm = (nb >> fb0) * (ctx->prepared ? (size_t)1 : (size_t)nwin);
+    size_t per = bins_per_msm ? MAX_BINS / bins_per_msm : 0;
+    // Measured (tools/ab_batched.py, profiles/NOTES.md §20): 4 or 8 x 2^16 in one call 0.70 -> 0.645 ms per MSM with six side
+    // streams (three: 0.70), 4 x 2^17 0.87 -> 0.82 — there the reduction chains of the sub-batches (0.7 ms each, a
+    // fraction of the chip) overlap each other.  From
+    // 2^18 points on an accumulation fills every register of every SIMD for milliseconds and whatever is launched
+    // beside it, at any stream priority, crawls (k_tile_sums_loop 2.9 ms instead of 0.32, k_digit_sums_wide 1.6 instead
+    // of 0.09) and delays the next sub-batch: 4 x 2^20 3.26 ms per MSM on one stream, 3.3 - 3.5 with side streams.
+    // So the side streams serve batches of MSMs below 2^18 points; tuning key sub_large = 1 lifts the limit.
+    int nside = ctx->tune.sub_streams < 0 ? 0 : ctx->tune.sub_streams > MsmContext::MAXSUB ? MsmContext::MAXSUB : ctx->tune.sub_streams;
+    if (npoints >= ((size_t)1 << 18) && !ctx->tune.sub_large) nside = 0;
+    if (nside > 0 && per >= 1) {
+        // at least two sub-batches; from 2^18 points an MSM's accumulation alone fills the chip for a millisecond
+        const size_t cap = npoints >= ((size_t)1 << 18) ? (size_t)1 : (nbatch + 1) / 2;
+        if (per > cap) per = cap;
+    }
+    if (nb < ((size_t)1 << fb0) || per < 1 || per >= nbatch) return false;
+    const size_t out_stride = out_mode == OUT_COMPRESSED ? 48 : out_mode == OUT_WINDOWS ? (size_t)nwin * 144 : 144;
+    const size_t nsub = (nbatch + per - 1) / per;
+    const int lanes = nside > 0 ? (int)(nsub < (size_t)nside ? nsub : (size_t)nside) : 0;  // side streams in use
+    if (lanes > 0 && !ctx->sub_stream[lanes - 1]) {
+        int least = 0, greatest = 0;
+        HIP_TRY(hipDeviceGetStreamPriorityRange(&least, &greatest));
+        const int prio = ctx->tune.sub_prio ? greatest : 0;
+        for (int k = 0; k < lanes; ++k) {
+            if (!ctx->sub_stream[k]) HIP_TRY(hipStreamCreateWithPriority(&ctx->sub_stream[k], hipStreamNonBlocking, prio));
+            if (!ctx->ev_sub_join[k]) HIP_TRY(hipEventCreateWithFlags(&ctx->ev_sub_join[k], hipEventDisableTiming));
+            if (!ctx->ev_sorted[k]) HIP_TRY(hipEventCreateWithFlags(&ctx->ev_sorted[k], hipEventDisableTiming));
+            if (!ctx->ev_accd[k]) HIP_TRY(hipEventCreateWithFlags(&ctx->ev_accd[k], hipEventDisableTiming));
+        }
+    }
+    if (reserve_only) {  // the first sub-batch is the largest; every stream of the rotation gets its workspace
+        if (lanes == 0)
+            enqueue_buckets(ctx, ctx->workspace_for(stream), nullptr, nullptr, npoints, per, mont, stream, out_mode, true, nullptr);
+        for (int k = 0; k < lanes; ++k)
+            enqueue_buckets(ctx, ctx->workspace_for(ctx->sub_stream[k]), nullptr, nullptr, npoints, per, mont, ctx->sub_stream[k],
+                            out_mode, true, nullptr);
+        return true;
+    }
+    try {
+        if (lanes > 0) {
+            if (!ctx->ev_sub_fork) HIP_TRY(hipEventCreateWithFlags(&ctx->ev_sub_fork, hipEventDisableTiming));
+            // whatever produced the scalars (and last used the outputs) on the caller's stream comes first
+            HIP_TRY(hipEventRecord(ctx->ev_sub_fork, stream));
+            for (int k = 0; k < lanes; ++k) HIP_TRY(hipStreamWaitEvent(ctx->sub_stream[k], ctx->ev_sub_fork, 0));
+        }
+        size_t k = 0;
+        for (size_t b0 = 0; b0 < nbatch; b0 += per, ++k) {
+            const size_t nbp = b0 + per <= nbatch ? per : nbatch - b0;
+            void* const out = d_out ? (unsigned char*)d_out + b0 * out_stride : nullptr;
+            const void* const scalars = d_scalars ? (const unsigned char*)d_scalars + b0 * npoints * 32 : nullptr;
+            if (lanes == 0) {
+                enqueue_buckets(ctx, ctx->workspace_for(stream), out, scalars, npoints, nbp, mont, stream, out_mode, false, nullptr);
+                continue;
+            }
+            const int lane = (int)(k % (size_t)lanes);
+            const hipStream_t st = ctx->sub_stream[lane];
+            const SubLink link{stream, ctx->ev_sorted[lane], ctx->ev_accd[lane]};
+            enqueue_buckets(ctx, ctx->workspace_for(st), out, scalars, npoints, nbp, mont, st, out_mode, false, &link);
+        }
+    } catch (...) {
+        // the side streams that were given work still join the caller's stream: what the caller enqueues next (or its
+        // synchronisation before freeing the buffers) comes after them.  Errors of these calls are ignored.
+        for (int j = 0; j < lanes; ++j) {
+            (void)hipEventRecord(ctx->ev_sub_join[j], ctx->sub_stream[j]);
+            (void)hipStreamWaitEvent(stream, ctx->ev_sub_join[j], 0);
+        }
+        throw;
+    }
+    for (int j = 0; j < lanes; ++j) {
+        HIP_TRY(hipEventRecord(ctx->ev_sub_join[j], ctx->sub_stream[j]));
+        HIP_TRY(hipStreamWaitEvent(stream, ctx->ev_sub_join[j], 0));
+    }
+    return true;
+}
+
+// enqueue nbatch MSMs over the first npoints bases; d_scalars / d_out device pointers
+// reserve_only: size and allocate the workspace `stream` will use for this shape, launch nothing (hipMalloc
+// synchronises the device, so callers that must not stall a running pipeline reserve during set-up)
+void msm_enqueue(MsmContext* ctx, void* d_out, const void* d_scalars, size_t npoints, size_t nbatch, int mont,
+                 hipStream_t stream, int out_mode, bool reserve_only, size_t nseg) {
+    if (npoints * (nseg ? nseg : 1) > ctx->n) throw HipErr{hipErrorInvalidValue, "npoints exceeds the prepared size"};
+    if ((nseg || out_mode == OUT_XYZZ) && !ctx->fbw)
+        throw HipErr{hipErrorInvalidValue, "segmented / XYZZ-output MSMs need the wide-table path"};
+    if (nbatch == 0) return;
+    const size_t nsets = ctx->prepared ? nbatch : nbatch * (size_t)ctx->nwin;
+    const size_t set_cap = ctx->prepared ? npoints * (size_t)ctx->nwin : (ctx->glv ? 2 * npoints : npoints);
+    if (npoints == 0) {
+        if (reserve_only) return;
+        if (out_mode == OUT_COMPRESSED) throw HipErr{hipErrorInvalidValue, "empty MSM in compressed mode"};
+        HIP_TRY(hipMemsetAsync(d_out, 0, nbatch * 144, stream));
+        return;
+    }
+    if (set_cap >= ((size_t)1 << 31) || nsets * ctx->nb >= ((size_t)1 << 40)) throw HipErr{hipErrorInvalidValue, "MSM too large"};
+    // the caller's stream takes its workspace before any side stream of a batch does: the handle's first workspace goes
+    // to the first caller stream (MsmContext::workspace_for)
+    Workspace& ws = ctx->workspace_for(stream);
+    if (ctx->fbw)
+        enqueue_wide(ctx, ws, d_out, d_scalars, npoints, nbatch, mont, stream, out_mode, reserve_only, nseg);
+    else if (!enqueue_sub_batches(ctx, d_out, d_scalars, npoints, nbatch, mont, stream, out_mode, reserve_only))
+        enqueue_buckets(ctx, ws, d_out, d_scalars, npoints, nbatch, mont, stream, out_mode, reserve_only, nullptr);
 }
 
 void msm_lock(MsmContext* ctx) { ctx->mu.lock(); }

@@ -481,13 +481,11 @@ int main() {
     EXPECT(!o.parse("lgc=1", &err) && !o.parse("lgc=9", &err) && !o.parse("window=1", &err) && !o.parse("window_prepared=1", &err));
     EXPECT(!o.parse("sha_lanes=2", &err) && !o.parse("wide_fold_max=-1", &err) && !o.parse("tile_rows=8", &err));
     EXPECT(o.parse("spl=16;blocksum_threads=128;fine_bits=10;lgc=2;window=2;sha_lanes=1;sub_streams=0", &err));
-    {   // keys that are forms of the same stretch of the engine do not combine
+    {   // the keys of the overlap forms that were removed (profiles/NOTES.md) are no keys any more
         Options x;
-        EXPECT(x.parse("sort_ahead=1;groups=2", &err) && !x.consistent(&err) && err.find("sort_ahead") != std::string::npos);
-        Options y;
-        EXPECT(y.parse("sort_ahead=1;sub_streams=2;sub_prio=0", &err) && y.consistent(&err));
-        Options z;
-        EXPECT(z.parse("sort_ahead=1;tail_pieces=2", &err) && !z.consistent(&err));
+        EXPECT(!x.parse("groups=2", &err) && err.find("unknown key 'groups'") != std::string::npos);
+        EXPECT(!x.parse("tail_pieces=2", &err) && err.find("unknown key 'tail_pieces'") != std::string::npos);
+        EXPECT(!x.parse("sort_ahead=1", &err) && err.find("unknown key 'sort_ahead'") != std::string::npos);
     }
     // resolve: defaults < environment < struct
     setenv("KZGAMD_TUNING", "spl=2;lgc=8", 1);
@@ -524,7 +522,7 @@ int main() {
     assert res.returncode == 0 and "fails 0" in res.stdout, res.stdout + res.stderr
     keys = [ln.split()[1:] for ln in res.stdout.splitlines() if ln.startswith("KEY ")]
     names = [k[0] for k in keys]
-    assert len(names) == len(set(names)) == 49
+    assert len(names) == len(set(names)) == 46
     for name, d, lo, hi in keys:
         assert re.fullmatch(r"[a-z0-9_]+", name) and int(lo) <= int(d) <= int(hi), name
     # one row per key, same default and range

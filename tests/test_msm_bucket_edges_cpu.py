@@ -36,7 +36,7 @@ def test_constants_match_the_source():
     g = [int(x) for x in m.groups()]
     assert tuple((1 << g[i], g[i + 1]) for i in range(0, 8, 2)) + ((0, g[8]),) == bp.LGC_BY_SIZE
     assert "int lgc_lo = lgc > 6 ? lgc - 2 : (lgc > 4 ? 4 : lgc);" in src
-    assert "const ChunkSel csel{lgc_lo, lgc, (u32)(%d / sets_per_group)};" % bp.LANE_TARGET in src
+    assert "const ChunkSel csel{lgc_lo, lgc, (u32)(%d / nsets)};" % bp.LANE_TARGET in src
     assert re.search(r"k_heavy, dim3\(%d, 64\), dim3\(64\)" % bp.K_HEAVY_GRID_X, src)
     assert "const bool use_top = nsets <= %d;" % bp.USE_TOP_MAX_SETS in src
     assert re.search(r"while \(l > cs\.lo && \(total >> l\) < cs\.target\) --l;", src)

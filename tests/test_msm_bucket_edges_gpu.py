@@ -19,7 +19,7 @@ pytestmark = pytest.mark.gpu
 
 # forms of the engine (tuning keys added to the steering ones); keys an entry point ignores at a size change nothing
 ALL_FORMS = [{}, {"one_level_sort": 1}, {"direct_scatter": 1}, {"scatter_atomics": 1}, {"no_wide_tail": 1}, {"tree_tail": 1},
-             {"digit_min_log": 10}, {"digit_min_log": 10, "flat_digits": 1}, {"tail_pieces": 2}, {"groups": 2}]
+             {"digit_min_log": 10}, {"digit_min_log": 10, "flat_digits": 1}]
 TWO_FORMS = [{}, {"digit_min_log": 10}]  # the (A, M) tree with load_bucket, and the tiled digit reduction
 
 CASES = {
