@@ -530,7 +530,8 @@ void kzgamd_p2_add(blst_p2 *out, const blst_p2 *a, const blst_p2 *b);
  *
  * out[i] = scalars[i] * (*base), i < n; base == NULL: the generator.  Scalars are Montgomery blst_fr (as G1Mul/G2Mul take
  * them).  The base is a Jacobian point of the prime-order subgroup with any Z (Z == 0: every output is infinity).  The G1
- * base is tested (blst_p1_in_g1); a G2 base is the caller's responsibility, like every blst_p2 this library accepts: for
+ * base is tested (blst_p1_in_g1); a G2 base is the caller's responsibility, like every blst_p2 this library accepts
+ * (kzgamd_p2_in_g2 tests one, kzgamd_g2_uncompress_batch with check_subgroup tests them as they are parsed): for
  * one outside the subgroup the outputs are still the multiples k_i * base of the curve's group law.
  * n == 0: success, nothing written, the pointers are not looked at.
  *
@@ -556,6 +557,56 @@ int kzgamd_g2_mul_batch(blst_p2 *out, const blst_p2 *base, const blst_fr *scalar
 int kzgamd_generate_trusted_setup(void *ntt, blst_p1 *g1_monomial, blst_p1 *g1_lagrange, blst_p2 *g2_monomial,
                                   size_t num_g1, size_t num_g2, const uint8_t secret[32], const KzgAmdConfig *cfg);
 int kzgamd_group_mul_info(size_t *slice_points, int *g1_window_bits, int *g2_window_bits);
+
+/* Batched point serialisation ON THE GPU: G1::from_bytes / to_bytes / is_valid, G2::from_bytes / to_bytes and
+ * G1Affine::into_affines of the reference (kzg/src/lib.rs:89-99, 400-402, 255-265) for many points in one call.
+ * Handle-less, as the calls above: the calling thread's current device (cfg->device, when cfg is given and names one),
+ * host buffers, thread-safe, a stream per call.
+ *
+ * Format: ZCash-compressed, 48 bytes in G1 and 96 in G2 (x.c1 | x.c0), big-endian, the three flag bits on top, as
+ * kzgamd_p2_uncompress / kzgamd_p2_compress and bytes_to_kzg_commitment read and write it.
+ * Inputs of compress / to_affine: Jacobian points with canonical coordinates (below p), as blst produces them, any Z.
+ * The identity is Z == 0 (all-zero limbs) whatever X and Y hold; it compresses to 0xc0 00 .. 00 and its affine form is
+ * (0, 0), blst's affine infinity.
+ * uncompress: out[i] has Z = 1 and canonical Montgomery coordinates; the identity is all-zero.  status[i] (status may be
+ * NULL): 0 ok; 1 not a valid encoding (flag bits, a coordinate >= p, no point with that x); 2 on the curve but outside
+ * the prime-order subgroup, given only when check_subgroup != 0 (G1: phi(P) == -[x^2]P; G2: psi(P) == [x]P).  An entry
+ * whose status is not 0 is written all-zero.
+ *
+ * Return codes:  0 every point was accepted (compress / to_affine: done);  1 at least one point was refused, outputs
+ * and statuses are written;  -1 a needed pointer is NULL;  -2 or -(100 + hipError_t) device errors (-2 also for a
+ * malformed cfg).  n == 0: success, nothing written, the pointers are not looked at.
+ * cfg may be NULL.  Its tuning string takes ONE key, of these calls alone and not listed by kzgamd_tuning_keys:
+ * codec_slice=<points per slice of workspace: a power of two, at least 64>; any other key fails the call.  Counts above
+ * the slice run slice by slice through one workspace; kzgamd_codec_info reports the default (may be NULL; returns 0).
+ * Everything runs on the GPU for every n >= 1: a call costs a stream, its workspace, the copies and a launch whatever
+ * n is, so a caller with ONE point is better served by the host helpers (kzgamd_p2_uncompress, kzgamd_p2_compress,
+ * kzgamd_p2_in_g2, bytes_to_kzg_commitment).
+ * kzgamd_p2_in_g2 is that subgroup test for one point on the host (no GPU involved): 1 the point is in G2 (the identity
+ * included), 0 it is not, -1 NULL.  The point must be on the curve, as every decoded point is. */
+int kzgamd_g1_compress_batch(uint8_t *out48, const blst_p1 *in, size_t n, const KzgAmdConfig *cfg);
+int kzgamd_g1_to_affine_batch(blst_p1_affine *out, const blst_p1 *in, size_t n, const KzgAmdConfig *cfg);
+int kzgamd_g1_uncompress_batch(blst_p1 *out, uint8_t *status, const uint8_t *in48, size_t n, int check_subgroup,
+                               const KzgAmdConfig *cfg);
+int kzgamd_g2_compress_batch(uint8_t *out96, const blst_p2 *in, size_t n, const KzgAmdConfig *cfg);
+int kzgamd_g2_uncompress_batch(blst_p2 *out, uint8_t *status, const uint8_t *in96, size_t n, int check_subgroup,
+                               const KzgAmdConfig *cfg);
+int kzgamd_p2_in_g2(const blst_p2 *p);
+int kzgamd_codec_info(size_t *slice_points);
+/* Trusted-setup files of ANY size, host text around the calls above, in the layout load_trusted_setup_file reads (and
+ * tests/golden/trusted_setup.txt has): the two counts, then the Lagrange G1 points in natural order, the G2 points and
+ * the monomial G1 points; lowercase hex, one point per line.  cfg as above (codec_slice).
+ * write compresses the three arrays on the GPU and writes the text to `out` (flushed, not closed).
+ * read: on entry *num_g1 and *num_g2 are the capacities of the arrays, on return the counts of the file.  The points
+ * are parsed on the GPU with the subgroup test on for all three arrays; whitespace as load_trusted_setup_file accepts
+ * it.  Any of the three arrays may be NULL: that section is skipped (with all three NULL the call only reads the counts).
+ * Return codes:  0 ok;  1 malformed text or a count that does not parse;  2 a capacity is too small (the counts are
+ * still written, no point is);  3 a point was refused (such entries are all-zero, the others are written);
+ * -1 a needed pointer is NULL;  -2 or -(100 + hipError_t) device errors, a malformed cfg, a failed write. */
+int kzgamd_write_trusted_setup_file(FILE *out, const blst_p1 *g1_monomial, const blst_p1 *g1_lagrange,
+                                    const blst_p2 *g2_monomial, size_t num_g1, size_t num_g2, const KzgAmdConfig *cfg);
+int kzgamd_read_trusted_setup_file(FILE *in, blst_p1 *g1_monomial, blst_p1 *g1_lagrange, blst_p2 *g2_monomial,
+                                   size_t *num_g1, size_t *num_g2, const KzgAmdConfig *cfg);
 
 typedef struct { uint8_t bytes[2048]; } Cell;
 C_KZG_RET compute_cells_and_kzg_proofs(Cell *cells, KZGProof *proofs, const Blob *blob, const CKZGSettings *s);

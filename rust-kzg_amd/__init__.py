@@ -88,6 +88,9 @@ EXPORTS = [
     "kzgamd_compute_blob_kzg_proof_device",
     "kzgamd_p2_uncompress", "kzgamd_p2_compress", "kzgamd_p2_generator", "kzgamd_p2_mult", "kzgamd_p2_add",
     "kzgamd_g1_mul_batch", "kzgamd_g2_mul_batch", "kzgamd_generate_trusted_setup", "kzgamd_group_mul_info",
+    "kzgamd_g1_compress_batch", "kzgamd_g1_to_affine_batch", "kzgamd_g1_uncompress_batch", "kzgamd_g2_compress_batch",
+    "kzgamd_g2_uncompress_batch", "kzgamd_p2_in_g2", "kzgamd_codec_info",
+    "kzgamd_write_trusted_setup_file", "kzgamd_read_trusted_setup_file",
     "kzgamd_load_trusted_setup_file_multi", "kzgamd_free_trusted_setup_multi", "kzgamd_blob_to_kzg_commitment_batch_multi",
     "kzgamd_compute_blob_kzg_proof_batch_multi", "kzgamd_compute_cells_and_kzg_proofs_batch_multi",
     "kzgamd_verify_blob_kzg_proof_batch_multi", "kzgamd_mult_pippenger_prepared_multi", "kzgamd_shard_range",
@@ -376,6 +379,20 @@ def lib():
     L.kzgamd_generate_trusted_setup.argtypes = [vp, vp, vp, vp, C.c_size_t, C.c_size_t, vp, vp]
     L.kzgamd_group_mul_info.restype = C.c_int
     L.kzgamd_group_mul_info.argtypes = [vp, vp, vp]
+    for name in ("kzgamd_g1_compress_batch", "kzgamd_g1_to_affine_batch", "kzgamd_g2_compress_batch"):
+        getattr(L, name).restype = C.c_int
+        getattr(L, name).argtypes = [vp, vp, C.c_size_t, vp]
+    for name in ("kzgamd_g1_uncompress_batch", "kzgamd_g2_uncompress_batch"):
+        getattr(L, name).restype = C.c_int
+        getattr(L, name).argtypes = [vp, vp, vp, C.c_size_t, C.c_int, vp]
+    L.kzgamd_p2_in_g2.restype = C.c_int
+    L.kzgamd_p2_in_g2.argtypes = [vp]
+    L.kzgamd_codec_info.restype = C.c_int
+    L.kzgamd_codec_info.argtypes = [vp]
+    L.kzgamd_write_trusted_setup_file.restype = C.c_int
+    L.kzgamd_write_trusted_setup_file.argtypes = [vp, vp, vp, vp, C.c_size_t, C.c_size_t, vp]
+    L.kzgamd_read_trusted_setup_file.restype = C.c_int
+    L.kzgamd_read_trusted_setup_file.argtypes = [vp, vp, vp, vp, vp, vp, vp]
     L.kzgamd_load_trusted_setup_file_multi.restype = C.c_int
     L.kzgamd_load_trusted_setup_file_multi.argtypes = [vp, vp, sz, vp]
     L.kzgamd_free_trusted_setup_multi.restype = None
@@ -514,14 +531,14 @@ def msm_reserve(handle, npoints, nbatch, stream=0):
 _libc = None
 
 
-def _fopen(path):
+def _fopen(path, mode=b"r"):
     global _libc
     if _libc is None:
         _libc = C.CDLL(None)
         _libc.fopen.restype = C.c_void_p
         _libc.fopen.argtypes = [C.c_char_p, C.c_char_p]
         _libc.fclose.argtypes = [C.c_void_p]
-    f = _libc.fopen(os.fsencode(path), b"r")
+    f = _libc.fopen(os.fsencode(path), mode)
     if not f:
         raise FileNotFoundError(path)
     return f
@@ -1359,6 +1376,107 @@ def group_mul_info():
     s, a, b = C.c_size_t(0), C.c_int(0), C.c_int(0)
     lib().kzgamd_group_mul_info(C.byref(s), C.byref(a), C.byref(b))
     return {"slice_points": s.value, "g1_window_bits": a.value, "g2_window_bits": b.value}
+
+
+def _codec_check(rc, what):
+    if rc not in (0, 1):
+        raise KzgAmdError("%s: %d" % (what, rc))
+    return rc
+
+
+def g1_compress_batch(points, n, config=None) -> bytes:
+    """the n Jacobian BlstP1 of `points` (ctypes array / buffer) as 48 bytes each, compressed on the GPU"""
+    out = C.create_string_buffer(48 * max(n, 1))
+    _codec_check(lib().kzgamd_g1_compress_batch(out, _addr(points) if n else None, n, _cfgp(config)), "kzgamd_g1_compress_batch")
+    return out.raw[:48 * n]
+
+
+def g1_to_affine_batch(points, n, config=None):
+    """the same points as a new (BlstP1Affine * n); the identity is (0, 0)"""
+    out = (BlstP1Affine * max(n, 1))()
+    _codec_check(lib().kzgamd_g1_to_affine_batch(out, _addr(points) if n else None, n, _cfgp(config)), "kzgamd_g1_to_affine_batch")
+    return out
+
+
+def g1_uncompress_batch(data: bytes, check_subgroup=True, config=None):
+    """len(data) / 48 compressed G1 points parsed on the GPU: (BlstP1 * n, status bytes, rc).  status[i]: 0 ok, 1 not a
+    valid encoding, 2 (check_subgroup) outside the subgroup; refused entries are all-zero; rc is 1 when any was refused."""
+    if len(data) % 48:
+        raise KzgAmdError("g1_uncompress_batch: the input is not a whole number of 48-byte points")
+    n = len(data) // 48
+    out = (BlstP1 * max(n, 1))()
+    status = C.create_string_buffer(max(n, 1))
+    rc = _codec_check(lib().kzgamd_g1_uncompress_batch(out, status, bytes(data), n, 1 if check_subgroup else 0, _cfgp(config)),
+                      "kzgamd_g1_uncompress_batch")
+    return out, status.raw[:n], rc
+
+
+def g2_compress_batch(points, n, config=None) -> bytes:
+    """the n Jacobian BlstP2 of `points` as 96 bytes each, compressed on the GPU"""
+    out = C.create_string_buffer(96 * max(n, 1))
+    _codec_check(lib().kzgamd_g2_compress_batch(out, _addr(points) if n else None, n, _cfgp(config)), "kzgamd_g2_compress_batch")
+    return out.raw[:96 * n]
+
+
+def g2_uncompress_batch(data: bytes, check_subgroup=True, config=None):
+    """as g1_uncompress_batch for 96-byte G2 points: (BlstP2 * n, status bytes, rc)"""
+    if len(data) % 96:
+        raise KzgAmdError("g2_uncompress_batch: the input is not a whole number of 96-byte points")
+    n = len(data) // 96
+    out = (BlstP2 * max(n, 1))()
+    status = C.create_string_buffer(max(n, 1))
+    rc = _codec_check(lib().kzgamd_g2_uncompress_batch(out, status, bytes(data), n, 1 if check_subgroup else 0, _cfgp(config)),
+                      "kzgamd_g2_uncompress_batch")
+    return out, status.raw[:n], rc
+
+
+def write_trusted_setup_file(path, g1_monomial, g1_lagrange, g2_monomial, num_g1, num_g2, config=None):
+    """a setup of any size as text in the layout load_trusted_setup_file reads; the points are compressed on the GPU"""
+    f = _fopen(path, b"w")
+    try:
+        rc = lib().kzgamd_write_trusted_setup_file(f, _addr(g1_monomial) if num_g1 else None, _addr(g1_lagrange) if num_g1 else None,
+                                                   _addr(g2_monomial) if num_g2 else None, num_g1, num_g2, _cfgp(config))
+    finally:
+        _libc.fclose(f)
+    if rc != 0:
+        raise KzgAmdError("kzgamd_write_trusted_setup_file: %d" % rc)
+
+
+def read_trusted_setup_file(path, config=None, capacity=None):
+    """(g1_monomial, g1_lagrange, g2_monomial, num_g1, num_g2, rc) of a setup file of any size, parsed on the GPU with
+    the subgroup test: rc 0 ok, 1 malformed text, 2 `capacity` = (g1, g2) too small, 3 a point was refused (all-zero).
+    capacity None: the counts are read first and the arrays sized by them."""
+    def call(mono, lag, g2, cap):
+        n1, n2 = C.c_size_t(cap[0]), C.c_size_t(cap[1])
+        f = _fopen(path)
+        try:
+            rc = lib().kzgamd_read_trusted_setup_file(f, mono, lag, g2, C.byref(n1), C.byref(n2), _cfgp(config))
+        finally:
+            _libc.fclose(f)
+        if rc < 0:
+            raise KzgAmdError("kzgamd_read_trusted_setup_file: %d" % rc)
+        return n1.value, n2.value, rc
+
+    if capacity is None:
+        n1, n2, rc = call(None, None, None, (0, 0))
+        if rc != 0:
+            return None, None, None, n1, n2, rc
+        capacity = (n1, n2)
+    mono, lag, g2 = (BlstP1 * max(capacity[0], 1))(), (BlstP1 * max(capacity[0], 1))(), (BlstP2 * max(capacity[1], 1))()
+    n1, n2, rc = call(mono, lag, g2, capacity)
+    return mono, lag, g2, n1, n2, rc
+
+
+def p2_in_g2(p) -> bool:
+    """the subgroup test of one BlstP2 on the host (psi(P) == [x]P)"""
+    return lib().kzgamd_p2_in_g2(C.byref(p)) == 1
+
+
+def codec_info() -> int:
+    """the points one slice of the batched codec calls takes"""
+    out = C.c_size_t(0)
+    lib().kzgamd_codec_info(C.byref(out))
+    return out.value
 
 
 def compute_challenge(blob: bytes, commitment_p1) -> BlstFr:

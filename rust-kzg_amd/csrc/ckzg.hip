@@ -823,6 +823,20 @@ void decode_check_enqueue(AffPt* d_pts, int* d_stat, const unsigned char* d_byte
         if (decoded) (void)hipEventRecord(decoded, st);
     }
 }
+// the same choice of form for the batched codec calls (codec.hip), which may ask for the decode alone
+void decode_enqueue(AffPt* d_pts, int* d_stat, const unsigned char* d_bytes, size_t np, hipStream_t st, bool check) {
+    if (check) {
+        decode_check_enqueue(d_pts, d_stat, d_bytes, np, st, true, nullptr);
+    } else if (np <= WIDE_CHECK_MAX) {
+        hipLaunchKernelGGL(k_decode_g1_wide, dim3((unsigned)((np + 3) / 4)), dim3(64), 0, st, d_pts, d_stat, d_bytes, np);
+    } else {
+        hipLaunchKernelGGL(k_decode_check_g1<false>, dim3((unsigned)((np + 63) / 64)), dim3(64), 0, st, d_pts, d_stat, d_bytes, np);
+    }
+}
+// decoded slots -> blst_p1 (Z = one, infinity all-zero); a slot whose status is not 0 holds nothing and gives nothing defined
+void affpt_to_blst_p1_enqueue(void* d_p1, const AffPt* d_pts, size_t np, hipStream_t st) {
+    hipLaunchKernelGGL(k_affpt_to_blst_p1, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, st, (ff::Fp*)d_p1, d_pts, np);
+}
 }  // namespace ckz
 namespace {
 
@@ -882,37 +896,8 @@ KzgAmdSettings* make_lane(KzgAmdSettings* parent) {
 namespace {
 
 // ---- trusted setup text (kzg/src/eip_4844.rs:151-228) ----
-bool is_ws(unsigned char c) { return c == ' ' || c == '\t' || c == '\n' || c == '\r' || c == '\v' || c == '\f'; }
-int hexval(unsigned char c) {
-    if (c >= '0' && c <= '9') return c - '0';
-    if (c >= 'a' && c <= 'f') return c - 'a' + 10;
-    if (c >= 'A' && c <= 'F') return c - 'A' + 10;
-    return -1;
-}
-bool scan_number(const std::string& s, size_t& off, size_t& out) {
-    while (off < s.size() && is_ws((unsigned char)s[off])) ++off;
-    if (off >= s.size()) return false;
-    size_t start = off;
-    while (off < s.size() && s[off] >= '0' && s[off] <= '9') ++off;
-    if (off >= s.size() || off == start || off - start > 18) return false;
-    out = 0;
-    for (size_t i = start; i < off; ++i) out = out * 10 + (size_t)(s[i] - '0');
-    return true;
-}
-bool scan_hex_byte(const std::string& s, size_t& off, uint8_t& out) {
-    while (off < s.size() && is_ws((unsigned char)s[off])) ++off;
-    if (off >= s.size()) return false;
-    int hi = hexval((unsigned char)s[off]);
-    if (hi < 0) return false;
-    if (off + 1 < s.size() && hexval((unsigned char)s[off + 1]) >= 0) {
-        out = (uint8_t)(hi * 16 + hexval((unsigned char)s[off + 1]));
-        off += 2;
-    } else {
-        out = (uint8_t)hi;
-        off += 1;
-    }
-    return true;
-}
+using ckz::scan_hex_byte;
+using ckz::scan_number;
 void parse_setup_text(const std::string& text, std::vector<uint8_t>& g1_mono, std::vector<uint8_t>& g1_lag,
                       std::vector<uint8_t>& g2_mono) {
     size_t off = 0, n1 = 0, n2 = 0;

@@ -587,12 +587,48 @@ struct KzgAmdSettings {
 };
 
 namespace ckz {
+// ---- the scanners of the trusted-setup text (kzg/src/eip_4844.rs:151-228), for ckzg.hip and codec.hip
+inline bool is_ws(unsigned char c) { return c == ' ' || c == '\t' || c == '\n' || c == '\r' || c == '\v' || c == '\f'; }
+inline int hexval(unsigned char c) {
+    if (c >= '0' && c <= '9') return c - '0';
+    if (c >= 'a' && c <= 'f') return c - 'a' + 10;
+    if (c >= 'A' && c <= 'F') return c - 'A' + 10;
+    return -1;
+}
+inline bool scan_number(const std::string& s, size_t& off, size_t& out) {
+    while (off < s.size() && is_ws((unsigned char)s[off])) ++off;
+    if (off >= s.size()) return false;
+    size_t start = off;
+    while (off < s.size() && s[off] >= '0' && s[off] <= '9') ++off;
+    if (off >= s.size() || off == start || off - start > 18) return false;
+    out = 0;
+    for (size_t i = start; i < off; ++i) out = out * 10 + (size_t)(s[i] - '0');
+    return true;
+}
+inline bool scan_hex_byte(const std::string& s, size_t& off, uint8_t& out) {
+    while (off < s.size() && is_ws((unsigned char)s[off])) ++off;
+    if (off >= s.size()) return false;
+    int hi = hexval((unsigned char)s[off]);
+    if (hi < 0) return false;
+    if (off + 1 < s.size() && hexval((unsigned char)s[off + 1]) >= 0) {
+        out = (uint8_t)(hi * 16 + hexval((unsigned char)s[off + 1]));
+        off += 2;
+    } else {
+        out = (uint8_t)hi;
+        off += 1;
+    }
+    return true;
+}
 // ---- defined in ckzg.hip
 KzgAmdSettings* lookup(const CKZGSettings* s);
 KzgAmdSettings* make_lane(KzgAmdSettings* parent);
 // decode + membership test of np compressed points (k_decode_g1_wide / k_affpts_in_g1_wide or the single-lane kernel)
 void decode_check_enqueue(g1::AffPt* d_pts, int* d_stat, const unsigned char* d_bytes, size_t np, hipStream_t st, bool wide,
                           hipEvent_t decoded = nullptr);
+// for codec.hip: the decode with (`check`) or without the membership test, in the form the count picks (wide up to
+// WIDE_CHECK_MAX points, the single-lane kernel above), and k_affpt_to_blst_p1 over the decoded slots
+void decode_enqueue(g1::AffPt* d_pts, int* d_stat, const unsigned char* d_bytes, size_t np, hipStream_t st, bool check);
+void affpt_to_blst_p1_enqueue(void* d_p1, const g1::AffPt* d_pts, size_t np, hipStream_t st);
 void compress_on_host(uint8_t* out48, const blst_p1* jac, size_t n);
 bool host_blob_valid(const uint8_t* blob);
 void prove_batch(KZGProof* proofs, Bytes32* ys, const Blob* blobs, const Bytes32* zs, const Bytes48* commitments, size_t n,

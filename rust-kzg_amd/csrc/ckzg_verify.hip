@@ -341,6 +341,12 @@ extern "C" void kzgamd_p2_compress(uint8_t out[96], const blst_p2* in) {
     memcpy(&p, in, sizeof p);
     kzgamd::pairing::g2_compress(out, p);
 }
+extern "C" int kzgamd_p2_in_g2(const blst_p2* in) {
+    if (!in) return -1;
+    kzgamd::pairing::G2Jac p;
+    memcpy(&p, in, sizeof p);
+    return kzgamd::pairing::g2_in_g2(p) ? 1 : 0;
+}
 extern "C" void kzgamd_p2_generator(blst_p2* out) {
     const kzgamd::pairing::G2Jac g = kzgamd::pairing::g2_generator();
     memcpy(out, &g, sizeof g);

@@ -9,6 +9,7 @@
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
+#include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
@@ -135,6 +136,29 @@ inline bool take_key(const char* str, const char* key, long long lo, long long h
         p = e;
     }
     return true;
+}
+
+// What a KzgAmdConfig means to a handle-less call that works through slices of workspace (groupmul.hip: mul_slice;
+// codec.hip: codec_slice): the device, and the slice from the ONE key `key` of that call (a power of two, at least
+// `slice_min`); anything else in the string fails the call.  0, or the call's return code (-2, said on stderr).
+inline int read_slice_config(const KzgAmdConfig* cfg, const char* who, const char* key, size_t slice_default, size_t slice_min,
+                             int* device, size_t* slice) {
+    *device = -1;
+    *slice = slice_default;
+    if (!cfg) return 0;
+    if (cfg->struct_size < offsetof(KzgAmdConfig, tuning) + sizeof(cfg->tuning)) {
+        fprintf(stderr, "kzg_mi355x: %s: KzgAmdConfig.struct_size is not that of any version of the struct\n", who);
+        return -2;
+    }
+    *device = cfg->device;
+    long long v = (long long)*slice;
+    std::string rest;
+    if (cfg->tuning && (!take_key(cfg->tuning, key, (long long)slice_min, 1ll << 30, &v, &rest) || !rest.empty() || (v & (v - 1)))) {
+        fprintf(stderr, "kzg_mi355x: %s: tuning: the one key of this call is '%s' (a power of two, at least %zu)\n", who, key, slice_min);
+        return -2;
+    }
+    *slice = (size_t)v;
+    return 0;
 }
 
 struct Options {

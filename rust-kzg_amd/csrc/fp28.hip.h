@@ -381,6 +381,11 @@ FF_HD bool is_zero_mod_p(const Fe& a_in) {
     }
     c += (u64)k * pl(L - 1);
     diff |= (u32)c ^ a.v[L - 1];
+#if defined(KZGAMD_FORCE_EXACT_TESTS)
+    // without the filter k goes up to 2^28 and the top limb of k*p beyond 32 bits, which the top limb of a never does:
+    // M*p - 2^396 (the Montgomery form of a small negative integer, plus a few p) would compare equal to M*p
+    diff |= (u32)(c >> 32);
+#endif
     return diff == 0;
 }
 

@@ -174,6 +174,51 @@ FF_HD void compress(unsigned char out[48], const g1::Xyzz& p) {
     compress_with_inverse(out, p, zi);
 }
 
+// One lane's share of a batched blst_p1_compress / blst_p1_to_affine (codec.hip): m <= CH Jacobian points in the blst_p1
+// layout (three Fp each, Montgomery 2^384, canonical; the identity is Z all-zero, whatever X and Y hold) with ONE
+// inversion, by Montgomery's trick over the non-zero Z of the chunk, as host_p1_compress_batch / host_p1_to_affine_batch
+// do it on the host.  AFFINE: out is blst_p1_affine[m] (two Fp per point, the identity as (0, 0)); otherwise 48 bytes per
+// point.  A chunk of 0 points, of 1 point and of identities only is handled (the inversion then runs on one).
+// Every operand is a product's output (< 2p): the running product, the prefixes, z^-1, x and y.  The loops are kept
+// rolled: the prefixes are indexed by the loop counter (scratch on the device) and the body is eight products long.
+template <int CH, bool AFFINE>
+FF_HD void jac_chunk_out(void* out, const ff::Fp* jac, int m) {
+    Fe pre[CH];
+    Fe run = fp28::one();
+#pragma unroll 1
+    for (int i = 0; i < m; ++i) {
+        pre[i] = run;
+        if (!jac[3 * i + 2].is_zero()) run = fp28::mul(run, fp28::from_blst(jac[3 * i + 2]));
+    }
+    Fe inv = m > 0 ? inverse(run) : run;
+#pragma unroll 1
+    for (int i = m - 1; i >= 0; --i) {
+        const bool inf = jac[3 * i + 2].is_zero();
+        Fe x = fp28::zero(), y = fp28::zero();
+        if (!inf) {
+            const Fe zi = fp28::mul(inv, pre[i]), zi2 = fp28::sqr(zi);
+            inv = fp28::mul(inv, fp28::from_blst(jac[3 * i + 2]));
+            x = fp28::mul(fp28::from_blst(jac[3 * i]), zi2);
+            y = fp28::mul(fp28::from_blst(jac[3 * i + 1]), fp28::mul(zi2, zi));
+        }
+        if (AFFINE) {
+            ff::Fp* o = (ff::Fp*)out + 2 * i;
+            o[0] = inf ? ff::Fp::zero() : fp28::to_blst(x);
+            o[1] = inf ? ff::Fp::zero() : fp28::to_blst(y);
+        } else {
+            unsigned char* o = (unsigned char*)out + 48 * i;
+            if (inf) {
+                for (int k = 0; k < 48; ++k) o[k] = 0;
+                o[0] = 0xc0;
+            } else {
+                sat_to_be48(o, to_plain(x));
+                o[0] |= 0x80;
+                if (is_lex_largest(to_plain(y))) o[0] |= 0x20;
+            }
+        }
+    }
+}
+
 // the r-torsion test of a decoded point: phi(P) == -[x^2]P, phi(x,y) = (beta*x, y), x the BLS parameter (the in-tree
 // statement of the same test: zkcrypto/bls12_381/src/g1.rs:401-435).  Two 64-bit scalar multiplications instead of one
 // by the 255-bit group order.

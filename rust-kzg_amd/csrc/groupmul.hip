@@ -197,18 +197,7 @@ __global__ void __launch_bounds__(64) k_g2_mul(ff::Fp* __restrict__ out, const F
 // ---------------------------------------------------------------- host side
 namespace hp = kzgamd::pairing;
 
-struct Stream {
-    hipStream_t st = nullptr;
-    Stream() { DEV_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking)); }
-    ~Stream() {
-        if (st) {
-            (void)hipStreamSynchronize(st);
-            (void)hipStreamDestroy(st);
-        }
-    }
-    Stream(const Stream&) = delete;
-    Stream& operator=(const Stream&) = delete;
-};
+using Stream = kzgamd::CallStream;
 
 g1::AffPt g1_affpt(const ff::Fp& x, const ff::Fp& y) {  // canonical blst affine coordinates -> table-point form
     g1::AffPt a;
@@ -291,24 +280,7 @@ const g2::AffPt* g2_generator_table(int device, hipStream_t st) {
 
 // what a KzgAmdConfig means to these calls: 0, or the call's return code
 int read_config(const KzgAmdConfig* cfg, const char* who, int* device, size_t* slice) {
-    *device = -1;
-    *slice = SLICE_DEFAULT;
-    if (!cfg) return 0;
-    if (cfg->struct_size < offsetof(KzgAmdConfig, tuning) + sizeof(cfg->tuning)) {
-        fprintf(stderr, "kzg_mi355x: %s: KzgAmdConfig.struct_size is not that of any version of the struct\n", who);
-        return -2;
-    }
-    *device = cfg->device;
-    // mul_slice is the one key of these calls: anything else in the string fails them
-    long long v = (long long)*slice;
-    std::string rest;
-    if (cfg->tuning &&
-        (!kzgamd::take_key(cfg->tuning, "mul_slice", (long long)SLICE_MIN, 1ll << 30, &v, &rest) || !rest.empty() || (v & (v - 1)))) {
-        fprintf(stderr, "kzg_mi355x: %s: tuning: the one key of this call is 'mul_slice' (a power of two, at least 64)\n", who);
-        return -2;
-    }
-    *slice = (size_t)v;
-    return 0;
+    return kzgamd::read_slice_config(cfg, who, "mul_slice", SLICE_DEFAULT, SLICE_MIN, device, slice);
 }
 
 int current_or(int device, hipError_t* e) {

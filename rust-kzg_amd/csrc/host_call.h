@@ -59,6 +59,20 @@ struct ScopedBuf {
     ScopedBuf& operator=(const ScopedBuf&) = delete;
 };
 
+// the stream of one handle-less call: created with the call, drained and destroyed when it ends, whichever way
+struct CallStream {
+    hipStream_t st = nullptr;
+    CallStream() { DEV_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking)); }
+    ~CallStream() {
+        if (st) {
+            (void)hipStreamSynchronize(st);
+            (void)hipStreamDestroy(st);
+        }
+    }
+    CallStream(const CallStream&) = delete;
+    CallStream& operator=(const CallStream&) = delete;
+};
+
 inline unsigned blocks(size_t total, unsigned per = 256) { return (unsigned)((total + per - 1) / per); }
 inline size_t next_pow2(size_t v) {
     size_t n = 1;

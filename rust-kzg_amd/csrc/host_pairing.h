@@ -423,6 +423,31 @@ inline Fp12 f12_frobenius(const Fp12& a) {
     r.c1 = {f2_mul(f2_conj(a.c1.c0), k.g[1]), f2_mul(f2_conj(a.c1.c1), k.g[3]), f2_mul(f2_conj(a.c1.c2), k.g[5])};  // w, vw, v^2 w
     return r;
 }
+// ---------------------------------------------------------------- membership in G2
+// The endomorphism psi = twist o Frobenius o untwist of E'(Fp2): with w^6 = xi the untwist divides x by w^2 and y by w^3,
+// Frobenius conjugates the coordinates and sends w^k to w^(k p), and twisting back leaves
+//     psi(x, y) = (conj(x) / xi^((p-1)/3), conj(y) / xi^((p-1)/2)):
+// the inverses of two of the Frobenius constants above.  On G2 it is multiplication by p = x (mod r).
+inline G2Affine g2_psi(const G2Affine& a) {
+    if (a.inf) return a;
+    static const Fp2 cx = f2_inv(frobenius_constants().g[2]), cy = f2_inv(frobenius_constants().g[3]);
+    return {f2_mul(f2_conj(a.x), cx), f2_mul(f2_conj(a.y), cy), false};
+}
+// P in G2, the test: psi(P) == [x]P = -[|x|]P (sufficient on BLS12 curves: M. Scott, "A note on group membership tests
+// for G1, G2 and GT on BLS pairing-friendly curves", ePrint 2021/1130, section 4).  Infinity is a member.
+inline bool g2_in_g2(const G2Jac& p) {
+    if (g2_is_inf(p)) return true;
+    const uint32_t k[8] = {(uint32_t)BLS_X_ABS, (uint32_t)(BLS_X_ABS >> 32), 0, 0, 0, 0, 0, 0};
+    const G2Affine s = g2_psi(g2_to_affine(p));
+    return g2_equal({s.x, s.y, f2_one()}, g2_neg(g2_mul(p, k)));
+}
+// ... and the definition: [r]P is the identity
+inline bool g2_in_g2_by_order(const G2Jac& p) {
+    uint32_t r[8];
+    for (int i = 0; i < 8; ++i) r[i] = ff::FrParams::p(i);
+    return g2_is_inf(g2_mul(p, r));
+}
+
 // conj(f^|x|) = f^x for the (negative) BLS parameter, f in the cyclotomic subgroup (where inversion = conjugation)
 inline Fp12 f12_exp_x(const Fp12& f) {
     const uint64_t X = 0xd201000000010000ull;

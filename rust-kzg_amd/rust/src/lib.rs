@@ -115,6 +115,23 @@ extern "C" {
                                      g2_monomial: *mut blst_p2, num_g1: usize, num_g2: usize, secret: *const u8,
                                      cfg: *const KzgAmdConfig) -> c_int;
     fn kzgamd_group_mul_info(slice_points: *mut usize, g1_window_bits: *mut c_int, g2_window_bits: *mut c_int) -> c_int;
+
+    fn kzgamd_g1_compress_batch(out48: *mut u8, points: *const blst_p1, n: usize, cfg: *const KzgAmdConfig) -> c_int;
+    fn kzgamd_g1_to_affine_batch(out: *mut blst_p1_affine, points: *const blst_p1, n: usize, cfg: *const KzgAmdConfig) -> c_int;
+    fn kzgamd_g1_uncompress_batch(out: *mut blst_p1, status: *mut u8, in48: *const u8, n: usize, check_subgroup: c_int,
+                                  cfg: *const KzgAmdConfig) -> c_int;
+    fn kzgamd_g2_compress_batch(out96: *mut u8, points: *const blst_p2, n: usize, cfg: *const KzgAmdConfig) -> c_int;
+    fn kzgamd_g2_uncompress_batch(out: *mut blst_p2, status: *mut u8, in96: *const u8, n: usize, check_subgroup: c_int,
+                                  cfg: *const KzgAmdConfig) -> c_int;
+    fn kzgamd_p2_in_g2(p: *const blst_p2) -> c_int;
+    fn kzgamd_codec_info(slice_points: *mut usize) -> c_int;
+    /// `out` / `input` are C `FILE *` streams (e.g. from `libc::fopen` / `libc::fdopen`).
+    pub fn kzgamd_write_trusted_setup_file(out: *mut c_void, g1_monomial: *const blst_p1, g1_lagrange: *const blst_p1,
+                                           g2_monomial: *const blst_p2, num_g1: usize, num_g2: usize,
+                                           cfg: *const KzgAmdConfig) -> c_int;
+    pub fn kzgamd_read_trusted_setup_file(input: *mut c_void, g1_monomial: *mut blst_p1, g1_lagrange: *mut blst_p1,
+                                          g2_monomial: *mut blst_p2, num_g1: *mut usize, num_g2: *mut usize,
+                                          cfg: *const KzgAmdConfig) -> c_int;
 }
 
 fn group_mul_result(rc: c_int, what: &str) -> Result<(), String> {
@@ -148,6 +165,68 @@ pub fn group_mul_info() -> (usize, i32, i32) {
     let (mut s, mut a, mut b) = (0usize, 0 as c_int, 0 as c_int);
     unsafe { kzgamd_group_mul_info(&mut s, &mut a, &mut b) };
     (s, a as i32, b as i32)
+}
+
+fn codec_result(rc: c_int, what: &str) -> Result<bool, String> {
+    match rc {
+        0 => Ok(true),
+        1 => Ok(false),
+        e => Err(format!("{what}: {e}")),
+    }
+}
+
+/// `G1::to_bytes` for many Jacobian points on the GPU: 48 bytes each.
+pub fn g1_compress_batch(points: &[blst_p1]) -> Result<Vec<u8>, String> {
+    let mut out = vec![0u8; 48 * points.len()];
+    let rc = unsafe { kzgamd_g1_compress_batch(out.as_mut_ptr(), points.as_ptr(), points.len(), core::ptr::null()) };
+    codec_result(rc, "kzgamd_g1_compress_batch").map(|_| out)
+}
+
+/// `G1Affine::into_affines` on the GPU; the identity is (0, 0).
+pub fn g1_to_affine_batch(points: &[blst_p1]) -> Result<Vec<blst_p1_affine>, String> {
+    let mut out = vec![blst_p1_affine::default(); points.len()];
+    let rc = unsafe { kzgamd_g1_to_affine_batch(out.as_mut_ptr(), points.as_ptr(), points.len(), core::ptr::null()) };
+    codec_result(rc, "kzgamd_g1_to_affine_batch").map(|_| out)
+}
+
+/// `G1::from_bytes` (and `is_valid`, with `check_subgroup`) for `bytes.len() / 48` points on the GPU: the points, a
+/// status per point (0 ok, 1 no valid encoding, 2 outside the subgroup; such entries are all-zero) and "all accepted".
+pub fn g1_uncompress_batch(bytes: &[u8], check_subgroup: bool) -> Result<(Vec<blst_p1>, Vec<u8>, bool), String> {
+    let n = bytes.len() / 48;
+    let (mut out, mut status) = (vec![blst_p1::default(); n], vec![0u8; n]);
+    let rc = unsafe {
+        kzgamd_g1_uncompress_batch(out.as_mut_ptr(), status.as_mut_ptr(), bytes.as_ptr(), n, check_subgroup as c_int, core::ptr::null())
+    };
+    codec_result(rc, "kzgamd_g1_uncompress_batch").map(|ok| (out, status, ok))
+}
+
+/// `G2::to_bytes` for many Jacobian points on the GPU: 96 bytes each.
+pub fn g2_compress_batch(points: &[blst_p2]) -> Result<Vec<u8>, String> {
+    let mut out = vec![0u8; 96 * points.len()];
+    let rc = unsafe { kzgamd_g2_compress_batch(out.as_mut_ptr(), points.as_ptr(), points.len(), core::ptr::null()) };
+    codec_result(rc, "kzgamd_g2_compress_batch").map(|_| out)
+}
+
+/// `G2::from_bytes` for `bytes.len() / 96` points on the GPU, as `g1_uncompress_batch`.
+pub fn g2_uncompress_batch(bytes: &[u8], check_subgroup: bool) -> Result<(Vec<blst_p2>, Vec<u8>, bool), String> {
+    let n = bytes.len() / 96;
+    let (mut out, mut status) = (vec![blst_p2::default(); n], vec![0u8; n]);
+    let rc = unsafe {
+        kzgamd_g2_uncompress_batch(out.as_mut_ptr(), status.as_mut_ptr(), bytes.as_ptr(), n, check_subgroup as c_int, core::ptr::null())
+    };
+    codec_result(rc, "kzgamd_g2_uncompress_batch").map(|ok| (out, status, ok))
+}
+
+/// The subgroup test of one G2 point on the host.
+pub fn p2_in_g2(p: &blst_p2) -> bool {
+    unsafe { kzgamd_p2_in_g2(p) == 1 }
+}
+
+/// Points per slice of workspace of the batched codec calls.
+pub fn codec_info() -> usize {
+    let mut s = 0usize;
+    unsafe { kzgamd_codec_info(&mut s) };
+    s
 }
 
 fn check(err: RustError, what: &str) -> Result<(), String> {
