@@ -608,6 +608,55 @@ int kzgamd_write_trusted_setup_file(FILE *out, const blst_p1 *g1_monomial, const
 int kzgamd_read_trusted_setup_file(FILE *in, blst_p1 *g1_monomial, blst_p1 *g1_lagrange, blst_p2 *g2_monomial,
                                    size_t *num_g1, size_t *num_g2, const KzgAmdConfig *cfg);
 
+/* G2 linear combinations ON THE GPU, and the verification of a trusted setup made of them.  Handle-less, as the calls
+ * above: the calling thread's current device (cfg->device, when cfg is given and names one), host buffers, thread-safe,
+ * a stream per call.
+ *
+ * kzgamd_g2_lincomb: *out = sum_i scalars[i] * points[i], i < n.  Scalars are Montgomery blst_fr.  Points are Jacobian
+ * with canonical coordinates and any Z; Z == 0 is the identity.  The output is Jacobian, canonical, all-zero for the
+ * identity.  n == 0 gives the identity, and points and scalars are not looked at.  The points are the caller's
+ * responsibility, like every blst_p2 this library accepts: for points outside the subgroup the result is still the sum
+ * of the curve's group law, as in kzgamd_g2_mul_batch.  One lane per point walks the 256 bits of its scalar
+ * (double-and-add); the terms are summed pairwise on the device.
+ * Return codes:  0 ok;  -1 a needed pointer is NULL;  -2 or -(100 + hipError_t) device errors (-2 also for a malformed
+ * cfg).  cfg may be NULL.  Its tuning string takes ONE key, of the calls of this block alone and not listed by
+ * kzgamd_tuning_keys: lincomb_slice=<points per slice of workspace: a power of two, at least 64>; any other key fails
+ * the call.  Counts above the slice run slice by slice through one workspace, and the slice sums are added.
+ * kzgamd_g2_lincomb_info reports the default slice (may be NULL; returns 0).
+ *
+ * kzgamd_verify_trusted_setup: is (M, L, Q) = (g1_monomial, g1_lagrange, g2_monomial) a trusted setup: the powers of
+ * ONE secret on both sides, from the two generators, and L the inverse transform of M (natural order, as
+ * kzgamd_generate_trusted_setup returns it and a setup file stores it)?  L may be NULL: that check is not made, and
+ * `ntt` is not needed.  With L, `ntt` is an NTT handle at least num_g1 wide, and the call runs on its device.
+ * PRECONDITION: every point is in its prime-order subgroup.  Neither this call nor any other tests a blst_p1 / blst_p2
+ * array handed over; kzgamd_read_trusted_setup_file and the uncompress_batch calls with check_subgroup test points as
+ * they are parsed (the file form below goes through the former).
+ * The challenge: r = hash_to_bls_field(seed) (the 32 bytes as a big-endian integer mod r, the rule of `secret` in
+ * kzgamd_generate_trusted_setup); r == 0 is replaced by 1.  With seed == NULL the 32 bytes are
+ *     SHA-256( "KZGAMD_VERIFY_SETUP_V1" (22 bytes, no terminator) | num_g1 as 8 bytes big-endian | num_g2 as 8 bytes
+ *              big-endian | one byte: 1 with L, 0 without | M compressed, 48 bytes a point | L compressed, 48 bytes a
+ *              point (with L only) | Q compressed, 96 bytes a point ),
+ * so a setup cannot be chosen after its challenge.  A caller's seed must be one the maker of the setup could not know.
+ * The checks, each a bit of *failed (failed may be NULL); all of them run, not only the first to fail:
+ *     1   M[0] is the G1 generator and Q[0] is the G2 generator (as points, any Z)
+ *     2   G1 powers:  e(B, Q[0]) == e(A, Q[1])  with A = sum_{i < num_g1 - 1} r^i M[i],  B = sum_{i < num_g1 - 1} r^i M[i + 1]
+ *     4   G2 powers:  e(M[1], C) == e(M[0], D)  with C = sum_{j < num_g2 - 1} r^j Q[j],  D = sum_{j < num_g2 - 1} r^j Q[j + 1]
+ *     8   Lagrange form:  sum_i f[i] L[i] == sum_k r^k M[k]  with f = ntt_fr(r^0 ... r^(num_g1 - 1)) (forward)
+ * What passes is a setup except with probability at most (2 num_g1 + num_g2) / |Fr| over r.
+ * Return codes:  0 every requested check passed;  1 at least one failed, *failed says which;  2 num_g1 < 2 or
+ * num_g2 < 2;  3 L was given but num_g1 is not a power of two, ntt is NULL, or num_g1 exceeds the handle's width;
+ * -1 a needed pointer is NULL;  -2 or -(100 + hipError_t) device errors or a malformed cfg (lincomb_slice, as above).
+ *
+ * kzgamd_verify_trusted_setup_file reads `in` with kzgamd_read_trusted_setup_file (subgroup test on, all three arrays)
+ * and verifies what it read, L included.  That call's codes 1, 2, 3 come back as 11, 12, 13 (13: a point was refused,
+ * which also covers a point outside its subgroup); otherwise the codes above. */
+int kzgamd_g2_lincomb(blst_p2 *out, const blst_p2 *points, const blst_fr *scalars, size_t n, const KzgAmdConfig *cfg);
+int kzgamd_g2_lincomb_info(size_t *slice_points);
+int kzgamd_verify_trusted_setup(void *ntt, unsigned *failed, const blst_p1 *g1_monomial, const blst_p1 *g1_lagrange,
+                                const blst_p2 *g2_monomial, size_t num_g1, size_t num_g2, const uint8_t seed[32],
+                                const KzgAmdConfig *cfg);
+int kzgamd_verify_trusted_setup_file(void *ntt, unsigned *failed, FILE *in, const uint8_t seed[32], const KzgAmdConfig *cfg);
+
 typedef struct { uint8_t bytes[2048]; } Cell;
 C_KZG_RET compute_cells_and_kzg_proofs(Cell *cells, KZGProof *proofs, const Blob *blob, const CKZGSettings *s);
 C_KZG_RET kzgamd_compute_cells_and_kzg_proofs_batch(Cell *cells, KZGProof *proofs, const Blob *blobs, size_t n,

@@ -91,6 +91,7 @@ EXPORTS = [
     "kzgamd_g1_compress_batch", "kzgamd_g1_to_affine_batch", "kzgamd_g1_uncompress_batch", "kzgamd_g2_compress_batch",
     "kzgamd_g2_uncompress_batch", "kzgamd_p2_in_g2", "kzgamd_codec_info",
     "kzgamd_write_trusted_setup_file", "kzgamd_read_trusted_setup_file",
+    "kzgamd_g2_lincomb", "kzgamd_g2_lincomb_info", "kzgamd_verify_trusted_setup", "kzgamd_verify_trusted_setup_file",
     "kzgamd_load_trusted_setup_file_multi", "kzgamd_free_trusted_setup_multi", "kzgamd_blob_to_kzg_commitment_batch_multi",
     "kzgamd_compute_blob_kzg_proof_batch_multi", "kzgamd_compute_cells_and_kzg_proofs_batch_multi",
     "kzgamd_verify_blob_kzg_proof_batch_multi", "kzgamd_mult_pippenger_prepared_multi", "kzgamd_shard_range",
@@ -393,6 +394,14 @@ def lib():
     L.kzgamd_write_trusted_setup_file.argtypes = [vp, vp, vp, vp, C.c_size_t, C.c_size_t, vp]
     L.kzgamd_read_trusted_setup_file.restype = C.c_int
     L.kzgamd_read_trusted_setup_file.argtypes = [vp, vp, vp, vp, vp, vp, vp]
+    L.kzgamd_g2_lincomb.restype = C.c_int
+    L.kzgamd_g2_lincomb.argtypes = [vp, vp, vp, C.c_size_t, vp]
+    L.kzgamd_g2_lincomb_info.restype = C.c_int
+    L.kzgamd_g2_lincomb_info.argtypes = [vp]
+    L.kzgamd_verify_trusted_setup.restype = C.c_int
+    L.kzgamd_verify_trusted_setup.argtypes = [vp, vp, vp, vp, vp, C.c_size_t, C.c_size_t, vp, vp]
+    L.kzgamd_verify_trusted_setup_file.restype = C.c_int
+    L.kzgamd_verify_trusted_setup_file.argtypes = [vp, vp, vp, vp, vp]
     L.kzgamd_load_trusted_setup_file_multi.restype = C.c_int
     L.kzgamd_load_trusted_setup_file_multi.argtypes = [vp, vp, sz, vp]
     L.kzgamd_free_trusted_setup_multi.restype = None
@@ -1465,6 +1474,54 @@ def read_trusted_setup_file(path, config=None, capacity=None):
     mono, lag, g2 = (BlstP1 * max(capacity[0], 1))(), (BlstP1 * max(capacity[0], 1))(), (BlstP2 * max(capacity[1], 1))()
     n1, n2, rc = call(mono, lag, g2, capacity)
     return mono, lag, g2, n1, n2, rc
+
+
+def g2_lincomb(points, scalars, n, config=None):
+    """sum_i scalars[i] * points[i] on the GPU: BlstP2[n] (any Z) and Montgomery blst_fr[n]; returns a new BlstP2
+    (all-zero for the identity, which is also what n = 0 gives)"""
+    out = BlstP2()
+    rc = lib().kzgamd_g2_lincomb(C.byref(out), _addr(points) if n else None, _addr(scalars) if n else None, n, _cfgp(config))
+    if rc != 0:
+        raise KzgAmdError("kzgamd_g2_lincomb: %d" % rc)
+    return out
+
+
+def g2_lincomb_info() -> int:
+    """the points one slice of g2_lincomb takes"""
+    out = C.c_size_t(0)
+    lib().kzgamd_g2_lincomb_info(C.byref(out))
+    return out.value
+
+
+def verify_trusted_setup(g1_monomial, g1_lagrange, g2_monomial, num_g1, num_g2, fft_settings=None, seed=None, config=None):
+    """(rc, failed) of kzgamd_verify_trusted_setup: rc 0 the setup passed, 1 it did not and `failed` has the bits of the
+    checks that failed (1 generators, 2 G1 powers, 4 G2 powers, 8 Lagrange form), 2 fewer than two points on a side,
+    3 the Lagrange form cannot be checked (no FFTSettings, not a power of two, too wide).  g1_lagrange None: that check
+    is not made.  seed: 32 bytes the maker of the setup could not know, or None (a hash of the setup itself)."""
+    if seed is not None and len(seed) != 32:
+        raise KzgAmdError("verify_trusted_setup: the seed is 32 bytes")
+    failed = C.c_uint(0)
+    rc = lib().kzgamd_verify_trusted_setup(fft_settings.handle if fft_settings is not None else None, C.byref(failed), _addr(g1_monomial),
+                                           _addr(g1_lagrange) if g1_lagrange is not None else None, _addr(g2_monomial), num_g1, num_g2,
+                                           bytes(seed) if seed is not None else None, _cfgp(config))
+    if rc < 0:
+        raise KzgAmdError("kzgamd_verify_trusted_setup: %d" % rc)
+    return rc, failed.value
+
+
+def verify_trusted_setup_file(path, fft_settings, seed=None, config=None):
+    """(rc, failed) of kzgamd_verify_trusted_setup_file: as verify_trusted_setup, and 11, 12, 13 for what the reader
+    refuses (malformed text, -, a refused point)"""
+    failed = C.c_uint(0)
+    f = _fopen(path)
+    try:
+        rc = lib().kzgamd_verify_trusted_setup_file(fft_settings.handle if fft_settings is not None else None, C.byref(failed), f,
+                                                    bytes(seed) if seed is not None else None, _cfgp(config))
+    finally:
+        _libc.fclose(f)
+    if rc < 0:
+        raise KzgAmdError("kzgamd_verify_trusted_setup_file: %d" % rc)
+    return rc, failed.value
 
 
 def p2_in_g2(p) -> bool:

@@ -113,7 +113,7 @@ inline bool tune_value_allowed(int id, long v) {
 inline bool is_sep(char c) { return c == ';' || c == ',' || c == ' ' || c == '\t' || c == '\n'; }
 
 // A key that belongs to one entry point, not to the table above (pairing_gpu_min of kzgamd_kzg_new, fk20_table of
-// kzgamd_fk20_new, mul_slice of the group multiplications), taken out of a tuning string before Options::parse sees it:
+// kzgamd_fk20_new, mul_slice of the group multiplications, lincomb_slice of setupcheck.hip), taken out of a tuning string before Options::parse sees it:
 // a token "<key>=<integer>" sets *value (the last one wins), every other token is appended to *rest, joined with ';'.
 // false when the key's value is missing, is not wholly an integer or lies outside lo ... hi.
 inline bool take_key(const char* str, const char* key, long long lo, long long hi, long long* value, std::string* rest) {
@@ -139,7 +139,7 @@ inline bool take_key(const char* str, const char* key, long long lo, long long h
 }
 
 // What a KzgAmdConfig means to a handle-less call that works through slices of workspace (groupmul.hip: mul_slice;
-// codec.hip: codec_slice): the device, and the slice from the ONE key `key` of that call (a power of two, at least
+// codec.hip: codec_slice; setupcheck.hip: lincomb_slice): the device, and the slice from the ONE key `key` of that call (a power of two, at least
 // `slice_min`); anything else in the string fails the call.  0, or the call's return code (-2, said on stderr).
 inline int read_slice_config(const KzgAmdConfig* cfg, const char* who, const char* key, size_t slice_default, size_t slice_min,
                              int* device, size_t* slice) {

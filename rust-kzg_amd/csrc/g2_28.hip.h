@@ -1,7 +1,8 @@
 // G2 point arithmetic over fp28::Fe, one value per lane: Fp2 = Fp[u]/(u^2 + 1) and points of the twist
 // E'(Fp2): y^2 = x^3 + 4(1 + u), in the style of g1_28.hip.h.  host_pairing.h is the specification: f2_mul / f2_sqr
-// with the same Karatsuba split, g2_dbl (dbl-2009-l), g2_add with Z2 = 1 (add-2007-bl), g2_to_affine; every routine
-// returns the value the host routine returns (tests/test_g2_lane_cpu.py compares them as canonical residues).
+// with the same Karatsuba split, g2_dbl (dbl-2009-l), g2_add (add-2007-bl) with Z2 = 1 and in full, g2_to_affine; every
+// routine returns the value the host routine returns (tests/test_g2_lane_cpu.py and tests/test_g2_add_cpu.py compare
+// them as canonical residues).
 //
 // Bounds.  An Fp2 value is two fp28 components, each NORMALIZED (limbs 0..12 < 2^28) with a value below a stated
 // multiple of p; "a < K" below means both components of a are normalized with value < K*p.  The rules of fp28.hip.h
@@ -25,9 +26,11 @@
 //   madd(P, Q)     X1, Y1 < 3, Z1 < 10 (or P infinity);      X, Y < 3, Z < 10, or one of the states below
 //                  Q affine: x, y < 3, not infinity
 //   madd_tab(P, e, neg)  P as madd; e a table entry (canonical x, y, or flagged infinite)   as madd; complete
-// so the output of either is an input of either, and a table point (canonical x, y; -Q as neg<2>(y) <= 2) an input of
-// madd.  The rare exact-zero tests sit in madd alone (H == 0, then r == 0), through fp28::is_zero_mod_p, which honours
-// KZGAMD_FORCE_EXACT_TESTS.
+//   add(P, Q)      X, Y < 3, Z < 10 on both sides, or either     X, Y < 2, Z < 10, or infinity; complete
+//                  at infinity
+// so the output of any of dbl, madd and add is an input of any of them, and a table point (canonical x, y; -Q as
+// neg<2>(y) <= 2) an input of madd.  The rare exact-zero tests sit in madd and add alone (H == 0, then r == 0), through
+// fp28::is_zero_mod_p, which honours KZGAMD_FORCE_EXACT_TESTS.
 #pragma once
 #include "fp28.hip.h"
 #include "g1_io.hip.h"
@@ -161,6 +164,41 @@ FF_HD u32 madd(Jac& p, const F2& x2, const F2& y2) {
 // the complete addition: p += (x2, y2) whatever the two points are
 FF_HD void madd_complete(Jac& p, const F2& x2, const F2& y2) {
     if (madd(p, x2, y2) == MADD_DOUBLE) dbl(p);
+}
+
+// p += q, two Jacobian points, complete in both operands (add-2007-bl, the value of pairing::g2_add; P + P is dbl(p)
+// as there, P - P is infinity, an operand at infinity gives the other).  X, Y < 3 and Z < 10 on both sides.
+//   Z1Z1, Z2Z2 < 4; U1 = X1 Z2Z2, U2 = X2 Z1Z1: 3 * 4, < 10; S1 = (Y1 Z2) Z2Z2, S2 = (Y2 Z1) Z1Z1: 3 * 10, then
+//   10 * 4, < 10; U1 and S1 reduced: < 2 (they are subtracted, and multiplied again below);
+//   H = U2 + 4p - U1 < 14, r = S2 + 4p - S1 < 14; both zero-tested (< 2^6);
+//   I = (2H)^2 = 4 H^2 < 16 (H < 15, H^2 < 4); J = H I: 14 * 16, < 10; V = U1 I: 2 * 16, < 10;
+//   (2r)^2 = 4 r^2 < 16; J + 2V < 30 <= 31: X3 = 4r^2 + 32p - J - 2V < 48, reduced: < 2;
+//   (2r)(V + 4p - X3): 28 * 14 <= 630, < 10; 2 S1 J: S1 J is 2 * 10, < 10, doubled < 20 <= 31: Y3 < 42, reduced: < 2;
+//   Z3 = ((Z1 + Z2)^2 - Z1Z1 - Z2Z2) H = ((2 Z1) Z2) H: 20 * 10, < 10, then 10 * 14, < 10.
+// The doubling inside takes X, Y < 15, Z < 21.
+FF_HD void add(Jac& p, const Jac& q) {
+    if (is_inf(q)) return;
+    if (is_inf(p)) {
+        p = q;
+        return;
+    }
+    const F2 Z1Z1 = sqr(p.z), Z2Z2 = sqr(q.z);
+    const F2 U1 = red(mul(p.x, Z2Z2)), U2 = mul(q.x, Z1Z1);
+    const F2 S1 = red(mul(mul(p.y, q.z), Z2Z2)), S2 = mul(mul(q.y, p.z), Z1Z1);
+    const F2 H = sub<4>(U2, U1), r = sub<4>(S2, S1);
+    if (is_zero(H)) {
+        if (is_zero(r)) dbl(p);
+        else set_inf(p);
+        return;
+    }
+    const F2 I = dbl(dbl(sqr(H)));
+    const F2 J = mul(H, I), V = mul(U1, I);
+    const F2 rr4 = dbl(dbl(sqr(r)));
+    const F2 X3 = red(sub<32>(rr4, add(J, dbl(V))));
+    const F2 Y3 = red(sub<32>(mul(dbl(r), sub<4>(V, X3)), dbl(mul(S1, J))));
+    p.z = mul(mul(dbl(p.z), q.z), H);
+    p.x = X3;
+    p.y = Y3;
 }
 
 // One step of a table walk: p += e for neg == 0, p -= e otherwise, e a table entry (canonical x, y, or flagged as

@@ -42,6 +42,7 @@
 #include "host_g1.h"
 #include "host_pairing.h"
 #include "ntt_internal.h"
+#include "setupcheck_internal.h"
 
 using ff::Fr;
 using ff::u32;
@@ -312,6 +313,10 @@ void enqueue_powers(Fr* d_out, const Fr& s, const Fr& c, size_t start, size_t n,
 }
 
 }  // namespace
+
+void kzgamd::fr_powers_enqueue(Fr* d_out, const Fr& s, const Fr& c, size_t start, size_t n, hipStream_t st) {
+    enqueue_powers(d_out, s, c, start, n, st);
+}
 
 extern "C" int kzgamd_group_mul_info(size_t* slice_points, int* g1_window_bits, int* g2_window_bits) {
     if (slice_points) *slice_points = SLICE_DEFAULT;
