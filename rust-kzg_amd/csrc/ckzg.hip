@@ -965,6 +965,7 @@ void load_impl(CKZGSettings* out, const uint8_t* g1_mono, size_t n1m, const uint
     try {
         CK_HIP(placed.err);
         CK_HIP(hipGetDevice(&dev->device));
+        dev->slots.emplace(BYTES_PER_BLOB, KzgAmdSettings::NSLOTS, kzgamd::SlotGrowth::AllAtOnce, kzgamd::PinnedMapped{dev->device});
         CK_HIP(hipStreamCreateWithFlags(&dev->stream, hipStreamNonBlocking));
         // stream2 carries the long one-lane latency chains that nothing waits for until the end of a call (the
         // commitment checks of a proof batch: 1.9 ms): a low-priority stream gets a hardware queue of its own — on a
@@ -1495,91 +1496,45 @@ extern "C" void free_trusted_setup(CKZGSettings* s) {
     free_host_arrays(s);
 }
 
+struct CommitReq : kzgamd::CombineRequest {
+    const Blob* blob;
+    KZGCommitment* out;
+    const unsigned char* staged = nullptr;  // the caller's page-locked copy of the blob (KzgAmdSettings::slots), if it got a slot
+    C_KZG_RET rc = C_KZG_ERROR;
+};
+
 namespace {
-// See KzgAmdSettings::CoalesceQueue.  Req has `bool done`, `C_KZG_RET rc` and `void side_work()`; run(batch) serves
-// every request of the batch (sets rc).  A caller returns as soon as its own request is served; leadership passes to
-// whoever is waiting.  side_work() is the part of a request that needs no GPU (the host-side commitment check of a blob
-// proof): a waiting caller does it before it sleeps, a leader between launching a batch and waiting for it
-// (run's implementation calls it), and whoever has not got to it by the end does it then.
+// One single-blob call through its entry point's queue (KzgAmdSettings::q_*): Req has `C_KZG_RET rc`; run(batch) serves
+// every request of the batch (sets rc).  side_work() is the part of a request that needs no GPU (the host-side
+// commitment check of a blob proof): a waiting caller does it before it sleeps, a leader between launching a batch and
+// waiting for it (run's implementation calls it), and whoever has not got to it by the end does it then.
 template <class Req, class Run>
-C_KZG_RET coalesced_call(KzgAmdSettings::CoalesceQueue& q, Req& me, Run&& run) {
-    const size_t gather_min = q.gather_min;
-    const int gather_us = q.gather_us;
-    // everything that can allocate happens before the request is visible to other callers: nothing below throws
-    std::vector<Req*> batch;
-    std::unique_lock<std::mutex> lk(q.mu, std::defer_lock);
+C_KZG_RET coalesced_call(kzgamd::CombineQueue<Req>& q, Req& me, Run&& run) {
     try {
-        batch.reserve(KzgAmdSettings::LANE_MAX_BLOBS);
-        lk.lock();
-        q.pending.push_back(&me);
-    } catch (...) {
-        return C_KZG_MALLOC;
-    }
-    q.cv.notify_one();  // a leader gathering requests may have enough now
-    bool idled = false;
-    while (!me.done) {
-        if (q.leaders < q.max_leaders && !q.pending.empty()) {
-            ++q.leaders;
-            while (!q.pending.empty() && !me.done) {
-                // under load (other batches in flight) a short wait lets the callers that have just been served come
-                // back with their next request: larger batches, fewer pipeline invocations
-                if (q.leaders > 1 && q.pending.size() < gather_min) {
-                    const auto until = std::chrono::steady_clock::now() + std::chrono::microseconds(gather_us);
-                    while (q.pending.size() < gather_min && !me.done &&
-                           q.cv.wait_until(lk, until) != std::cv_status::timeout) {
-                    }
-                    if (me.done) break;
-                    if (q.pending.empty()) continue;
-                }
-                batch.clear();
-                while (!q.pending.empty() && batch.size() < KzgAmdSettings::LANE_MAX_BLOBS) {
-                    batch.push_back(static_cast<Req*>(q.pending.front()));
-                    q.pending.pop_front();
-                }
-                lk.unlock();
+        kzgamd::combined_call(
+            q, me, [](const Req&, const Req&) { return true; },
+            [&run](const std::vector<Req*>& batch, int) {
                 // a failure of the batch as a whole (a HIP error, no memory) fails every request of it, with the same
                 // mapping as every other entry point (guarded: BadArgs like the reference, or Malloc); run() has waited
                 // for the lane's stream before it throws, so the callers' staged blobs are no longer being read
                 const C_KZG_RET brc = guarded([&] { run(batch); });
                 if (brc != C_KZG_OK)
                     for (Req* r : batch) r->rc = brc;
-                lk.lock();
-                for (Req* r : batch) r->done = true;
-                q.cv.notify_all();
-            }
-            --q.leaders;
-            q.cv.notify_all();
-        } else if (!idled) {
-            idled = true;
-            lk.unlock();
-            me.side_work();
-            lk.lock();
-        } else {
-            q.cv.wait(lk);
-        }
+            });
+    } catch (...) {  // no memory to queue the request: nobody has seen it
+        return C_KZG_MALLOC;
     }
-    lk.unlock();
-    me.side_work();
     return me.rc;
 }
-
-struct CommitReq {
-    const Blob* blob;
-    KZGCommitment* out;
-    const unsigned char* staged = nullptr;  // the caller's page-locked copy of the blob (PinnedSlots), if it got a slot
-    bool done = false;
-    C_KZG_RET rc = C_KZG_ERROR;
-    void side_work() {}
-};
 
 // releases a caller's slot on every way out of its entry point
 struct SlotHold {
     KzgAmdSettings* dev;
     unsigned char* p;
-    SlotHold(KzgAmdSettings* d, const void* blob) : dev(d), p(d->slots.acquire(d->device)) {
+    SlotHold(KzgAmdSettings* d, const void* blob) : dev(d), p(d->slots->acquire()) {
         if (p) memcpy(p, blob, BYTES_PER_BLOB);
     }
-    ~SlotHold() { dev->slots.release(p); }
+    ~SlotHold() { dev->slots->release(p); }
     SlotHold(const SlotHold&) = delete;
     SlotHold& operator=(const SlotHold&) = delete;
 };
@@ -1794,8 +1749,7 @@ extern "C" C_KZG_RET kzgamd_compute_blob_kzg_proof_device(void* d_proofs, void* 
     });
 }
 
-namespace {
-struct ProofReq {
+struct ProofReq : kzgamd::CombineRequest {
     const Blob* blob;
     const Bytes48* commitment;  // compute_blob_kzg_proof
     const Bytes32* z;           // compute_kzg_proof; compute_blob_kzg_proof: the derived challenge (zder)
@@ -1804,7 +1758,6 @@ struct ProofReq {
     const unsigned char* staged = nullptr;  // the caller's page-locked copy of the blob, if it got a slot
     Bytes32 zder;
     bool commitment_ok = true, checked = false;
-    bool done = false;
     C_KZG_RET rc = C_KZG_ERROR;
     // validate_batched_input's half for the commitment (decode + subgroup, ~0.2 ms of one core): never on the GPU's
     // critical path
@@ -1816,6 +1769,7 @@ struct ProofReq {
     }
 };
 
+namespace {
 // A batch of merged single-proof calls on one lane.  Every caller has staged its blob (page-locked slot), validated it
 // and derived its challenge on its own thread; here: gather the blobs on the device, quotient + MSM, results back
 // through the lane's page-locked buffer, one wait.  Status is per request (k_quotient flags a blob or an evaluation
@@ -1883,7 +1837,7 @@ extern "C" C_KZG_RET compute_kzg_proof(KZGProof* proof_out, Bytes32* y_out, cons
     if (!proof_out || !y_out || !blob || !z_bytes) return C_KZG_BADARGS;
     KzgAmdSettings* dev = lookup(s);
     if (!dev) return C_KZG_BADARGS;
-    ProofReq me{blob, nullptr, z_bytes, proof_out, y_out};
+    ProofReq me{{}, blob, nullptr, z_bytes, proof_out, y_out};
     SlotHold slot(dev, blob);
     me.staged = slot.p;
     return coalesced_call(dev->q_proof, me, [&](const std::vector<ProofReq*>& batch) { proof_lane_batch(dev, batch, &me); });
@@ -1924,7 +1878,7 @@ extern "C" C_KZG_RET compute_blob_kzg_proof(KZGProof* out, const Blob* blob, con
     KzgAmdSettings* dev = lookup(s);
     if (!dev) return C_KZG_BADARGS;
     KZGProof proof;  // *out is written only when the call succeeds (an invalid commitment is found after the proof)
-    ProofReq me{blob, commitment_bytes, nullptr, &proof, nullptr};
+    ProofReq me{{}, blob, commitment_bytes, nullptr, &proof, nullptr};
     // this thread's share, in parallel with the other callers': the page-locked copy, blob_to_polynomial's range check
     // and the Fiat-Shamir challenge (one SHA-256 over the blob)
     SlotHold slot(dev, blob);

@@ -16,6 +16,7 @@
 
 #include "../../include/kzg_mi355x.h"
 #include "ckzg_internal.h"
+#include "combine.h"
 #include "config.h"
 #include "device_guard.h"
 #include "ff.hip.h"
@@ -29,9 +30,9 @@
 #include "sha256.h"
 #include <atomic>
 #include <condition_variable>
-#include <deque>
 #include <functional>
 #include <memory>
+#include <optional>
 #include <thread>
 
 using ff::u32;
@@ -162,6 +163,8 @@ constexpr size_t HOST_CHECK_MAX = 64;  // commitments of a proof batch validated
 
 
 // ---------------------------------------------------------------- settings object
+struct CommitReq;  // ckzg.hip: the requests of the coalesced single-blob entry points
+struct ProofReq;
 struct KzgAmdSettings {
     int device = 0;
     kzgamd::MsmContext* msm = nullptr;  // prepared over g1_lagrange_brp
@@ -207,22 +210,16 @@ struct KzgAmdSettings {
     // of queueing on one mutex.  Lane objects are created on demand and live as long as the parent.
     static constexpr size_t LANE_MAX_BLOBS = 16;
     static constexpr int MAX_LANES = 15;
-    // Coalescing of concurrent single-blob calls (one queue per entry point): callers push a request; up to
-    // MAX_LEADERS of them at a time take everything queued (up to LANE_MAX_BLOBS requests) and run it as ONE batch on a
+    // Coalescing of concurrent single-blob calls (one queue per entry point, combine.h): callers push a request; up to
+    // `leaders` of them at a time take everything queued (up to LANE_MAX_BLOBS requests) and run it as ONE batch on a
     // lane, so that the ~10 runtime operations of a pipeline invocation (each of them takes a device-wide lock inside
     // the HIP runtime: ~100 us of serialised host time per invocation) are paid per batch, not per call.
-    struct CoalesceQueue {
-        std::mutex mu;
-        std::condition_variable cv;
-        std::deque<void*> pending;
-        int leaders = 0;
-        int max_leaders = 3, gather_us = 60;  // tuning keys leaders / gather_min / gather_us (apply_options)
-        size_t gather_min = 6;
-    };
+    // Tuning keys leaders / gather_min / gather_us (apply_options).
+    kzgamd::CombineQueue<CommitReq> q_commit;
+    kzgamd::CombineQueue<ProofReq> q_blob_proof, q_proof;
     // the tuning keys of config.h this layer reads, copied once when the settings object is created (apply_options;
     // lanes take their parent's)
     kzgamd::Options opt;
-    CoalesceQueue q_commit, q_blob_proof, q_proof;
     bool cfg_device_sha = false;
     int cfg_sha_lanes = 0;  // lanes per blob of the device Fiat-Shamir hash (tuning key sha_lanes; 0 = by batch size)
     size_t cfg_host_check_max = 64;  // see HOST_CHECK_MAX
@@ -233,11 +230,15 @@ struct KzgAmdSettings {
     void apply_options(const kzgamd::Options& o) {
         using namespace kzgamd;
         opt = o;
-        for (CoalesceQueue* q : {&q_commit, &q_blob_proof, &q_proof}) {
-            q->max_leaders = (int)o.t[T_LEADERS];
-            q->gather_min = (size_t)o.t[T_GATHER_MIN];
-            q->gather_us = (int)o.t[T_GATHER_US];
-        }
+        auto configure = [&o](auto& q) {
+            q.max_leaders = (int)o.t[T_LEADERS];
+            q.batch_max = LANE_MAX_BLOBS;
+            q.gather_min = (size_t)o.t[T_GATHER_MIN];
+            q.gather_us = (int)o.t[T_GATHER_US];
+        };
+        configure(q_commit);
+        configure(q_blob_proof);
+        configure(q_proof);
         cfg_device_sha = o.t[T_DEVICE_SHA] != 0;
         cfg_sha_lanes = (int)o.t[T_SHA_LANES];
         cfg_host_check_max = (size_t)o.t[T_HOST_CHECK_MAX];
@@ -263,40 +264,9 @@ struct KzgAmdSettings {
     // Page-locked blob slots for the callers of the coalesced entry points: a caller copies its blob into a slot on its
     // own thread (in parallel with the other callers) before it queues its request; the batch's kernels read the
     // slots in place.  The pool belongs to the root settings object; a caller that finds it empty leaves the copy
-    // to the leader (the lane's own staging).
-    struct PinnedSlots {
-        static constexpr int NSLOTS = 48;
-        std::mutex mu;
-        unsigned char* base = nullptr;
-        bool failed = false;
-        std::vector<unsigned char*> free_;
-        unsigned char* acquire(int device) {
-            std::lock_guard<std::mutex> lk(mu);
-            if (!base && !failed) {
-                kzgamd::DeviceGuard on_device(device);
-                if (on_device.err != hipSuccess ||
-                    hipHostMalloc((void**)&base, (size_t)NSLOTS * BYTES_PER_BLOB, hipHostMallocPortable | hipHostMallocMapped) != hipSuccess) {
-                    base = nullptr;
-                    failed = true;
-                    (void)hipGetLastError();
-                } else {
-                    for (int i = NSLOTS; i-- > 0;) free_.push_back(base + (size_t)i * BYTES_PER_BLOB);
-                }
-            }
-            if (free_.empty()) return nullptr;
-            unsigned char* p = free_.back();
-            free_.pop_back();
-            return p;
-        }
-        void release(unsigned char* p) {
-            if (!p) return;
-            std::lock_guard<std::mutex> lk(mu);
-            free_.push_back(p);
-        }
-        ~PinnedSlots() {
-            if (base) (void)hipHostFree(base);
-        }
-    } slots;
+    // to the leader (the lane's own staging).  All NSLOTS are pinned with the first caller.
+    static constexpr int NSLOTS = 48;
+    std::optional<kzgamd::SlotPool<kzgamd::PinnedMapped>> slots;  // the root's only, made once its device is known
     std::mutex lanes_mu;
     std::vector<std::unique_ptr<KzgAmdSettings>> lanes;
     std::atomic<unsigned> lane_rr{0};

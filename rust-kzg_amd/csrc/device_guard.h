@@ -27,4 +27,20 @@ struct DeviceGuard {
     DeviceGuard& operator=(const DeviceGuard&) = delete;
 };
 
+// The allocator of a handle's staging slots (combine.h: SlotPool): page-locked host memory that kernels on any device
+// read and write in place.  NULL on failure, with the runtime's sticky last-error cleared.
+struct PinnedMapped {
+    int device = 0;  // the handle's
+    void* alloc(size_t bytes) const {
+        DeviceGuard on_device(device);
+        void* p = nullptr;
+        if (on_device.err != hipSuccess || hipHostMalloc(&p, bytes, hipHostMallocPortable | hipHostMallocMapped) != hipSuccess) {
+            (void)hipGetLastError();
+            return nullptr;
+        }
+        return p;
+    }
+    void free(void* p) const { (void)hipHostFree(p); }
+};
+
 }  // namespace kzgamd

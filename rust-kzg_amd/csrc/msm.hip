@@ -21,10 +21,8 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
-#include <chrono>
-#include <condition_variable>
-#include <deque>
 #include <mutex>
+#include <optional>
 #include <string>
 #include <vector>
 
@@ -35,9 +33,11 @@
 #include "g1_30s.hip.h"
 #include "glv.hip.h"
 #include "host_g1.h"
+#include "combine.h"
 #include "config.h"
 #include "device_guard.h"
 #include "msm_internal.h"
+#include "slot_gather.hip.h"
 
 using ff::u32;
 using ff::u64;
@@ -2100,17 +2100,6 @@ struct MsmTuning {
     }
 };
 
-// The scalars of a combined batch stay where their callers staged them (page-locked slots, one per caller): one kernel
-// fetches them over PCIe into the batch's contiguous buffer instead of one copy operation per request on the stream.
-struct ScalarSlots {
-    const uint4* p[32];  // MsmContext::COMBINE_MAX
-};
-__global__ void __launch_bounds__(256) k_gather_scalars(uint4* __restrict__ dst, ScalarSlots slots, size_t per, size_t nreq) {
-    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= nreq * per) return;
-    dst[t] = slots.p[t / per][t % per];
-}
-
 struct kzgamd::MsmContext {
     std::mutex mu;
     kzgamd::Options opt;
@@ -2166,22 +2155,23 @@ struct kzgamd::MsmContext {
     static constexpr size_t EV_MAX = 4 * 512;
     // Combining of concurrent host-buffer calls on ONE prepared handle.  The reference shares the handle between rayon
     // workers (SpparkPrecomputation is Send + Sync, kzg/src/msm/sppark.rs:24-44; verify_blob_kzg_proof_batch calls the
-    // MSM from par_chunks, kzg/src/eip_4844.rs:781-805): callers of mult_pippenger_prepared queue a request; one of
-    // them at a time (the leader) takes everything queued with the same length, up to COMBINE_MAX requests, and runs
-    // it as ONE nbatch launch — the ~10 runtime operations of an invocation are paid per batch, not per call, and
-    // the GPU sees a few thousand waves instead of a few hundred.  A caller returns as soon as its own request is
-    // served; leadership passes to whoever is waiting.  Each caller copies its scalars into a page-locked slot on its
-    // own thread before it queues (truly asynchronous H2D copies; a copy from pageable memory goes through the
-    // runtime's staging path, which serialises concurrent callers).
-    struct HostCall {
+    // MSM from par_chunks, kzg/src/eip_4844.rs:781-805): callers of mult_pippenger_prepared queue a request (combine.h);
+    // a leader takes everything queued with the same length, up to COMBINE_MAX requests, and runs it as ONE nbatch
+    // launch — the ~10 runtime operations of an invocation are paid per batch, not per call, and the GPU sees a few
+    // thousand waves instead of a few hundred.  Each caller copies its scalars into a page-locked slot on its own thread
+    // before it queues (a kernel gathers them over PCIe; a copy from pageable memory goes through the runtime's staging
+    // path, which serialises concurrent callers).  A caller that finds the pool empty queues its pageable pointer.
+    struct HostCall : CombineRequest {
         void* out;
         const void* scalars;
         size_t npoints;
         unsigned char* slot = nullptr;
-        bool done = false, failed = false;
+        bool failed = false;
         HipErr err{hipSuccess, ""};
+        HostCall(void* o, const void* s, size_t np) : out(o), scalars(s), npoints(np) {}
     };
-    static constexpr size_t COMBINE_MAX = 32;  // = the pointers of ScalarSlots
+    static constexpr size_t COMBINE_MAX = 32;
+    static_assert(COMBINE_MAX == SlotPtrs::MAX, "a batch's slots travel to k_slots_gather in one SlotPtrs");
     static constexpr int COMBINE_SLOTS = 48;
     // Calls of more scalars than this take the plain path: their kernels run for a millisecond and more, next to which
     // the per-invocation cost the combiner removes is nothing — and 48 slots of the handle's full length would pin
@@ -2196,27 +2186,13 @@ struct kzgamd::MsmContext {
         DevBuf<u32> scalars;
         DevBuf<ff::Fp> out;
         unsigned char* h_out = nullptr;  // COMBINE_MAX x 144, page-locked
-        bool busy = false;
     };
-    struct Combine {
-        std::mutex mu;
-        std::condition_variable cv;
-        std::deque<HostCall*> pending;
-        int leaders = 0;
-        CombineLane lanes[COMBINE_LANES];
-        // page-locked staging slots, allocated in chunks as callers need them (4, 4, 8, 16, 16): a handle that one thread
-        // uses at a time pins four slots (a single caller keeps the fast staging path: a copy from a page-locked slot
-        // instead of the runtime's staging of pageable memory), sixteen concurrent callers grow the pool to what they use
-        std::vector<unsigned char*> slot_chunks;
-        int slots_allocated = 0;
-        size_t slot_bytes = 0;
-        bool pinned_failed = false;
-        std::vector<unsigned char*> free_slots;
-    } comb;
+    CombineQueue<HostCall> comb;  // settings from the tuning keys combine_lanes / combine_gather_min / combine_gather_us
+    CombineLane lanes[COMBINE_LANES];
+    std::optional<SlotPool<PinnedMapped>> slots;  // a prepared handle's: COMBINE_SLOTS x min(n, COMBINE_NMAX) scalars, grown in chunks
     ~MsmContext() {
         delete matrix;
-        for (auto* c : comb.slot_chunks) (void)hipHostFree(c);
-        for (auto& l : comb.lanes) {
+        for (auto& l : lanes) {
             if (l.h_out) (void)hipHostFree(l.h_out);
             l.scalars.release();
             l.out.release();
@@ -2318,6 +2294,13 @@ MsmContext* msm_create(const void* points, size_t n, bool points_on_device, bool
         HIP_TRY(hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking));
         ctx->n = n;
         ctx->prepared = prepare;
+        ctx->comb.max_leaders = ctx->tune.combine_lanes;
+        ctx->comb.batch_max = MsmContext::COMBINE_MAX;
+        ctx->comb.gather_min = (size_t)ctx->tune.combine_gather_min;
+        ctx->comb.gather_us = ctx->tune.combine_gather_us;
+        // nothing is pinned before the first combined call (prepared handles only: their n never changes)
+        ctx->slots.emplace((n < MsmContext::COMBINE_NMAX ? n : MsmContext::COMBINE_NMAX) * 32, MsmContext::COMBINE_SLOTS, SlotGrowth::Chunked,
+                           PinnedMapped{ctx->device});
         ctx->window_forced = (int)ctx->opt.t[prepare ? T_WINDOW_PREPARED : T_WINDOW];
         // The variable-base engine's GLV split (k = k1 + k2 x^2, second base psi(P) = [x^2]P) is an identity of the
         // r-torsion subgroup only, and the reference's G1::from_bytes accepts any curve point
@@ -3092,10 +3075,10 @@ static void msm_run_combined_batch(MsmContext* ctx, MsmContext::CombineLane& lan
                 bool all_slots = true;
                 for (size_t j = 0; j < nb; ++j) all_slots = all_slots && batch[j]->slot != nullptr;
                 if (all_slots) {
-                    ScalarSlots ss;
-                    for (size_t j = 0; j < MsmContext::COMBINE_MAX; ++j) ss.p[j] = j < nb ? (const uint4*)batch[j]->slot : nullptr;
+                    SlotPtrs ss;
+                    for (size_t j = 0; j < MsmContext::COMBINE_MAX; ++j) ss.p[j] = j < nb ? (uint4*)batch[j]->slot : nullptr;
                     const size_t per = np * 2, total = nb * per;  // 16-byte words per request
-                    hipLaunchKernelGGL(k_gather_scalars, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, lane.st,
+                    hipLaunchKernelGGL(k_slots_gather, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, lane.st,
                                        (uint4*)lane.scalars.p, ss, per, nb);
                 } else {  // a caller found the slot pool empty: its scalars are in pageable memory
                     for (size_t j = 0; j < nb; ++j)
@@ -3125,82 +3108,18 @@ static void msm_run_combined_batch(MsmContext* ctx, MsmContext::CombineLane& lan
 }
 
 static void msm_run_host_combined(MsmContext* ctx, void* out, const void* scalars, size_t npoints) {
-    MsmContext::HostCall me{out, scalars, npoints};
-    auto& q = ctx->comb;
-    std::vector<MsmContext::HostCall*> batch;
-    batch.reserve(MsmContext::COMBINE_MAX);  // everything that can throw happens before the request is visible
-    std::unique_lock<std::mutex> lk(q.mu);
-    if (q.free_slots.empty() && !q.pinned_failed && q.slots_allocated < MsmContext::COMBINE_SLOTS) {
-        DeviceGuard on_device(ctx->device);
-        q.slot_bytes = (ctx->n < MsmContext::COMBINE_NMAX ? ctx->n : MsmContext::COMBINE_NMAX) * 32;
-        int grow = q.slots_allocated < 8 ? 4 : q.slots_allocated < 16 ? 8 : 16;
-        if (grow > MsmContext::COMBINE_SLOTS - q.slots_allocated) grow = MsmContext::COMBINE_SLOTS - q.slots_allocated;
-        unsigned char* chunk = nullptr;
-        if (on_device.err != hipSuccess ||
-            hipHostMalloc((void**)&chunk, (size_t)grow * q.slot_bytes, hipHostMallocPortable | hipHostMallocMapped) != hipSuccess) {
-            q.pinned_failed = true;  // callers without a slot hand their own (pageable) buffer to the batch
-            (void)hipGetLastError();
-        } else {
-            q.slot_chunks.push_back(chunk);
-            q.slots_allocated += grow;
-            for (int i = grow; i-- > 0;) q.free_slots.push_back(chunk + (size_t)i * q.slot_bytes);
-        }
+    MsmContext::HostCall me(out, scalars, npoints);
+    me.slot = ctx->slots->acquire();  // none: the batch copies from the caller's own (pageable) buffer
+    if (me.slot) memcpy(me.slot, scalars, npoints * 32);
+    try {
+        combined_call(
+            ctx->comb, me, [](const MsmContext::HostCall& a, const MsmContext::HostCall& b) { return a.npoints == b.npoints; },
+            [ctx](const std::vector<MsmContext::HostCall*>& batch, int lane) { msm_run_combined_batch(ctx, ctx->lanes[lane], batch); });
+    } catch (...) {  // no memory to queue the request: nobody has seen it
+        ctx->slots->release(me.slot);
+        throw;
     }
-    if (!q.free_slots.empty()) {
-        me.slot = q.free_slots.back();
-        q.free_slots.pop_back();
-        lk.unlock();
-        memcpy(me.slot, scalars, npoints * 32);
-        lk.lock();
-    }
-    q.pending.push_back(&me);
-    q.cv.notify_one();  // a leader gathering requests may have enough now
-    while (!me.done) {
-        if (q.leaders < ctx->tune.combine_lanes && !q.pending.empty()) {
-            ++q.leaders;
-            MsmContext::CombineLane* lane = nullptr;
-            for (auto& l : q.lanes)
-                if (!l.busy) {
-                    lane = &l;
-                    break;
-                }
-            lane->busy = true;  // leaders <= lanes: one is free
-            while (!q.pending.empty() && !me.done) {
-                // another batch is in flight: a short wait lets the callers it is about to release come back with their
-                // next request — larger batches, fewer invocations
-                if (q.leaders > 1 && q.pending.size() < (size_t)ctx->tune.combine_gather_min && ctx->tune.combine_gather_us > 0) {
-                    const auto until = std::chrono::steady_clock::now() + std::chrono::microseconds(ctx->tune.combine_gather_us);
-                    while (q.pending.size() < (size_t)ctx->tune.combine_gather_min && !me.done &&
-                           q.cv.wait_until(lk, until) != std::cv_status::timeout) {
-                    }
-                    if (me.done) break;
-                    if (q.pending.empty()) continue;
-                }
-                batch.clear();
-                const size_t np = q.pending.front()->npoints;
-                for (auto it = q.pending.begin(); it != q.pending.end() && batch.size() < MsmContext::COMBINE_MAX;) {
-                    if ((*it)->npoints == np) {
-                        batch.push_back(*it);
-                        it = q.pending.erase(it);
-                    } else {
-                        ++it;
-                    }
-                }
-                lk.unlock();
-                msm_run_combined_batch(ctx, *lane, batch);
-                lk.lock();
-                for (auto* r : batch) r->done = true;
-                q.cv.notify_all();
-            }
-            lane->busy = false;
-            --q.leaders;
-            q.cv.notify_all();  // whoever still waits leads what is left
-        } else {
-            q.cv.wait(lk);
-        }
-    }
-    if (me.slot) q.free_slots.push_back(me.slot);
-    lk.unlock();
+    ctx->slots->release(me.slot);
     if (me.failed) throw me.err;
 }
 

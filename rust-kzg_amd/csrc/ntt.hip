@@ -29,6 +29,7 @@
 #include "device_guard.h"
 #include "ntt_internal.h"
 #include "ntt_plan.h"
+#include "slot_gather.hip.h"
 
 using ff::Fr;
 using fr29::Fe;
@@ -511,6 +512,9 @@ void* kzgamd::ntt_create(unsigned scale, const kzgamd::Options& opt) {
         ctx->g1_quad_max = (size_t)opt.t[kzgamd::T_G1_QUAD_MAX];
         ctx->g1_pair_max = (size_t)opt.t[kzgamd::T_G1_PAIR_MAX];
         ctx->combine = opt.t[kzgamd::T_COMBINE] != 0;
+        ctx->comb.max_leaders = NttCtx::COMB_LANES;
+        ctx->comb.batch_max = NttCtx::COMB_MAX;
+        ctx->slots.emplace(NttCtx::COMB_NMAX * sizeof(Fr), NttCtx::COMB_SLOTS, kzgamd::SlotGrowth::Chunked, kzgamd::PinnedMapped{ctx->device});
         kzgamd::expand_roots(ctx->roots, scale);
         // device twiddles in the 2^261 domain, w*2^261 = (w*2^256) * 2^5, already sliced into the 9 x 29-bit limbs
         // the butterflies multiply with (36 bytes per root instead of 32, ~27 instructions less per butterfly)
@@ -572,18 +576,8 @@ extern "C" int kzgamd_ntt_fr_device(void* vctx, void* d_out, const void* d_in, s
 }
 
 namespace {
-// ---- combining of concurrent host-buffer calls on one handle (see NttCtx::Combine) ----
-struct SlotPtrs {
-    uint4* p[32];  // NttCtx::COMB_MAX
-};
-__global__ void __launch_bounds__(256) k_slots_gather(uint4* __restrict__ dst, SlotPtrs slots, size_t per, size_t nreq) {
-    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t < nreq * per) dst[t] = slots.p[t / per][t % per];
-}
-__global__ void __launch_bounds__(256) k_slots_scatter(SlotPtrs slots, const uint4* __restrict__ src, size_t per, size_t nreq) {
-    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t < nreq * per) slots.p[t / per][t % per] = src[t];
-}
+// ---- combining of concurrent host-buffer calls on one handle (see NttCtx::comb) ----
+static_assert(NttCtx::COMB_MAX == SlotPtrs::MAX, "a batch's slots travel to k_slots_gather / k_slots_scatter in one SlotPtrs");
 void das_enqueue(NttCtx* ctx, Fr* d_odds, const Fr* d_evens, Fr* d_tmp, size_t n, size_t nbatch, hipStream_t stream);
 
 // one batch on `lane`: every request has the same kind and length; sets rc of each
@@ -619,74 +613,20 @@ void run_combined_batch(NttCtx* ctx, NttCtx::CombLane& lane, const std::vector<N
 
 // returns false when the call cannot be combined (no slot): the caller takes the plain path
 bool run_host_combined(NttCtx* ctx, void* out, const void* in, size_t n, int kind, int* rc_out) {
-    NttCtx::HostCall me{out, in, n, kind};
-    auto& q = ctx->comb;
-    std::vector<NttCtx::HostCall*> batch;
-    batch.reserve(NttCtx::COMB_MAX);
-    std::unique_lock<std::mutex> lk(q.mu);
-    if (q.free_slots.empty() && !q.pinned_failed && q.slots_allocated < NttCtx::COMB_SLOTS) {
-        kzgamd::DeviceGuard on_device(ctx->device);
-        q.slot_bytes = NttCtx::COMB_NMAX * sizeof(Fr);
-        int grow = q.slots_allocated < 8 ? 4 : q.slots_allocated < 16 ? 8 : 16;
-        if (grow > NttCtx::COMB_SLOTS - q.slots_allocated) grow = NttCtx::COMB_SLOTS - q.slots_allocated;
-        unsigned char* chunk = nullptr;
-        if (on_device.err != hipSuccess ||
-            hipHostMalloc((void**)&chunk, (size_t)grow * q.slot_bytes, hipHostMallocPortable | hipHostMallocMapped) != hipSuccess) {
-            q.pinned_failed = true;
-            (void)hipGetLastError();
-        } else {
-            q.slot_chunks.push_back(chunk);
-            q.slots_allocated += grow;
-            for (int i = grow; i-- > 0;) q.free_slots.push_back(chunk + (size_t)i * q.slot_bytes);
-        }
+    unsigned char* slot = ctx->slots->acquire();
+    if (!slot) return false;
+    memcpy(slot, in, n * sizeof(Fr));
+    NttCtx::HostCall me(n, kind, slot);
+    try {
+        kzgamd::combined_call(
+            ctx->comb, me, [](const NttCtx::HostCall& a, const NttCtx::HostCall& b) { return a.n == b.n && a.kind == b.kind; },
+            [ctx](const std::vector<NttCtx::HostCall*>& batch, int lane) { run_combined_batch(ctx, ctx->lanes[lane], batch); });
+    } catch (...) {  // no memory to queue the request: nobody has seen it
+        ctx->slots->release(slot);
+        return false;
     }
-    if (q.free_slots.empty()) return false;
-    me.slot = q.free_slots.back();
-    q.free_slots.pop_back();
-    lk.unlock();
-    memcpy(me.slot, in, n * sizeof(Fr));
-    lk.lock();
-    q.pending.push_back(&me);
-    while (!me.done) {
-        if (q.leaders < NttCtx::COMB_LANES && !q.pending.empty()) {
-            ++q.leaders;
-            NttCtx::CombLane* lane = nullptr;
-            for (auto& l : q.lanes)
-                if (!l.busy) {
-                    lane = &l;
-                    break;
-                }
-            lane->busy = true;
-            while (!q.pending.empty() && !me.done) {
-                batch.clear();
-                const size_t bn = q.pending.front()->n;
-                const int bk = q.pending.front()->kind;
-                for (auto it = q.pending.begin(); it != q.pending.end() && batch.size() < NttCtx::COMB_MAX;) {
-                    if ((*it)->n == bn && (*it)->kind == bk) {
-                        batch.push_back(*it);
-                        it = q.pending.erase(it);
-                    } else {
-                        ++it;
-                    }
-                }
-                lk.unlock();
-                run_combined_batch(ctx, *lane, batch);
-                lk.lock();
-                for (auto* r : batch) r->done = true;
-                q.cv.notify_all();
-            }
-            lane->busy = false;
-            --q.leaders;
-            q.cv.notify_all();
-        } else {
-            q.cv.wait(lk);
-        }
-    }
-    lk.unlock();
-    if (me.rc == 0) memcpy(out, me.slot, n * sizeof(Fr));
-    lk.lock();
-    q.free_slots.push_back(me.slot);
-    lk.unlock();
+    if (me.rc == 0) memcpy(out, slot, n * sizeof(Fr));
+    ctx->slots->release(slot);
     *rc_out = me.rc;
     return true;
 }

@@ -2,12 +2,12 @@
 // behind the opaque handle of kzgamd_ntt_new().
 #pragma once
 #include <hip/hip_runtime.h>
-#include <condition_variable>
-#include <deque>
 #include <map>
 #include <mutex>
+#include <optional>
 #include <vector>
 
+#include "combine.h"
 #include "ff.hip.h"
 #include "host_call.h"
 
@@ -41,46 +41,32 @@ struct NttCtx {
     size_t g1_wide_max = 4096, g1_quad_max = 16384, g1_pair_max = 32768;
 
     // Combining of concurrent host-buffer calls (ntt_fr, das_fft_extension) on ONE handle — the reference shares its
-    // FFTSettings by reference between rayon workers.  As for the prepared MSM handle (msm.hip): a caller copies its input
-    // into a page-locked slot on its own thread and queues a request; one caller at a time per lane takes everything
-    // queued of the same kind and length (up to COMB_MAX requests) and runs it as ONE batched launch: a kernel gathers the
-    // inputs from the slots over PCIe, the batched transform runs, a kernel writes the results back into the slots; every
-    // caller copies its result out of its slot.  A 4096-point transform is 4 us of GPU under ~60 us of copies, launches
-    // and a synchronisation: per batch instead of per call.  Lists longer than COMB_NMAX take the plain path.
-    struct HostCall {
-        void* out;
-        const void* in;
+    // FFTSettings by reference between rayon workers.  A caller copies its input into a page-locked slot on its own thread
+    // and queues a request (combine.h); a leader takes everything queued of the same kind and length (up to COMB_MAX
+    // requests) and runs it as ONE batched launch: a kernel gathers the inputs from the slots over PCIe, the batched
+    // transform runs, a kernel writes the results back into the slots; every caller copies its result out of its slot.
+    // A 4096-point transform is 4 us of GPU under ~60 us of copies, launches and a synchronisation: per batch instead of
+    // per call.  Lists longer than COMB_NMAX, and callers that find no slot, take the plain path.
+    struct HostCall : kzgamd::CombineRequest {
         size_t n;
         int kind;  // 0 forward, 1 inverse, 2 DAS extension
-        unsigned char* slot = nullptr;
-        bool done = false;
+        unsigned char* slot;
         int rc = 0;
+        HostCall(size_t n_, int kind_, unsigned char* slot_) : n(n_), kind(kind_), slot(slot_) {}
     };
     static constexpr size_t COMB_MAX = 32, COMB_NMAX = 8192;
     static constexpr int COMB_SLOTS = 40, COMB_LANES = 2;
     struct CombLane {
         hipStream_t st = nullptr;
         Fr *d_in = nullptr, *d_out = nullptr, *d_tmp = nullptr;  // COMB_MAX x COMB_NMAX elements each
-        bool busy = false;
     };
-    struct Combine {
-        std::mutex mu;
-        std::condition_variable cv;
-        std::deque<HostCall*> pending;
-        int leaders = 0;
-        CombLane lanes[COMB_LANES];
-        // page-locked, mapped staging slots, allocated in chunks as callers need them (4, 4, 8, ...): see msm.hip's pool
-        std::vector<unsigned char*> slot_chunks;
-        int slots_allocated = 0;
-        size_t slot_bytes = 0;
-        bool pinned_failed = false;
-        std::vector<unsigned char*> free_slots;
-    } comb;
+    kzgamd::CombineQueue<HostCall> comb;  // COMB_LANES leaders, batches of COMB_MAX, no gather wait
+    CombLane lanes[COMB_LANES];
+    std::optional<kzgamd::SlotPool<kzgamd::PinnedMapped>> slots;  // COMB_SLOTS x COMB_NMAX elements, grown in chunks
     bool combine = true;  // tuning key combine
 
     ~NttCtx() {
-        for (auto* c : comb.slot_chunks) (void)hipHostFree(c);
-        for (auto& l : comb.lanes) {
+        for (auto& l : lanes) {
             if (l.d_in) (void)hipFree(l.d_in);
             if (l.d_out) (void)hipFree(l.d_out);
             if (l.d_tmp) (void)hipFree(l.d_tmp);

@@ -1,9 +1,11 @@
 """Concurrent callers on ONE B1 / B2 handle (calls of the same kind and length are combined into batched launches below
-the seam: msm.hip msm_run_host_combined, ntt.hip run_host_combined).  The reference shares its handles between rayon workers: SpparkPrecomputation
+the seam: combine.h combined_call, which msm.hip msm_run_host_combined and ntt.hip run_host_combined queue their requests
+on).  The reference shares its handles between rayon workers: SpparkPrecomputation
 is Send + Sync and lives in an Arc (kzg/src/msm/sppark.rs:24-44), verify_blob_kzg_proof_batch calls the MSM from
 par_chunks (kzg/src/eip_4844.rs:781-805), FFT settings are shared by reference.  Sixteen threads per handle, every
-result against the oracle: mult_pippenger_prepared (whose concurrent calls are combined into one launch, msm.hip:
-msm_run_host_combined), ntt_fr / das_fft_extension, fft_g1."""
+result against the oracle: mult_pippenger_prepared (whose concurrent calls are combined into one launch),
+ntt_fr / das_fft_extension, fft_g1.  Sixty-four threads per handle, more than it has staging slots (48 / 40): the
+callers that find the pool empty."""
 import ctypes as C
 import random
 import threading
@@ -31,10 +33,10 @@ def fr_bulk(vals):
     return arr
 
 
-def run_threads(work):
-    """work(t) on THREADS threads released together; returns the list of failures the threads recorded"""
+def run_threads(work, threads=THREADS):
+    """work(t) on `threads` threads released together; returns the list of failures the threads recorded"""
     failures = []
-    gate = threading.Barrier(THREADS)
+    gate = threading.Barrier(threads)
 
     def body(t):
         try:
@@ -43,7 +45,7 @@ def run_threads(work):
         except Exception as e:  # noqa: BLE001
             failures.append((t, repr(e)))
 
-    ts = [threading.Thread(target=body, args=(t,)) for t in range(THREADS)]
+    ts = [threading.Thread(target=body, args=(t,)) for t in range(threads)]
     for th in ts:
         th.start()
     for th in ts:
@@ -231,3 +233,90 @@ def test_calls_at_and_beyond_the_combining_limit_share_one_handle(kzg, oracle):
     for key, (m, c) in got.items():
         assert c == want[m], (key, m)
     h.close()
+
+
+MANY = 64  # callers per handle in the two tests below: more than its staging slots
+
+
+def test_more_callers_than_slots_share_one_prepared_msm_handle(kzg, oracle, oracle_settings):
+    """64 threads, 8 calls each, on one prepared handle of 64 points whose pool holds 48 page-locked slots: a caller that
+    finds the pool empty queues its own (pageable) scalars, and a batch with such a request copies per request instead
+    of gathering from the slots (msm.hip: msm_run_combined_batch).  Whether a given run empties the pool is up to the
+    scheduler; that an empty pool gives no slot is checked deterministically on the CPU (test_combine_queue_cpu.py).
+    Every result against what a combine=0 handle over the same points returns for the same scalars, one call after
+    the other, and one call of each length against the oracle."""
+    L = oracle.lib()
+    n = 64
+    pts = oracle_settings.g1_lagrange_brp
+    h = kzg.prepare_multi_scalar_mult(pts, n, kzg.make_config(table_budget_gb=0.5))
+    plain = kzg.prepare_multi_scalar_mult(pts, n, kzg.make_config(table_budget_gb=0.5, tuning={"combine": 0}))
+    calls = 8
+    inputs, want = {}, {}
+    for t in range(MANY):
+        rnd = random.Random(4100 + t)
+        for k in range(calls):
+            m = 64 if (t + k) % 2 == 0 else 17
+            inputs[(t, k)] = (m, fr_bulk([rnd.randrange(O.R) for _ in range(m)]))
+    for key, (m, sc) in inputs.items():
+        want[key] = compressed(L, kzg.multi_scalar_mult_prepared(plain, sc, m))
+    for key in ((0, 0), (0, 1)):
+        m, sc = inputs[key]
+        exp = O.G1()
+        L.omsm_affine(C.byref(exp), pts, sc, m)
+        assert want[key] == compressed(L, exp), (key, m)
+    got = {}
+
+    def work(t):
+        for k in range(calls):
+            m, sc = inputs[(t, k)]
+            got[(t, k)] = compressed(L, kzg.multi_scalar_mult_prepared(h, sc, m))
+
+    assert run_threads(work, MANY) == []
+    assert len(got) == MANY * calls
+    for key in inputs:
+        assert got[key] == want[key], key
+    plain.close()
+    h.close()
+
+
+def test_more_callers_than_slots_share_one_ntt_handle(kzg):
+    """64 threads, 8 calls each, on one scale-5 handle whose pool holds 40 page-locked slots: a caller that finds the pool
+    empty takes the plain path on the handle's mutex, beside the batches of the others (ntt.hip: run_host_combined).
+    Whether a given run empties the pool is up to the scheduler; that an empty pool gives no slot is checked
+    deterministically on the CPU (test_combine_queue_cpu.py).  Lengths 32 and 8, kinds rotating over forward, inverse
+    and DAS extension — whose list is half the domain at most, so it takes 16 where the others take 32.  Every result
+    against the bytes of a combine=0 handle, one call after the other."""
+    scale = 5
+    fs = kzg.FFTSettings(scale)
+    plain = kzg.FFTSettings(scale, kzg.make_config(tuning={"combine": 0}))
+    calls = 8
+
+    def call(h, kind, n, data):
+        out = h.das_fft_extension(data, n) if kind == 2 else h.fft_fr(data, n, inverse=kind == 1)
+        return bytes(out)[: 32 * n]
+
+    inputs, want = {}, {}
+    for t in range(MANY):
+        rnd = random.Random(5200 + t)
+        for k in range(calls):
+            kind = (t + k) % 3
+            n = 32 if k % 2 == 0 else 8
+            if kind == 2 and n == 32:
+                n = 16
+            inputs[(t, k)] = (kind, n, fr_bulk([rnd.randrange(O.R) for _ in range(n)]))
+    for key, (kind, n, data) in inputs.items():
+        want[key] = call(plain, kind, n, data)
+    assert len({(kind, n) for kind, n, _ in inputs.values()}) == 6
+    got = {}
+
+    def work(t):
+        for k in range(calls):
+            kind, n, data = inputs[(t, k)]
+            got[(t, k)] = call(fs, kind, n, data)
+
+    assert run_threads(work, MANY) == []
+    assert len(got) == MANY * calls
+    for key in inputs:
+        assert got[key] == want[key], key
+    plain.close()
+    fs.close()
