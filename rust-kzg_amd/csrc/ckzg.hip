@@ -870,7 +870,6 @@ KzgAmdSettings* lookup(const CKZGSettings* s) {
 KzgAmdSettings* make_lane(KzgAmdSettings* parent) {
     std::unique_ptr<KzgAmdSettings> ln(new KzgAmdSettings());
     ln->apply_options(parent->opt);
-    ln->is_lane = true;
     ln->device = parent->device;
     kzgamd::DeviceGuard on_device(parent->device);
     CK_HIP(on_device.err);
@@ -955,10 +954,6 @@ void load_impl(CKZGSettings* out, const uint8_t* g1_mono, size_t n1m, const uint
 
     auto* dev = new KzgAmdSettings();
     dev->apply_options(opt);
-    unsigned char* d_bytes = nullptr;
-    AffPt* d_pts = nullptr;
-    int* d_bad = nullptr;
-    ff::Fp* d_p1 = nullptr;
     int cur_dev = 0;
     (void)hipGetDevice(&cur_dev);
     kzgamd::DeviceGuard placed(opt.device >= 0 ? opt.device : cur_dev);  // the caller's device is restored on return
@@ -980,32 +975,37 @@ void load_impl(CKZGSettings* out, const uint8_t* g1_mono, size_t n1m, const uint
         std::vector<uint8_t> stage(2 * N * 48);
         memcpy(stage.data(), g1_mono, N * 48);
         for (size_t i = 0; i < N; ++i) memcpy(&stage[(N + i) * 48], g1_lag + 48 * reverse_bits(i, 12), 48);
-        CK_HIP(hipMalloc(&d_bytes, stage.size()));
-        CK_HIP(hipMalloc(&d_pts, 2 * N * sizeof(AffPt)));
-        CK_HIP(hipMalloc(&d_bad, sizeof(int)));
-        CK_HIP(hipMalloc(&d_p1, 2 * N * 144));
-        CK_HIP(hipMemcpyAsync(d_bytes, stage.data(), stage.size(), hipMemcpyHostToDevice, dev->stream));
-        CK_HIP(hipMemsetAsync(d_bad, 0, sizeof(int), dev->stream));
-        hipLaunchKernelGGL(k_uncompress, dim3((unsigned)((2 * N + 127) / 128)), dim3(128), 0, dev->stream, d_pts, d_bad,
-                           d_bytes, 2 * N);
-        hipLaunchKernelGGL(k_affpt_to_blst_p1, dim3((unsigned)((2 * N + 255) / 256)), dim3(256), 0, dev->stream, d_p1,
-                           d_pts, 2 * N);
+        DevArray<unsigned char> d_bytes;
+        DevArray<AffPt> d_pts;
+        DevArray<int> d_bad;
+        DevArray<ff::Fp> d_p1;  // 2N Jacobian points
+        CK_HIP(d_bytes.try_ensure(stage.size()));
+        CK_HIP(d_pts.try_ensure(2 * N));
+        CK_HIP(d_bad.try_ensure(1));
+        CK_HIP(d_p1.try_ensure(2 * N * 3));
+        CK_HIP(hipMemcpyAsync(d_bytes.p, stage.data(), stage.size(), hipMemcpyHostToDevice, dev->stream));
+        CK_HIP(hipMemsetAsync(d_bad.p, 0, sizeof(int), dev->stream));
+        hipLaunchKernelGGL(k_uncompress, dim3((unsigned)((2 * N + 127) / 128)), dim3(128), 0, dev->stream, d_pts.p, d_bad.p,
+                           d_bytes.p, 2 * N);
+        hipLaunchKernelGGL(k_affpt_to_blst_p1, dim3((unsigned)((2 * N + 255) / 256)), dim3(256), 0, dev->stream, d_p1.p,
+                           d_pts.p, 2 * N);
         int bad = 0;
-        CK_HIP(hipMemcpyAsync(&bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, dev->stream));
+        CK_HIP(hipMemcpyAsync(&bad, d_bad.p, sizeof(int), hipMemcpyDeviceToHost, dev->stream));
         CK_HIP(hipStreamSynchronize(dev->stream));
         CK_REQUIRE(bad == 0, "Invalid G1 point in trusted setup");
 
         out->g1_values_monomial = leak_array<blst_p1>(N);
         out->g1_values_lagrange_brp = leak_array<blst_p1>(N);
-        CK_HIP(hipMemcpy(out->g1_values_monomial, d_p1, N * 144, hipMemcpyDeviceToHost));
-        CK_HIP(hipMemcpy(out->g1_values_lagrange_brp, d_p1 + 3 * N, N * 144, hipMemcpyDeviceToHost));
+        CK_HIP(hipMemcpy(out->g1_values_monomial, d_p1.p, N * 144, hipMemcpyDeviceToHost));
+        CK_HIP(hipMemcpy(out->g1_values_lagrange_brp, d_p1.p + 3 * N, N * 144, hipMemcpyDeviceToHost));
 
         // fixed-base MSM table over the bit-reversed Lagrange points (FsKZGSettings::new ->
         // prepare_msm, blst/src/types/kzg_settings.rs:109-123)
         dev->opt.device = -1;  // dev->device names the GPU from here on
-        dev->msm = kzgamd::msm_create(d_pts + N, N, true, true, true, kzgamd::G1_TRUSTED, &dev->opt);
-        CK_HIP(hipMalloc(&dev->d_monomial, N * sizeof(AffPt)));
-        CK_HIP(hipMemcpy(dev->d_monomial, d_pts, N * sizeof(AffPt), hipMemcpyDeviceToDevice));
+        dev->msm_owned.reset(kzgamd::msm_create(d_pts.p + N, N, true, true, true, kzgamd::G1_TRUSTED, &dev->opt));
+        dev->msm = dev->msm_owned.get();
+        CK_HIP(dev->d_monomial.try_ensure(N));
+        CK_HIP(hipMemcpy(dev->d_monomial.p, d_pts.p, N * sizeof(AffPt), hipMemcpyDeviceToDevice));
 
         // is_trusted_setup_in_lagrange_form (eip_4844.rs:1005-1020), the reference's own test: a file whose
         // "Lagrange" section is the monomial setup satisfies e(L_1, G2_0) == e(L_0, G2_1) (L_1 = tau * L_0).
@@ -1033,8 +1033,9 @@ void load_impl(CKZGSettings* out, const uint8_t* g1_mono, size_t n1m, const uint
             dev->brp_roots[i] = roots[reverse_bits(i, 13)];
             memcpy(&out->brp_roots_of_unity[i], &dev->brp_roots[i], 32);
         }
-        CK_HIP(hipMalloc(&dev->d_brp_roots, N * sizeof(ff::Fr)));
-        CK_HIP(hipMemcpy(dev->d_brp_roots, dev->brp_roots.data(), N * sizeof(ff::Fr), hipMemcpyHostToDevice));
+        CK_HIP(dev->brp_roots_owned.try_ensure(N));
+        dev->d_brp_roots = dev->brp_roots_owned.p;
+        CK_HIP(hipMemcpy(dev->brp_roots_owned.p, dev->brp_roots.data(), N * sizeof(ff::Fr), hipMemcpyHostToDevice));
         // FK20 columns of the settings struct (FsKZGSettings::new, blst/src/types/kzg_settings.rs:84-101): for every
         // offset < 64 the size-128 G1 transform of [ s^(N - 64 - 1 - offset - 64 i) ]_{i < 63}, identity, 64 x identity;
         // x_ext_fft_columns[row][offset] = transform[row].  This library's own cell proofs do not use them (they are
@@ -1049,26 +1050,18 @@ void load_impl(CKZGSettings* out, const uint8_t* g1_mono, size_t n1m, const uint
                 const size_t start = N - CELL_SIZE - 1 - offset;
                 for (size_t i = 0; i + 1 < CELLS_PER_BLOB; ++i) xin[offset * K2 + i] = out->g1_values_monomial[start - i * CELL_SIZE];
             }
-            dev->ntt = kzgamd::ntt_create(13, dev->opt);
+            dev->ntt.reset(kzgamd::ntt_create(13, dev->opt));
             if (!dev->ntt) throw CkErr{C_KZG_ERROR, "kzgamd_ntt_new failed"};
-            if (kzgamd_fft_g1_batch(dev->ntt, xout.data(), xin.data(), K2, CELL_SIZE, 0) != 0) throw CkErr{C_KZG_ERROR, "fft_g1"};
+            if (kzgamd_fft_g1_batch(dev->ntt.get(), xout.data(), xin.data(), K2, CELL_SIZE, 0) != 0) throw CkErr{C_KZG_ERROR, "fft_g1"};
             out->x_ext_fft_columns = leak_array<blst_p1*>(K2);
             for (size_t row = 0; row < K2; ++row) {
                 out->x_ext_fft_columns[row] = leak_array<blst_p1>(CELL_SIZE);
                 for (size_t offset = 0; offset < CELL_SIZE; ++offset) out->x_ext_fft_columns[row][offset] = xout[offset * K2 + row];
             }
         }
-        (void)hipFree(d_bytes);
-        (void)hipFree(d_pts);
-        (void)hipFree(d_bad);
-        (void)hipFree(d_p1);
         std::lock_guard<std::mutex> lk(g_registry_mu);
         g_registry[out->g1_values_lagrange_brp] = dev;
     } catch (...) {
-        if (d_bytes) (void)hipFree(d_bytes);
-        if (d_pts) (void)hipFree(d_pts);
-        if (d_bad) (void)hipFree(d_bad);
-        if (d_p1) (void)hipFree(d_p1);
         delete dev;
         free_host_arrays(out);
         throw;
@@ -1115,19 +1108,19 @@ static ff::Fr n_inverse() {
 void prove_enqueue(KzgAmdSettings* dev, size_t off, size_t n, hipStream_t stream, bool evaluate_only = false,
                    int out_mode = kzgamd::OUT_COMPRESSED) {
     // blobs [off, off + n) of the staging buffers
-    u32* scal = dev->d_scalars + off * N * 8;
-    u32* yv = dev->d_y + off * 8;
-    int* stat = dev->d_status + off;
-    const u32* bl = (const u32*)(dev->d_blobs + off * BYTES_PER_BLOB);
-    const u32* zv = (const u32*)(dev->d_z + off * 8);
+    u32* scal = dev->d_scalars.p + off * N * 8;
+    u32* yv = dev->d_y.p + off * 8;
+    int* stat = dev->d_status.p + off;
+    const u32* bl = (const u32*)(dev->d_blobs.p + off * BYTES_PER_BLOB);
+    const u32* zv = (const u32*)(dev->d_z.p + off * 8);
     CK_HIP(hipMemsetAsync(stat, 0, n * sizeof(int), stream));
     if (n <= QSPLIT_MAX) {
         // a few blobs: QS workgroups per blob, two phases (k_quotient alone is 0.4 ms of latency per call)
-        if (!dev->d_qscratch) CK_HIP(hipMalloc(&dev->d_qscratch, QSPLIT_MAX * QSCR_BYTES));
-        hipLaunchKernelGGL(k_quotient_init, dim3(1), dim3(64), 0, stream, dev->d_qscratch, n);
-        hipLaunchKernelGGL(k_quotient_a, dim3((unsigned)(n * QS)), dim3(QT), 0, stream, dev->d_qscratch, stat, bl, zv,
+        CK_HIP(dev->d_qscratch.try_ensure(QSPLIT_MAX * QSCR_BYTES));
+        hipLaunchKernelGGL(k_quotient_init, dim3(1), dim3(64), 0, stream, dev->d_qscratch.p, n);
+        hipLaunchKernelGGL(k_quotient_a, dim3((unsigned)(n * QS)), dim3(QT), 0, stream, dev->d_qscratch.p, stat, bl, zv,
                            (const ff::Fr*)dev->d_brp_roots);
-        hipLaunchKernelGGL(k_quotient_b, dim3((unsigned)(n * QS)), dim3(QT), 0, stream, scal, yv, dev->d_qscratch, bl, zv,
+        hipLaunchKernelGGL(k_quotient_b, dim3((unsigned)(n * QS)), dim3(QT), 0, stream, scal, yv, dev->d_qscratch.p, bl, zv,
                            (const ff::Fr*)dev->d_brp_roots, n_inverse());
     } else {
         hipLaunchKernelGGL(k_quotient, dim3((unsigned)n), dim3(QT), 0, stream, scal, yv, stat, bl, zv,
@@ -1136,7 +1129,7 @@ void prove_enqueue(KzgAmdSettings* dev, size_t off, size_t n, hipStream_t stream
     if (evaluate_only) return;  // y = p(z) is all the caller wants (the field work of batched verification)
     {
         kzgamd::MsmLock locked(dev->msm);
-        kzgamd::msm_enqueue(dev->msm, dev->d_out + off * (out_mode == kzgamd::OUT_JACOBIAN ? 144 : 48), scal, N, n, 0, stream,
+        kzgamd::msm_enqueue(dev->msm, dev->d_out.p + off * (out_mode == kzgamd::OUT_JACOBIAN ? 144 : 48), scal, N, n, 0, stream,
                             out_mode);
     }
 }
@@ -1212,7 +1205,7 @@ void prove_batch(KZGProof* proofs, Bytes32* ys, const Blob* blobs, const Bytes32
     const bool derive = zs == nullptr;
     // The blobs are in pageable memory: the copy call below returns when they are staged (~1.5 ms for 256 blobs).
     // When the challenges have to be derived, the hashing threads are started first and run beside it.
-    if (!derive) CK_HIP(hipMemcpyAsync(dev->d_blobs, blobs, n * BYTES_PER_BLOB, hipMemcpyHostToDevice, dev->stream));
+    if (!derive) CK_HIP(hipMemcpyAsync(dev->d_blobs.p, blobs, n * BYTES_PER_BLOB, hipMemcpyHostToDevice, dev->stream));
     // Commitment validity (decode + subgroup) only decides BadArgs at the end; nothing downstream depends
     // on it.  A few commitments: on the host while the GPU proves (a serial 381-bit chain is ~7x faster on
     // a CPU core than in one GPU lane); a batch: one lane each on a second stream.
@@ -1227,23 +1220,23 @@ void prove_batch(KZGProof* proofs, Bytes32* ys, const Blob* blobs, const Bytes32
     if (derive) {
         cstat.assign(n, 0);
         if (!host_check && !commitments_checked_elsewhere) {
-            CK_HIP(hipMemcpyAsync(dev->d_commit, commitments, n * 48, hipMemcpyHostToDevice, dev->stream2));
+            CK_HIP(hipMemcpyAsync(dev->d_commit.p, commitments, n * 48, hipMemcpyHostToDevice, dev->stream2));
             if (device_sha) {
                 if (!dev->ev_commit) CK_HIP(hipEventCreateWithFlags(&dev->ev_commit, hipEventDisableTiming));
                 CK_HIP(hipEventRecord(dev->ev_commit, dev->stream2));
             }
-            CK_HIP(hipMemsetAsync(dev->d_cstatus, 0, n * sizeof(int), dev->stream2));
+            CK_HIP(hipMemsetAsync(dev->d_cstatus.p, 0, n * sizeof(int), dev->stream2));
             // up to 512 commitments: square root and membership test limb-parallel (0.3 + 0.25 ms instead of 1.7 ms of
             // single-lane chain; a wave per point is ~9x the instructions of a lane per point, which a larger batch,
             // whose MSM hides the chain anyway, should not pay)
             if (n <= WIDE_COMMIT_CHECK_MAX && dev->cfg_wide_check) {
-                hipLaunchKernelGGL(k_decode_g1_wide, dim3((unsigned)((n + 3) / 4)), dim3(64), 0, dev->stream2, dev->d_cpts,
-                                   dev->d_cstatus, (const unsigned char*)dev->d_commit, n);
-                hipLaunchKernelGGL(k_affpts_in_g1_wide, dim3((unsigned)n), dim3(64), 0, dev->stream2, dev->d_cstatus,
-                                   (const AffPt*)dev->d_cpts, n);
+                hipLaunchKernelGGL(k_decode_g1_wide, dim3((unsigned)((n + 3) / 4)), dim3(64), 0, dev->stream2, dev->d_cpts.p,
+                                   dev->d_cstatus.p, (const unsigned char*)dev->d_commit.p, n);
+                hipLaunchKernelGGL(k_affpts_in_g1_wide, dim3((unsigned)n), dim3(64), 0, dev->stream2, dev->d_cstatus.p,
+                                   (const AffPt*)dev->d_cpts.p, n);
             } else {
                 hipLaunchKernelGGL(k_check_commitments, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, dev->stream2,
-                                   dev->d_cstatus, (const unsigned char*)dev->d_commit, n);
+                                   dev->d_cstatus.p, (const unsigned char*)dev->d_commit.p, n);
             }
             // its result is fetched at the very end: a device-to-host copy into pageable memory blocks the calling
             // thread until the kernel is done (1.7 ms for 256 commitments), and nothing below depends on it
@@ -1268,14 +1261,14 @@ void prove_batch(KZGProof* proofs, Bytes32* ys, const Blob* blobs, const Bytes32
         for (size_t k = 0; k < nchunks; ++k) {
             const size_t off = k * chunk, cn = off + chunk <= n ? chunk : n - off;
             hipStream_t cs = dev->pipe_stream(k);
-            CK_HIP(hipMemcpyAsync(dev->d_blobs + off * BYTES_PER_BLOB, blobs + off, cn * BYTES_PER_BLOB, hipMemcpyHostToDevice, cs));
+            CK_HIP(hipMemcpyAsync(dev->d_blobs.p + off * BYTES_PER_BLOB, blobs + off, cn * BYTES_PER_BLOB, hipMemcpyHostToDevice, cs));
             if (k < (size_t)KzgAmdSettings::NPIPE) CK_HIP(hipStreamWaitEvent(cs, dev->ev_commit, 0));
-            launch_challenge_sha256((u32*)(dev->d_z + off * 8), (const u32*)(dev->d_blobs + off * BYTES_PER_BLOB),
-                                    (const u32*)(dev->d_commit + off * 48), cn, dev->cfg_sha_lanes, cs);
+            launch_challenge_sha256((u32*)(dev->d_z.p + off * 8), (const u32*)(dev->d_blobs.p + off * BYTES_PER_BLOB),
+                                    (const u32*)(dev->d_commit.p + off * 48), cn, dev->cfg_sha_lanes, cs);
             prove_enqueue(dev, off, cn, cs, proofs == nullptr, out_mode);
         }
         dev->pipe_join();  // dev->stream now waits for every chunk
-        CK_HIP(hipMemcpyAsync(zbuf.data(), dev->d_z, n * 32, hipMemcpyDeviceToHost, dev->stream));
+        CK_HIP(hipMemcpyAsync(zbuf.data(), dev->d_z.p, n * 32, hipMemcpyDeviceToHost, dev->stream));
     } else if (derive && nth > 1 && n >= 2 * PROVE_CHUNK) {
         // blobs per pipeline chunk (median ms per call, chunk 64 / 128 / 256: 256 blobs 6.63 / 6.25 / 6.41, 512 blobs
         // 11.0 / 9.1 / 9.7, 1024 blobs 19.0 / 16.5 / 16.2)
@@ -1313,7 +1306,7 @@ void prove_batch(KZGProof* proofs, Bytes32* ys, const Blob* blobs, const Bytes32
             (void)hipSetDevice(dev->device);
             for (size_t k = 0; k < nchunks; ++k) {
                 const size_t off = coff[k], cn = coff[k + 1] - off;
-                if (hipMemcpyAsync(dev->d_blobs + off * BYTES_PER_BLOB, blobs + off, cn * BYTES_PER_BLOB, hipMemcpyHostToDevice,
+                if (hipMemcpyAsync(dev->d_blobs.p + off * BYTES_PER_BLOB, blobs + off, cn * BYTES_PER_BLOB, hipMemcpyHostToDevice,
                                    cs[k]) != hipSuccess)
                     copy_err.store(1);
                 copied.store(k + 1, std::memory_order_release);
@@ -1342,7 +1335,7 @@ void prove_batch(KZGProof* proofs, Bytes32* ys, const Blob* blobs, const Bytes32
                 std::this_thread::yield();
             for (size_t i = off; i < off + cn; ++i) all_ok = all_ok && blob_ok[i];
             if (!all_ok || copy_err.load()) break;
-            CK_HIP(hipMemcpyAsync(dev->d_z + off * 8, zs + off, cn * 32, hipMemcpyHostToDevice, cs[k]));
+            CK_HIP(hipMemcpyAsync(dev->d_z.p + off * 8, zs + off, cn * 32, hipMemcpyHostToDevice, cs[k]));
             prove_enqueue(dev, off, cn, cs[k], proofs == nullptr, out_mode);
         }
         copier.join();
@@ -1364,7 +1357,7 @@ void prove_batch(KZGProof* proofs, Bytes32* ys, const Blob* blobs, const Bytes32
                 }
             };
             if (nth == 1) {
-                CK_HIP(hipMemcpyAsync(dev->d_blobs, blobs, n * BYTES_PER_BLOB, hipMemcpyHostToDevice, dev->stream));
+                CK_HIP(hipMemcpyAsync(dev->d_blobs.p, blobs, n * BYTES_PER_BLOB, hipMemcpyHostToDevice, dev->stream));
                 work(0);
             } else {
                 // hash on the pool while this thread stages the blobs (pageable memory: the copy call returns when
@@ -1373,7 +1366,7 @@ void prove_batch(KZGProof* proofs, Bytes32* ys, const Blob* blobs, const Bytes32
                 hipError_t ce = hipSuccess;
                 std::thread copier([&] {
                     (void)hipSetDevice(dev->device);
-                    ce = hipMemcpyAsync(dev->d_blobs, blobs, n * BYTES_PER_BLOB, hipMemcpyHostToDevice, dev->stream);
+                    ce = hipMemcpyAsync(dev->d_blobs.p, blobs, n * BYTES_PER_BLOB, hipMemcpyHostToDevice, dev->stream);
                 });
                 struct Joiner {  // an exception out of the pool must not leave a joinable thread behind (std::terminate)
                     std::thread& t;
@@ -1392,7 +1385,7 @@ void prove_batch(KZGProof* proofs, Bytes32* ys, const Blob* blobs, const Bytes32
                     throw CkErr{C_KZG_BADARGS, "Invalid scalar"};
                 }
         }
-        CK_HIP(hipMemcpyAsync(dev->d_z, zs, n * 32, hipMemcpyHostToDevice, dev->stream));
+        CK_HIP(hipMemcpyAsync(dev->d_z.p, zs, n * 32, hipMemcpyHostToDevice, dev->stream));
         prove_enqueue(dev, 0, n, dev->stream, proofs == nullptr, out_mode);
     }
     // commitment check on the host, while the GPU works (the copies below block until it is done)
@@ -1413,15 +1406,15 @@ void prove_batch(KZGProof* proofs, Bytes32* ys, const Blob* blobs, const Bytes32
     std::vector<int> status(n);
     std::vector<u32> ylimbs(n * 8);
     blst_p1 jac[HOST_COMPRESS_MAX];
-    CK_HIP(hipMemcpyAsync(status.data(), dev->d_status, n * sizeof(int), hipMemcpyDeviceToHost, dev->stream));
-    CK_HIP(hipMemcpyAsync(ylimbs.data(), dev->d_y, n * 32, hipMemcpyDeviceToHost, dev->stream));
-    if (host_compress) CK_HIP(hipMemcpyAsync(jac, dev->d_out, n * 144, hipMemcpyDeviceToHost, dev->stream));
-    else if (proofs) CK_HIP(hipMemcpyAsync(proofs, dev->d_out, n * 48, hipMemcpyDeviceToHost, dev->stream));
+    CK_HIP(hipMemcpyAsync(status.data(), dev->d_status.p, n * sizeof(int), hipMemcpyDeviceToHost, dev->stream));
+    CK_HIP(hipMemcpyAsync(ylimbs.data(), dev->d_y.p, n * 32, hipMemcpyDeviceToHost, dev->stream));
+    if (host_compress) CK_HIP(hipMemcpyAsync(jac, dev->d_out.p, n * 144, hipMemcpyDeviceToHost, dev->stream));
+    else if (proofs) CK_HIP(hipMemcpyAsync(proofs, dev->d_out.p, n * 48, hipMemcpyDeviceToHost, dev->stream));
     CK_HIP(hipStreamSynchronize(dev->stream));
     if (zs_out) memcpy(zs_out, zs, n * 32);
     if (derive) {
         if (!host_check && !commitments_checked_elsewhere) {
-            CK_HIP(hipMemcpyAsync(cstat.data(), dev->d_cstatus, n * sizeof(int), hipMemcpyDeviceToHost, dev->stream2));
+            CK_HIP(hipMemcpyAsync(cstat.data(), dev->d_cstatus.p, n * sizeof(int), hipMemcpyDeviceToHost, dev->stream2));
             CK_HIP(hipStreamSynchronize(dev->stream2));
         }
         for (size_t i = 0; i < n; ++i) CK_REQUIRE(cstat[i] == 0, "Invalid commitment");
@@ -1562,10 +1555,10 @@ void commit_lane_batch(KzgAmdSettings* dev, const std::vector<CommitReq*>& reqs)
     int* hs = reinterpret_cast<int*>(dev->h_res);
     unsigned char* ho = dev->h_res + KzgAmdSettings::LANE_MAX_BLOBS * sizeof(int);
     auto enqueue_all = [&] {
-        commit_enqueue(dev, dev->d_out, dev->d_status, nullptr, dev->d_scalars, n, dev->stream,
+        commit_enqueue(dev, dev->d_out.p, dev->d_status.p, nullptr, dev->d_scalars.p, n, dev->stream,
                        host_compress ? kzgamd::OUT_JACOBIAN : kzgamd::OUT_COMPRESSED, &ptrs);
-        CK_HIP(hipMemcpyAsync(hs, dev->d_status, n * sizeof(int), hipMemcpyDeviceToHost, dev->stream));
-        CK_HIP(hipMemcpyAsync(ho, dev->d_out, n * (host_compress ? 144 : 48), hipMemcpyDeviceToHost, dev->stream));
+        CK_HIP(hipMemcpyAsync(hs, dev->d_status.p, n * sizeof(int), hipMemcpyDeviceToHost, dev->stream));
+        CK_HIP(hipMemcpyAsync(ho, dev->d_out.p, n * (host_compress ? 144 : 48), hipMemcpyDeviceToHost, dev->stream));
     };
     // (Replaying this sequence as one captured graph per batch size was measured: 19.4 k vs 18.9 k commitments/s at 16
     // threads, 3 991 vs 4 040 /s for one — nothing; the call-by-call form stays.  profiles/NOTES.md §9.)
@@ -1645,22 +1638,22 @@ extern "C" C_KZG_RET kzgamd_blob_to_kzg_commitment_batch(KZGCommitment* out, con
             for (size_t k = 0; off < n; ++k) {
                 const size_t cn = k == 0 ? first : (off + chunk <= n ? chunk : n - off);
                 hipStream_t cs = dev->pipe_stream(k);
-                CK_HIP(hipMemcpyAsync(dev->d_blobs + off * BYTES_PER_BLOB, blobs + off, cn * BYTES_PER_BLOB, hipMemcpyHostToDevice, cs));
-                commit_enqueue(dev, dev->d_out + off * 48, dev->d_status + off, dev->d_blobs + off * BYTES_PER_BLOB,
-                               dev->d_scalars + off * N * 8, cn, cs, kzgamd::OUT_COMPRESSED);
+                CK_HIP(hipMemcpyAsync(dev->d_blobs.p + off * BYTES_PER_BLOB, blobs + off, cn * BYTES_PER_BLOB, hipMemcpyHostToDevice, cs));
+                commit_enqueue(dev, dev->d_out.p + off * 48, dev->d_status.p + off, dev->d_blobs.p + off * BYTES_PER_BLOB,
+                               dev->d_scalars.p + off * N * 8, cn, cs, kzgamd::OUT_COMPRESSED);
                 off += cn;
             }
             dev->pipe_join();
         } else {
-            CK_HIP(hipMemcpyAsync(dev->d_blobs, blobs, n * BYTES_PER_BLOB, hipMemcpyHostToDevice, dev->stream));
-            commit_enqueue(dev, dev->d_out, dev->d_status, dev->d_blobs, dev->d_scalars, n, dev->stream,
+            CK_HIP(hipMemcpyAsync(dev->d_blobs.p, blobs, n * BYTES_PER_BLOB, hipMemcpyHostToDevice, dev->stream));
+            commit_enqueue(dev, dev->d_out.p, dev->d_status.p, dev->d_blobs.p, dev->d_scalars.p, n, dev->stream,
                            host_compress ? kzgamd::OUT_JACOBIAN : kzgamd::OUT_COMPRESSED);
         }
         std::vector<int> status(n);
         blst_p1 jac[HOST_COMPRESS_MAX];
-        CK_HIP(hipMemcpyAsync(status.data(), dev->d_status, n * sizeof(int), hipMemcpyDeviceToHost, dev->stream));
-        if (host_compress) CK_HIP(hipMemcpyAsync(jac, dev->d_out, n * 144, hipMemcpyDeviceToHost, dev->stream));
-        else CK_HIP(hipMemcpyAsync(out, dev->d_out, n * 48, hipMemcpyDeviceToHost, dev->stream));
+        CK_HIP(hipMemcpyAsync(status.data(), dev->d_status.p, n * sizeof(int), hipMemcpyDeviceToHost, dev->stream));
+        if (host_compress) CK_HIP(hipMemcpyAsync(jac, dev->d_out.p, n * 144, hipMemcpyDeviceToHost, dev->stream));
+        else CK_HIP(hipMemcpyAsync(out, dev->d_out.p, n * 48, hipMemcpyDeviceToHost, dev->stream));
         CK_HIP(hipStreamSynchronize(dev->stream));
         for (size_t i = 0; i < n; ++i) CK_REQUIRE(status[i] == 0, "Invalid scalar");
         if (host_compress) compress_on_host(out[0].bytes, jac, n);
@@ -1803,12 +1796,12 @@ void proof_lane_batch(KzgAmdSettings* root, const std::vector<ProofReq*>& reqs, 
         }
         try {
             hipLaunchKernelGGL(k_gather_blobs, dim3((unsigned)((n * (BYTES_PER_BLOB / 16) + 255) / 256)), dim3(256), 0, dev->stream,
-                               reinterpret_cast<uint4*>(dev->d_blobs), ptrs, n);
-            CK_HIP(hipMemcpyAsync(dev->d_z, hz, n * 32, hipMemcpyHostToDevice, dev->stream));
+                               reinterpret_cast<uint4*>(dev->d_blobs.p), ptrs, n);
+            CK_HIP(hipMemcpyAsync(dev->d_z.p, hz, n * 32, hipMemcpyHostToDevice, dev->stream));
             prove_enqueue(dev, 0, n, dev->stream, false, kzgamd::OUT_JACOBIAN);
-            CK_HIP(hipMemcpyAsync(hs, dev->d_status, n * sizeof(int), hipMemcpyDeviceToHost, dev->stream));
-            CK_HIP(hipMemcpyAsync(hy, dev->d_y, n * 32, hipMemcpyDeviceToHost, dev->stream));
-            CK_HIP(hipMemcpyAsync(ho, dev->d_out, n * 144, hipMemcpyDeviceToHost, dev->stream));
+            CK_HIP(hipMemcpyAsync(hs, dev->d_status.p, n * sizeof(int), hipMemcpyDeviceToHost, dev->stream));
+            CK_HIP(hipMemcpyAsync(hy, dev->d_y.p, n * 32, hipMemcpyDeviceToHost, dev->stream));
+            CK_HIP(hipMemcpyAsync(ho, dev->d_out.p, n * 144, hipMemcpyDeviceToHost, dev->stream));
         } catch (...) {
             (void)hipStreamSynchronize(dev->stream);  // whatever was enqueued still reads the callers' slots
             throw;
@@ -1923,7 +1916,7 @@ extern "C" void bytes_from_bls_field(Bytes32* out, const blst_fr* in) {         
 extern "C" int kzgamd_settings_table_info(const CKZGSettings* s, int which, int* window_bits, int* rows, int* wide_table) {
     KzgAmdSettings* dev = lookup(s);
     if (!dev || which < 0 || which > 2) return -1;
-    kzgamd::MsmContext* h = which == 0 ? dev->msm : which == 1 ? dev->msm_monomial : dev->msm_xext;
+    kzgamd::MsmContext* h = which == 0 ? dev->msm : which == 1 ? dev->msm_monomial.get() : dev->msm_xext.get();
     if (!h) {
         if (wide_table) *wide_table = 0;
         return 1;

@@ -112,44 +112,44 @@ void fk20_prepare(KzgAmdSettings* dev, const CKZGSettings* cs) {
     const size_t K2 = 2 * CELLS_PER_BLOB, total = K2 * CELL_SIZE;
     std::vector<ff::Fp> aff(2 * total);  // blst_p1_affine: x, y (the columns hold no point at infinity for a valid setup)
     kzgamd::host_p1_to_affine_batch(aff.data(), total, [&](size_t k) { return &cs->x_ext_fft_columns[k / CELL_SIZE][k % CELL_SIZE]; });
-    dev->msm_xext = kzgamd::msm_create(aff.data(), total, false, true, false, kzgamd::G1_TRUSTED, &dev->opt);
+    dev->msm_xext.reset(kzgamd::msm_create(aff.data(), total, false, true, false, kzgamd::G1_TRUSTED, &dev->opt));
 }
 
-// The 128 cell proofs of n polynomials whose 4096 monomial coefficients are in dev->d_fr_b, compressed into
-// dev->d_proofs (compute_fk20_proofs + reverse_bit_order, kzg/src/das.rs:280-288, 630-696): enqueue only.
+// The 128 cell proofs of n polynomials whose 4096 monomial coefficients are in dev->d_fr_b.p, compressed into
+// dev->d_proofs.p (compute_fk20_proofs + reverse_bit_order, kzg/src/das.rs:280-288, 630-696): enqueue only.
 // The caller has prepared the handle its `fk20` choice needs and the buffers (ensure_fk20 / ensure_q).
 void enqueue_cell_proofs(KzgAmdSettings* dev, size_t n, hipStream_t st, bool fk20) {
     if (fk20) {
         const size_t nv = n * 64 * 128;
-        hipLaunchKernelGGL(k_fk20_toeplitz, dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, st, dev->d_fk_a,
-                           (const ff::Fr*)dev->d_fr_b, n);
-        if (kzgamd_ntt_fr_device(dev->ntt, dev->d_fk_b, dev->d_fk_a, 128, 64 * n, 0, st) != 0) throw CkErr{C_KZG_ERROR, "ntt"};
+        hipLaunchKernelGGL(k_fk20_toeplitz, dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, st, dev->d_fk_a.p,
+                           (const ff::Fr*)dev->d_fr_b.p, n);
+        if (kzgamd_ntt_fr_device(dev->ntt.get(), dev->d_fk_b.p, dev->d_fk_a.p, 128, 64 * n, 0, st) != 0) throw CkErr{C_KZG_ERROR, "ntt"};
         ff::Fr k128 = ff::Fr::zero();
         k128.v[0] = 128;
         const ff::Fr inv128 = ff::inverse_bgcd(ff::to_mont(k128));  // Montgomery form of 1/128
-        hipLaunchKernelGGL(k_fk20_transpose, dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, st, dev->d_fk_a,
-                           (const ff::Fr*)dev->d_fk_b, n, inv128);
+        hipLaunchKernelGGL(k_fk20_transpose, dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, st, dev->d_fk_a.p,
+                           (const ff::Fr*)dev->d_fk_b.p, n, inv128);
         // h_ext_fft[blob][j] = sum_i coeffs[j][i] * x_ext_fft_columns[j][i]: 128 n MSMs of 64 points, column j of the table
         {
-            kzgamd::MsmLock locked(dev->msm_xext);
-            kzgamd::msm_enqueue(dev->msm_xext, dev->d_fk_h, dev->d_fk_a, CELL_SIZE, n * 128, 1, st, kzgamd::OUT_XYZZ, false, 128);
+            kzgamd::MsmLock locked(dev->msm_xext.get());
+            kzgamd::msm_enqueue(dev->msm_xext.get(), dev->d_fk_h.p, dev->d_fk_a.p, CELL_SIZE, n * 128, 1, st, kzgamd::OUT_XYZZ, false, 128);
         }
         // h = ifft_g1(h_ext_fft), upper half cleared, proofs = fft_g1(h), bit-reversed, compressed
-        g1::Xyzz* h = (g1::Xyzz*)kzgamd::fftg1_device((NttCtx*)dev->ntt, dev->d_fk_h, dev->d_fk_h2, 128, n, 1, st, false);
+        g1::Xyzz* h = (g1::Xyzz*)kzgamd::fftg1_device((NttCtx*)dev->ntt.get(), dev->d_fk_h.p, dev->d_fk_h2.p, 128, n, 1, st, false);
         if (!h) throw CkErr{C_KZG_ERROR, "fft_g1"};
-        g1::Xyzz* other = h == dev->d_fk_h ? dev->d_fk_h2 : dev->d_fk_h;
+        g1::Xyzz* other = h == dev->d_fk_h.p ? dev->d_fk_h2.p : dev->d_fk_h.p;
         hipLaunchKernelGGL(k_fk20_zero_upper, dim3((unsigned)((n * 64 + 255) / 256)), dim3(256), 0, st, h, n);
-        g1::Xyzz* pr = (g1::Xyzz*)kzgamd::fftg1_device((NttCtx*)dev->ntt, h, other, 128, n, 0, st);
+        g1::Xyzz* pr = (g1::Xyzz*)kzgamd::fftg1_device((NttCtx*)dev->ntt.get(), h, other, 128, n, 0, st);
         if (!pr) throw CkErr{C_KZG_ERROR, "fft_g1"};
         g1::Xyzz* fin = pr == h ? other : h;
         hipLaunchKernelGGL(k_fk20_brp, dim3((unsigned)((n * 128 + 255) / 256)), dim3(256), 0, st, fin, (const g1::Xyzz*)pr, n);
-        kzgamd::g1_compress_xyzz(dev->d_proofs, fin, n * 128, st);
+        kzgamd::g1_compress_xyzz(dev->d_proofs.p, fin, n * 128, st);
     } else {
-        hipLaunchKernelGGL(k_cell_quotients, dim3((unsigned)(n * 128)), dim3(64), 0, st, dev->d_q, (const ff::Fr*)dev->d_fr_b,
-                           (const ff::Fr*)dev->d_roots8192, n);
+        hipLaunchKernelGGL(k_cell_quotients, dim3((unsigned)(n * 128)), dim3(64), 0, st, dev->d_q.p, (const ff::Fr*)dev->d_fr_b.p,
+                           (const ff::Fr*)dev->d_roots8192.p, n);
         {
-            kzgamd::MsmLock locked(dev->msm_monomial);
-            kzgamd::msm_enqueue(dev->msm_monomial, dev->d_proofs, dev->d_q, N, n * 128, 0, st, kzgamd::OUT_COMPRESSED);
+            kzgamd::MsmLock locked(dev->msm_monomial.get());
+            kzgamd::msm_enqueue(dev->msm_monomial.get(), dev->d_proofs.p, dev->d_q.p, N, n * 128, 0, st, kzgamd::OUT_COMPRESSED);
         }
     }
 }
@@ -172,21 +172,20 @@ bool prepare_cell_proofs(KzgAmdSettings* dev, const CKZGSettings* cs, size_t n) 
         } catch (...) {
             dev->fk20_unavailable = true;
         }
-        if (!dev->fk20_unavailable && !kzgamd::msm_has_wide_table(dev->msm_xext)) dev->fk20_unavailable = true;
+        if (!dev->fk20_unavailable && !kzgamd::msm_has_wide_table(dev->msm_xext.get())) dev->fk20_unavailable = true;
         if (dev->fk20_unavailable) {
-            if (dev->msm_xext) kzgamd::msm_destroy(dev->msm_xext);
-            dev->msm_xext = nullptr;
+            dev->msm_xext.reset();
             fk20 = false;
         }
     }
-    if (!fk20 && !dev->msm_monomial) dev->msm_monomial = kzgamd::msm_create(dev->d_monomial, N, true, true, true, kzgamd::G1_TRUSTED, &dev->opt);
+    if (!fk20 && !dev->msm_monomial) dev->msm_monomial.reset(kzgamd::msm_create(dev->d_monomial.p, N, true, true, true, kzgamd::G1_TRUSTED, &dev->opt));
     return fk20;
 }
 
 void ensure_roots8192(KzgAmdSettings* dev, const CKZGSettings* cs) {
-    if (dev->d_roots8192) return;
-    CK_HIP(hipMalloc(&dev->d_roots8192, (2 * N + 1) * sizeof(ff::Fr)));
-    CK_HIP(hipMemcpy(dev->d_roots8192, cs->roots_of_unity, (2 * N + 1) * sizeof(ff::Fr), hipMemcpyHostToDevice));
+    if (dev->d_roots8192.p) return;
+    CK_HIP(dev->d_roots8192.try_ensure(2 * N + 1));
+    CK_HIP(hipMemcpy(dev->d_roots8192.p, cs->roots_of_unity, (2 * N + 1) * sizeof(ff::Fr), hipMemcpyHostToDevice));
 }
 
 // compute_cells_and_kzg_proofs (kzg/src/das.rs:244-292) for n blobs; cells / proofs may be null (not both)
@@ -202,21 +201,21 @@ void cells_and_proofs(uint8_t* cells, KZGProof* proofs, const Blob* blobs, size_
     if (proofs && fk20) dev->ensure_fk20(n);
     if (proofs && !fk20) dev->ensure_q(n);
     hipStream_t st = dev->stream;
-    CK_HIP(hipMemcpyAsync(dev->d_blobs, blobs, n * BYTES_PER_BLOB, hipMemcpyHostToDevice, st));
-    CK_HIP(hipMemsetAsync(dev->d_status, 0, n * sizeof(int), st));
-    hipLaunchKernelGGL(k_blob_to_fr_brp, dim3((unsigned)((n * N + 255) / 256)), dim3(256), 0, st, dev->d_fr_a, dev->d_status,
-                       (const u32*)dev->d_blobs, n);
+    CK_HIP(hipMemcpyAsync(dev->d_blobs.p, blobs, n * BYTES_PER_BLOB, hipMemcpyHostToDevice, st));
+    CK_HIP(hipMemsetAsync(dev->d_status.p, 0, n * sizeof(int), st));
+    hipLaunchKernelGGL(k_blob_to_fr_brp, dim3((unsigned)((n * N + 255) / 256)), dim3(256), 0, st, dev->d_fr_a.p, dev->d_status.p,
+                       (const u32*)dev->d_blobs.p, n);
     // poly_lagrange_to_monomial: inverse NTT of the bit-reversed evaluations
-    if (kzgamd_ntt_fr_device(dev->ntt, dev->d_fr_b, dev->d_fr_a, N, n, 1, st) != 0) throw CkErr{C_KZG_ERROR, "ntt"};
+    if (kzgamd_ntt_fr_device(dev->ntt.get(), dev->d_fr_b.p, dev->d_fr_a.p, N, n, 1, st) != 0) throw CkErr{C_KZG_ERROR, "ntt"};
     if (cells) {
-        hipLaunchKernelGGL(k_zero_extend, dim3((unsigned)((n * 2 * N + 255) / 256)), dim3(256), 0, st, dev->d_fr_ext,
-                           (const ff::Fr*)dev->d_fr_b, n);
+        hipLaunchKernelGGL(k_zero_extend, dim3((unsigned)((n * 2 * N + 255) / 256)), dim3(256), 0, st, dev->d_fr_ext.p,
+                           (const ff::Fr*)dev->d_fr_b.p, n);
         // d_fr_a is free again only for n*N elements; the 8192-point result needs its own buffer: reuse d_cells
         // as scratch for the transform output, then convert in place through d_fr_ext
-        ff::Fr* ev = reinterpret_cast<ff::Fr*>(dev->d_cells);
-        if (kzgamd_ntt_fr_device(dev->ntt, ev, dev->d_fr_ext, 2 * N, n, 0, st) != 0) throw CkErr{C_KZG_ERROR, "ntt"};
+        ff::Fr* ev = reinterpret_cast<ff::Fr*>(dev->d_cells.p);
+        if (kzgamd_ntt_fr_device(dev->ntt.get(), ev, dev->d_fr_ext.p, 2 * N, n, 0, st) != 0) throw CkErr{C_KZG_ERROR, "ntt"};
         hipLaunchKernelGGL(k_cells_out, dim3((unsigned)((n * 2 * N + 255) / 256)), dim3(256), 0, st,
-                           reinterpret_cast<u32*>(dev->d_fr_ext), (const ff::Fr*)ev, n);
+                           reinterpret_cast<u32*>(dev->d_fr_ext.p), (const ff::Fr*)ev, n);
         // fetched below, after the proof kernels are enqueued: a copy into pageable memory blocks this thread
     }
     // The cells (256 KiB per blob) go back on the second stream while the proof kernels run on the first: the copy
@@ -231,12 +230,12 @@ void cells_and_proofs(uint8_t* cells, KZGProof* proofs, const Blob* blobs, size_
         if (proofs) enqueue_cell_proofs(dev, n, st, fk20);
         if (side_copy) {
             CK_HIP(hipStreamWaitEvent(dev->stream2, dev->ev_cells, 0));
-            CK_HIP(hipMemcpyAsync(cells, dev->d_fr_ext, n * 2 * N * 32, hipMemcpyDeviceToHost, dev->stream2));
+            CK_HIP(hipMemcpyAsync(cells, dev->d_fr_ext.p, n * 2 * N * 32, hipMemcpyDeviceToHost, dev->stream2));
         } else if (cells) {
-            CK_HIP(hipMemcpyAsync(cells, dev->d_fr_ext, n * 2 * N * 32, hipMemcpyDeviceToHost, st));
+            CK_HIP(hipMemcpyAsync(cells, dev->d_fr_ext.p, n * 2 * N * 32, hipMemcpyDeviceToHost, st));
         }
-        if (proofs) CK_HIP(hipMemcpyAsync(proofs, dev->d_proofs, n * 128 * 48, hipMemcpyDeviceToHost, st));
-        CK_HIP(hipMemcpyAsync(status.data(), dev->d_status, n * sizeof(int), hipMemcpyDeviceToHost, st));
+        if (proofs) CK_HIP(hipMemcpyAsync(proofs, dev->d_proofs.p, n * 128 * 48, hipMemcpyDeviceToHost, st));
+        CK_HIP(hipMemcpyAsync(status.data(), dev->d_status.p, n * sizeof(int), hipMemcpyDeviceToHost, st));
     } catch (...) {
         // a copy into the caller's `cells` / `proofs` (or into `status`) may be in flight on either stream: nothing of it
         // may outlive this call
@@ -428,7 +427,7 @@ bool cells_to_limbs(std::vector<ff::Fr>& out, const Cell* cells, size_t ncells) 
     return ok;
 }
 
-// decode `np` compressed G1 points on the GPU (stream2): AffPt slots in dev->d_vpts, per-point status in dev->d_vstat
+// decode `np` compressed G1 points on the GPU (stream2): AffPt slots in dev->d_vpts.p, per-point status in dev->d_vstat.p
 // (0 ok, 1 not an encoding of a curve point, 2 on the curve but outside G1).  Caller holds dev->vmu.
 // `tail` (optional): `ntail` slots decoded and checked by an earlier call, appended behind the np decoded ones (status 0)
 void decode_points_begin(KzgAmdSettings* dev, const std::vector<uint8_t>& bytes, size_t np, const AffPt* tail = nullptr,
@@ -439,12 +438,12 @@ void decode_points_begin(KzgAmdSettings* dev, const std::vector<uint8_t>& bytes,
     dev->ensure_verify(np + ntail);
     dev->vstage = bytes;
     hipStream_t st = dev->stream2;
-    CK_HIP(hipMemcpyAsync(dev->d_vbytes, dev->vstage.data(), np * 48, hipMemcpyHostToDevice, st));
-    CK_HIP(hipMemsetAsync(dev->d_vstat, 0, (np + ntail) * sizeof(int), st));
-    CK_HIP(hipMemsetAsync(dev->d_vpts, 0, np * sizeof(AffPt), st));
-    if (ntail) CK_HIP(hipMemcpyAsync(dev->d_vpts + np, tail, ntail * sizeof(AffPt), hipMemcpyDeviceToDevice, st));
+    CK_HIP(hipMemcpyAsync(dev->d_vbytes.p, dev->vstage.data(), np * 48, hipMemcpyHostToDevice, st));
+    CK_HIP(hipMemsetAsync(dev->d_vstat.p, 0, (np + ntail) * sizeof(int), st));
+    CK_HIP(hipMemsetAsync(dev->d_vpts.p, 0, np * sizeof(AffPt), st));
+    if (ntail) CK_HIP(hipMemcpyAsync(dev->d_vpts.p + np, tail, ntail * sizeof(AffPt), hipMemcpyDeviceToDevice, st));
     if (!dev->ev_decoded) CK_HIP(hipEventCreateWithFlags(&dev->ev_decoded, hipEventDisableTiming));
-    decode_check_enqueue(dev->d_vpts, dev->d_vstat, (const unsigned char*)dev->d_vbytes, np, st, dev->cfg_wide_check, dev->ev_decoded);
+    decode_check_enqueue(dev->d_vpts.p, dev->d_vstat.p, (const unsigned char*)dev->d_vbytes.p, np, st, dev->cfg_wide_check, dev->ev_decoded);
     CK_HIP(hipGetLastError());
 }
 std::vector<int> decode_points_status(KzgAmdSettings* dev, size_t np) {
@@ -452,7 +451,7 @@ std::vector<int> decode_points_status(KzgAmdSettings* dev, size_t np) {
     kzgamd::DeviceGuard on_device(dev->device);
     CK_HIP(on_device.err);
     std::vector<int> stat(np);
-    CK_HIP(hipMemcpyAsync(stat.data(), dev->d_vstat, np * sizeof(int), hipMemcpyDeviceToHost, dev->stream2));
+    CK_HIP(hipMemcpyAsync(stat.data(), dev->d_vstat.p, np * sizeof(int), hipMemcpyDeviceToHost, dev->stream2));
     CK_HIP(hipStreamSynchronize(dev->stream2));
     return stat;
 }
@@ -522,13 +521,13 @@ void verify_cells(bool* ok, const Bytes48* commitments_bytes, const uint64_t* ce
         compress_on_host(dev->mono64_bytes.data(), cs->g1_values_monomial, CELL_SIZE);
     }
     // the 64 setup points are decoded and tested by the first call of a settings object and kept as slots (d_mono64)
-    const bool have_mono = dev->d_mono64 != nullptr;
+    const bool have_mono = dev->d_mono64.p != nullptr;
     const size_t ndec = have_mono ? n + m : np;
     std::vector<uint8_t> stage(ndec * 48);
     memcpy(stage.data(), proofs_bytes, n * 48);
     memcpy(stage.data() + n * 48, uniq.data(), m * 48);
     if (!have_mono) memcpy(stage.data() + (n + m) * 48, dev->mono64_bytes.data(), CELL_SIZE * 48);
-    decode_points_begin(dev, stage, ndec, dev->d_mono64, have_mono ? CELL_SIZE : 0);
+    decode_points_begin(dev, stage, ndec, dev->d_mono64.p, have_mono ? CELL_SIZE : 0);
     // host, meanwhile (the decode + subgroup tests are 0.75 ms of GPU latency): the cells' field elements, ...
     std::vector<ff::Fr> cf;
     if (!cells_to_limbs(cf, cells, n)) {
@@ -563,21 +562,18 @@ void verify_cells(bool* ok, const Bytes48* commitments_bytes, const uint64_t* ce
         CK_HIP(on_device.err);
         dev->ensure_recover(1);
         dev->ensure_vcells(n);
-        if (!dev->d_roots8192) {
-            CK_HIP(hipMalloc(&dev->d_roots8192, (2 * N + 1) * sizeof(ff::Fr)));
-            CK_HIP(hipMemcpy(dev->d_roots8192, cs->roots_of_unity, (2 * N + 1) * sizeof(ff::Fr), hipMemcpyHostToDevice));
-        }
+        ensure_roots8192(dev, cs);
         hipStream_t st = dev->stream;
-        CK_HIP(hipMemcpyAsync(dev->d_vc_cells, cf.data(), n * CELL_SIZE * 32, hipMemcpyHostToDevice, st));
-        CK_HIP(hipMemcpyAsync(dev->d_vc_cols, cols32.data(), cols32.size() * sizeof(u32), hipMemcpyHostToDevice, st));
-        CK_HIP(hipMemcpyAsync(dev->d_vc_pw, pws.data(), n * sizeof(ff::Fr), hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(k_vcell_agg, dim3((unsigned)(CELLS_PER_EXT_BLOB * CELL_SIZE / 256)), dim3(256), 0, st, dev->d_rec[0],
-                           (const u32*)dev->d_vc_cells, (const u32*)dev->d_vc_cols, (const ff::Fr*)dev->d_vc_pw);
-        if (kzgamd_ntt_fr_device(dev->ntt, dev->d_rec[1], dev->d_rec[0], CELL_SIZE, CELLS_PER_EXT_BLOB, 1, st) != 0)
+        CK_HIP(hipMemcpyAsync(dev->d_vc_cells.p, cf.data(), n * CELL_SIZE * 32, hipMemcpyHostToDevice, st));
+        CK_HIP(hipMemcpyAsync(dev->d_vc_cols.p, cols32.data(), cols32.size() * sizeof(u32), hipMemcpyHostToDevice, st));
+        CK_HIP(hipMemcpyAsync(dev->d_vc_pw.p, pws.data(), n * sizeof(ff::Fr), hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(k_vcell_agg, dim3((unsigned)(CELLS_PER_EXT_BLOB * CELL_SIZE / 256)), dim3(256), 0, st, dev->d_rec[0].p,
+                           (const u32*)dev->d_vc_cells.p, (const u32*)dev->d_vc_cols.p, (const ff::Fr*)dev->d_vc_pw.p);
+        if (kzgamd_ntt_fr_device(dev->ntt.get(), dev->d_rec[1].p, dev->d_rec[0].p, CELL_SIZE, CELLS_PER_EXT_BLOB, 1, st) != 0)
             throw CkErr{C_KZG_ERROR, "ntt"};
-        hipLaunchKernelGGL(k_vcell_interp, dim3((unsigned)CELL_SIZE), dim3((unsigned)CELLS_PER_EXT_BLOB), 0, st, dev->d_rec[2],
-                           (const ff::Fr*)dev->d_rec[1], (const ff::Fr*)dev->d_roots8192);
-        CK_HIP(hipMemcpyAsync(interp.data(), dev->d_rec[2], CELL_SIZE * sizeof(ff::Fr), hipMemcpyDeviceToHost, st));
+        hipLaunchKernelGGL(k_vcell_interp, dim3((unsigned)CELL_SIZE), dim3((unsigned)CELLS_PER_EXT_BLOB), 0, st, dev->d_rec[2].p,
+                           (const ff::Fr*)dev->d_rec[1].p, (const ff::Fr*)dev->d_roots8192.p);
+        CK_HIP(hipMemcpyAsync(interp.data(), dev->d_rec[2].p, CELL_SIZE * sizeof(ff::Fr), hipMemcpyDeviceToHost, st));
         CK_HIP(hipStreamSynchronize(st));
     }
     for (size_t k = 0; k < CELL_SIZE; ++k) interp[k] = ff::to_mont(interp[k]);  // the kernels work on canonical values
@@ -589,9 +585,9 @@ void verify_cells(bool* ok, const Bytes48* commitments_bytes, const uint64_t* ce
         kzgamd::DeviceGuard on_device(dev->device);
         CK_HIP(on_device.err);
         CK_HIP(hipEventSynchronize(dev->ev_decoded));
-        if (!dev->msm_verify) dev->msm_verify = kzgamd::msm_create(dev->d_vpts, np, true, false, true, kzgamd::G1_TRUSTED, &dev->opt);
-        else kzgamd::msm_reset_points(dev->msm_verify, dev->d_vpts, np);
-        kzgamd::msm_run_host(dev->msm_verify, out, sc.data(), np, 2);
+        if (!dev->msm_verify) dev->msm_verify.reset(kzgamd::msm_create(dev->d_vpts.p, np, true, false, true, kzgamd::G1_TRUSTED, &dev->opt));
+        else kzgamd::msm_reset_points(dev->msm_verify.get(), dev->d_vpts.p, np);
+        kzgamd::msm_run_host(dev->msm_verify.get(), out, sc.data(), np, 2);
     } catch (...) {
         (void)decode_points_status(dev, np);  // nothing of this call stays in flight
         throw;
@@ -607,10 +603,9 @@ void verify_cells(bool* ok, const Bytes48* commitments_bytes, const uint64_t* ce
             std::lock_guard<std::mutex> lk(dev->mu);
             kzgamd::DeviceGuard on_device(dev->device);
             CK_HIP(on_device.err);
-            AffPt* keep = nullptr;
-            CK_HIP(hipMalloc(&keep, CELL_SIZE * sizeof(AffPt)));
-            if (hipMemcpy(keep, dev->d_vpts + n + m, CELL_SIZE * sizeof(AffPt), hipMemcpyDeviceToDevice) == hipSuccess) dev->d_mono64 = keep;
-            else (void)hipFree(keep);
+            DevArray<AffPt> keep;
+            CK_HIP(keep.try_ensure(CELL_SIZE));
+            if (hipMemcpy(keep.p, dev->d_vpts.p + n + m, CELL_SIZE * sizeof(AffPt), hipMemcpyDeviceToDevice) == hipSuccess) dev->d_mono64 = std::move(keep);
         }
     }
     blst_p2 g2gen, g2s64;
@@ -660,19 +655,19 @@ void recover_cells(Cell* recovered_cells, KZGProof* recovered_proofs, const uint
     dev->ensure_recover(1);
     hipStream_t st = dev->stream;
     const size_t E = 2 * N;
-    ff::Fr *A = dev->d_rec[0], *B = dev->d_rec[1], *C = dev->d_rec[2], *D = dev->d_rec[3];
+    ff::Fr *A = dev->d_rec[0].p, *B = dev->d_rec[1].p, *C = dev->d_rec[2].p, *D = dev->d_rec[3].p;
     auto ntt = [&](ff::Fr* out, const ff::Fr* in, int inverse) {
-        if (kzgamd_ntt_fr_device(dev->ntt, out, in, E, 1, inverse, st) != 0) throw CkErr{C_KZG_ERROR, "ntt"};
+        if (kzgamd_ntt_fr_device(dev->ntt.get(), out, in, E, 1, inverse, st) != 0) throw CkErr{C_KZG_ERROR, "ntt"};
     };
     auto mul = [&](ff::Fr* out, const ff::Fr* a, const ff::Fr* b) {
         hipLaunchKernelGGL(k_fr_mul, dim3((unsigned)(E / 256)), dim3(256), 0, st, out, a, b, E);
     };
     // the provided evaluations in bit-reversed order, missing ones zero
     CK_HIP(hipMemsetAsync(A, 0, E * sizeof(ff::Fr), st));
-    CK_HIP(hipMemcpyAsync(dev->d_rec_in, cf.data(), ncells * CELL_SIZE * 32, hipMemcpyHostToDevice, st));
-    CK_HIP(hipMemcpyAsync(dev->d_rec_idx, idx32.data(), ncells * sizeof(u32), hipMemcpyHostToDevice, st));
+    CK_HIP(hipMemcpyAsync(dev->d_rec_in.p, cf.data(), ncells * CELL_SIZE * 32, hipMemcpyHostToDevice, st));
+    CK_HIP(hipMemcpyAsync(dev->d_rec_idx.p, idx32.data(), ncells * sizeof(u32), hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(k_rec_scatter, dim3((unsigned)((ncells * CELL_SIZE + 255) / 256)), dim3(256), 0, st, A,
-                       (const u32*)dev->d_rec_in, (const u32*)dev->d_rec_idx, ncells, ncells != CELLS_PER_EXT_BLOB);
+                       (const u32*)dev->d_rec_in.p, (const u32*)dev->d_rec_idx.p, ncells, ncells != CELLS_PER_EXT_BLOB);
     std::vector<ff::Fr> vanishing;  // must outlive the copy below
     if (ncells != CELLS_PER_EXT_BLOB) {
         // vanishing_polynomial_for_missing_cells (:520-551): roots w^(64 * brp7(i)) for the missing cells i, short
@@ -687,33 +682,30 @@ void recover_cells(Cell* recovered_cells, KZGProof* recovered_proofs, const uint
         ntt(C, B, 0);                      // vanishing_poly_eval
         mul(A, A, C);                      // extended_evaluation_times_zero
         ntt(D, A, 1);                      // ..._coeffs
-        mul(D, D, dev->d_pow7);            // coset_fft: shift_poly by 7, then the transform
+        mul(D, D, dev->d_pow7.p);            // coset_fft: shift_poly by 7, then the transform
         ntt(A, D, 0);                      // extended_evaluations_over_coset
-        mul(B, B, dev->d_pow7);
+        mul(B, B, dev->d_pow7.p);
         ntt(C, B, 0);                      // vanishing_poly_over_coset
         hipLaunchKernelGGL(k_fr_inverse, dim3((unsigned)(E / 64)), dim3(64), 0, st, C, E);
         mul(A, A, C);
         ntt(D, A, 1);                      // coset_ifft: the transform, then shift_poly by 1/7
-        mul(D, D, dev->d_pow7inv);         // reconstructed_poly_coeff
+        mul(D, D, dev->d_pow7inv.p);         // reconstructed_poly_coeff
         ntt(A, D, 0);                      // its 8192 evaluations, natural order
-        hipLaunchKernelGGL(k_cells_out, dim3((unsigned)(E / 256)), dim3(256), 0, st, reinterpret_cast<u32*>(dev->d_fr_ext),
+        hipLaunchKernelGGL(k_cells_out, dim3((unsigned)(E / 256)), dim3(256), 0, st, reinterpret_cast<u32*>(dev->d_fr_ext.p),
                            (const ff::Fr*)A, (size_t)1);
-        CK_HIP(hipMemcpyAsync(recovered_cells, dev->d_fr_ext, E * 32, hipMemcpyDeviceToHost, st));
+        CK_HIP(hipMemcpyAsync(recovered_cells, dev->d_fr_ext.p, E * 32, hipMemcpyDeviceToHost, st));
     } else {
         memcpy(recovered_cells, cells, E * 32);
         if (recovered_proofs) ntt(D, A, 1);  // poly_lagrange_to_monomial of the given cells (:186-188)
     }
     if (recovered_proofs) {
         // compute_fk20_proofs reads the first 4096 coefficients (:190-200, toeplitz_coeffs_stride :659-688)
-        if (!dev->d_roots8192) {
-            CK_HIP(hipMalloc(&dev->d_roots8192, (2 * N + 1) * sizeof(ff::Fr)));
-            CK_HIP(hipMemcpy(dev->d_roots8192, cs->roots_of_unity, (2 * N + 1) * sizeof(ff::Fr), hipMemcpyHostToDevice));
-        }
-        if (!dev->msm_monomial) dev->msm_monomial = kzgamd::msm_create(dev->d_monomial, N, true, true, true, kzgamd::G1_TRUSTED, &dev->opt);
+        ensure_roots8192(dev, cs);
+        if (!dev->msm_monomial) dev->msm_monomial.reset(kzgamd::msm_create(dev->d_monomial.p, N, true, true, true, kzgamd::G1_TRUSTED, &dev->opt));
         dev->ensure_q(1);
-        CK_HIP(hipMemcpyAsync(dev->d_fr_b, D, N * sizeof(ff::Fr), hipMemcpyDeviceToDevice, st));
+        CK_HIP(hipMemcpyAsync(dev->d_fr_b.p, D, N * sizeof(ff::Fr), hipMemcpyDeviceToDevice, st));
         enqueue_cell_proofs(dev, 1, st, false);
-        CK_HIP(hipMemcpyAsync(recovered_proofs, dev->d_proofs, CELLS_PER_EXT_BLOB * 48, hipMemcpyDeviceToHost, st));
+        CK_HIP(hipMemcpyAsync(recovered_proofs, dev->d_proofs.p, CELLS_PER_EXT_BLOB * 48, hipMemcpyDeviceToHost, st));
     }
     CK_HIP(hipStreamSynchronize(st));
 }
@@ -781,44 +773,44 @@ void recover_cells_batch(Cell* recovered_cells, KZGProof* recovered_proofs, cons
     const bool side_copy = recovered_proofs && dev->stream2 && dev->stream2 != st;
     if (side_copy && !dev->ev_cells) CK_HIP(hipEventCreateWithFlags(&dev->ev_cells, hipEventDisableTiming));
     const size_t E = 2 * N;
-    ff::Fr *A = dev->d_rec[0], *D = dev->d_rec[1], *Zs = dev->d_rec[2], *Zc = dev->d_rec[3];
-    const RecBlob* d_info = reinterpret_cast<const RecBlob*>(dev->d_rec_info);
+    ff::Fr *A = dev->d_rec[0].p, *D = dev->d_rec[1].p, *Zs = dev->d_rec[2].p, *Zc = dev->d_rec[3].p;
+    const RecBlob* d_info = reinterpret_cast<const RecBlob*>(dev->d_rec_info.p);
     for (size_t s0 = 0; s0 < n; s0 += per) {
         const size_t m = std::min(per, n - s0), c0 = first[s0], ncells = first[s0 + m] - c0;
         std::vector<RecBlob> sinfo(info.begin() + s0, info.begin() + s0 + m);
         for (size_t b = 0; b < m; ++b) sinfo[b].first = (u32)(first[s0 + b] - c0);
         const unsigned grid = (unsigned)(m * E / 256);
         auto ntt = [&](ff::Fr* out, const ff::Fr* in, int inverse) {
-            if (kzgamd_ntt_fr_device(dev->ntt, out, in, E, m, inverse, st) != 0) throw CkErr{C_KZG_ERROR, "ntt"};
+            if (kzgamd_ntt_fr_device(dev->ntt.get(), out, in, E, m, inverse, st) != 0) throw CkErr{C_KZG_ERROR, "ntt"};
         };
         try {
-            CK_HIP(hipMemcpyAsync(dev->d_rec_info, sinfo.data(), m * sizeof(RecBlob), hipMemcpyHostToDevice, st));
-            CK_HIP(hipMemcpyAsync(dev->d_rec_in, cells + c0, ncells * BYTES_PER_CELL, hipMemcpyHostToDevice, st));
+            CK_HIP(hipMemcpyAsync(dev->d_rec_info.p, sinfo.data(), m * sizeof(RecBlob), hipMemcpyHostToDevice, st));
+            CK_HIP(hipMemcpyAsync(dev->d_rec_in.p, cells + c0, ncells * BYTES_PER_CELL, hipMemcpyHostToDevice, st));
             hipLaunchKernelGGL(k_rec_vanishing, dim3((unsigned)(m * 128 / 64)), dim3(64), 0, st, Zs, Zc, d_info,
-                               (const ff::Fr*)dev->d_roots8192, seven64, m);
-            hipLaunchKernelGGL(k_rec_scatter_batch, dim3(grid), dim3(256), 0, st, A, (const u32*)dev->d_rec_in, d_info,
+                               (const ff::Fr*)dev->d_roots8192.p, seven64, m);
+            hipLaunchKernelGGL(k_rec_scatter_batch, dim3(grid), dim3(256), 0, st, A, (const u32*)dev->d_rec_in.p, d_info,
                                (const ff::Fr*)Zs, nul, m);
             ntt(D, A, 1);                                                                     // extended_evaluation_times_zero_coeffs
-            hipLaunchKernelGGL(k_rec_mul_pow, dim3(grid), dim3(256), 0, st, D, (const ff::Fr*)dev->d_pow7, (ff::Fr*)nullptr, m);
+            hipLaunchKernelGGL(k_rec_mul_pow, dim3(grid), dim3(256), 0, st, D, (const ff::Fr*)dev->d_pow7.p, (ff::Fr*)nullptr, m);
             ntt(A, D, 0);                                                                     // ... over the coset
             hipLaunchKernelGGL(k_rec_mul_periodic, dim3(grid), dim3(256), 0, st, A, (const ff::Fr*)Zc, m);
             ntt(D, A, 1);                                                                     // coset_ifft
-            hipLaunchKernelGGL(k_rec_mul_pow, dim3(grid), dim3(256), 0, st, D, (const ff::Fr*)dev->d_pow7inv,
-                               recovered_proofs ? dev->d_fr_b : (ff::Fr*)nullptr, m);          // reconstructed_poly_coeff
+            hipLaunchKernelGGL(k_rec_mul_pow, dim3(grid), dim3(256), 0, st, D, (const ff::Fr*)dev->d_pow7inv.p,
+                               recovered_proofs ? dev->d_fr_b.p : (ff::Fr*)nullptr, m);          // reconstructed_poly_coeff
             ntt(A, D, 0);                                                                     // its evaluations, natural order
-            hipLaunchKernelGGL(k_cells_out, dim3(grid), dim3(256), 0, st, reinterpret_cast<u32*>(dev->d_fr_ext), (const ff::Fr*)A, m);
+            hipLaunchKernelGGL(k_cells_out, dim3(grid), dim3(256), 0, st, reinterpret_cast<u32*>(dev->d_fr_ext.p), (const ff::Fr*)A, m);
             CK_HIP(hipGetLastError());
             uint8_t* out_cells = recovered_cells[s0 * CELLS_PER_EXT_BLOB].bytes;
             if (side_copy) CK_HIP(hipEventRecord(dev->ev_cells, st));
             if (recovered_proofs) enqueue_cell_proofs(dev, m, st, fk20);
             if (side_copy) {
                 CK_HIP(hipStreamWaitEvent(dev->stream2, dev->ev_cells, 0));
-                CK_HIP(hipMemcpyAsync(out_cells, dev->d_fr_ext, m * E * 32, hipMemcpyDeviceToHost, dev->stream2));
+                CK_HIP(hipMemcpyAsync(out_cells, dev->d_fr_ext.p, m * E * 32, hipMemcpyDeviceToHost, dev->stream2));
             } else {
-                CK_HIP(hipMemcpyAsync(out_cells, dev->d_fr_ext, m * E * 32, hipMemcpyDeviceToHost, st));
+                CK_HIP(hipMemcpyAsync(out_cells, dev->d_fr_ext.p, m * E * 32, hipMemcpyDeviceToHost, st));
             }
             if (recovered_proofs)
-                CK_HIP(hipMemcpyAsync(recovered_proofs + s0 * CELLS_PER_EXT_BLOB, dev->d_proofs, m * CELLS_PER_EXT_BLOB * 48,
+                CK_HIP(hipMemcpyAsync(recovered_proofs + s0 * CELLS_PER_EXT_BLOB, dev->d_proofs.p, m * CELLS_PER_EXT_BLOB * 48,
                                       hipMemcpyDeviceToHost, st));
         } catch (...) {
             // a copy into the caller's buffers may be in flight on either stream: nothing of it may outlive this call

@@ -23,6 +23,7 @@
 #include "fr29.hip.h"
 #include "g1_io.hip.h"
 #include "g1w.hip.h"
+#include "host_call.h"
 #include "host_g1.h"
 #include "host_pairing.h"
 #include "msm_internal.h"
@@ -38,6 +39,18 @@
 using ff::u32;
 using ff::u64;
 using g1::AffPt;
+using kzgamd::DevArray;
+using kzgamd::drop_all;
+
+// the engine handles a settings object owns
+struct MsmDeleter {
+    void operator()(kzgamd::MsmContext* m) const { kzgamd::msm_destroy(m); }
+};
+struct NttDeleter {
+    void operator()(void* n) const { kzgamd_ntt_free(n); }
+};
+using MsmPtr = std::unique_ptr<kzgamd::MsmContext, MsmDeleter>;
+using NttPtr = std::unique_ptr<void, NttDeleter>;
 
 
 // ---- errors (thrown across the three translation units, caught by guarded())
@@ -167,42 +180,31 @@ struct CommitReq;  // ckzg.hip: the requests of the coalesced single-blob entry 
 struct ProofReq;
 struct KzgAmdSettings {
     int device = 0;
-    kzgamd::MsmContext* msm = nullptr;  // prepared over g1_lagrange_brp
+    MsmPtr msm_owned;                   // prepared over g1_lagrange_brp: the root's
+    kzgamd::MsmContext* msm = nullptr;  // ... as every object reads it (a lane: its parent's)
     hipStream_t stream = nullptr;
     hipStream_t stream2 = nullptr;  // commitment validation runs beside the proving pipeline
     // EIP-7594 state, built on first use
-    AffPt* d_monomial = nullptr;              // g1_values_monomial as table slots
-    kzgamd::MsmContext* msm_monomial = nullptr;
-    kzgamd::MsmContext* msm_xext = nullptr;  // FK20: the 128 columns of 64 points of x_ext_fft_columns, one wide table
-    ff::Fr *d_fk_a = nullptr, *d_fk_b = nullptr;  // FK20: n x 64 x 128 Toeplitz vectors / their transforms
-    g1::Xyzz *d_fk_h = nullptr, *d_fk_h2 = nullptr;  // FK20: n x 128 points, and the transform scratch
-    size_t cap_fk = 0, cap_q = 0;
+    DevArray<AffPt> d_monomial;               // g1_values_monomial as table slots
+    MsmPtr msm_monomial;
+    MsmPtr msm_xext;  // FK20: the 128 columns of 64 points of x_ext_fft_columns, one wide table
+    DevArray<ff::Fr> d_fk_a, d_fk_b;  // FK20: n x 64 x 128 Toeplitz vectors / their transforms
+    DevArray<g1::Xyzz> d_fk_h, d_fk_h2;  // FK20: n x 128 points, and the transform scratch
+    // Every ensure_* below releases its whole group before it allocates any of it: a settings object sits beside a
+    // 137 GB table, and growing the members one at a time would raise the peak by the old size of the rest.
+    size_t cap_fk = 0;
     void ensure_fk20(size_t nblobs) {
         if (nblobs <= cap_fk) return;
-        release_fk20();
-        CK_HIP(hipMalloc(&d_fk_a, nblobs * 8192 * sizeof(ff::Fr)));
-        CK_HIP(hipMalloc(&d_fk_b, nblobs * 8192 * sizeof(ff::Fr)));
-        CK_HIP(hipMalloc(&d_fk_h, nblobs * 128 * sizeof(g1::Xyzz)));
-        CK_HIP(hipMalloc(&d_fk_h2, nblobs * 128 * sizeof(g1::Xyzz)));
+        cap_fk = 0;
+        drop_all(d_fk_a, d_fk_b, d_fk_h, d_fk_h2);
+        CK_HIP(d_fk_a.try_ensure(nblobs * 8192));
+        CK_HIP(d_fk_b.try_ensure(nblobs * 8192));
+        CK_HIP(d_fk_h.try_ensure(nblobs * 128));
+        CK_HIP(d_fk_h2.try_ensure(nblobs * 128));
         cap_fk = nblobs;
     }
-    void release_fk20() {
-        if (d_fk_a) (void)hipFree(d_fk_a);
-        if (d_fk_b) (void)hipFree(d_fk_b);
-        if (d_fk_h) (void)hipFree(d_fk_h);
-        if (d_fk_h2) (void)hipFree(d_fk_h2);
-        d_fk_a = d_fk_b = nullptr;
-        d_fk_h = d_fk_h2 = nullptr;
-        cap_fk = 0;
-    }
-    void ensure_q(size_t nblobs) {  // the 128 quotient vectors per blob of the direct cell-proof path (16 MB per blob)
-        if (nblobs <= cap_q) return;
-        if (d_q) (void)hipFree(d_q);
-        d_q = nullptr;
-        cap_q = 0;
-        CK_HIP(hipMalloc(&d_q, nblobs * 128 * N * 32));
-        cap_q = nblobs;
-    }
+    // the 128 quotient vectors per blob of the direct cell-proof path (16 MB per blob)
+    void ensure_q(size_t nblobs) { CK_HIP(d_q.try_ensure(nblobs * 128 * N * 8)); }
     // Lanes: the reference's callers share one settings object between rayon workers (kzg/src/eip_4844.rs:781-805).
     // A host-buffer call of a few blobs takes the first idle lane — a settings object of its own for everything a call
     // mutates (streams, staging buffers, mutex) that BORROWS the tables and engine handles of its parent — so that up to
@@ -249,7 +251,6 @@ struct KzgAmdSettings {
         cfg_commit_chunk = (size_t)o.t[T_COMMIT_CHUNK];
         cfg_fk20 = (int)o.t[T_FK20];
     }
-    bool is_lane = false;
     std::atomic<bool> busy{false};
     // page-locked staging for calls of up to LANE_MAX_BLOBS blobs: copies to and from it are truly asynchronous (a
     // copy from / to the caller's pageable memory goes through the runtime's own staging path, which serialises
@@ -270,25 +271,25 @@ struct KzgAmdSettings {
     std::mutex lanes_mu;
     std::vector<std::unique_ptr<KzgAmdSettings>> lanes;
     std::atomic<unsigned> lane_rr{0};
-    void* ntt = nullptr;                      // kzgamd_ntt_new(13)
-    ff::Fr* d_roots8192 = nullptr;            // roots_of_unity[0..=8192], Montgomery
-    ff::Fr *d_fr_a = nullptr, *d_fr_b = nullptr, *d_fr_ext = nullptr;  // 4096, 4096, 8192 per blob
-    u32* d_cells = nullptr;
-    u32* d_q = nullptr;                       // 128 x 4096 x 8 per blob
-    unsigned char* d_proofs = nullptr;
+    NttPtr ntt;                               // kzgamd_ntt_new(13)
+    DevArray<ff::Fr> d_roots8192;             // roots_of_unity[0..=8192], Montgomery
+    DevArray<ff::Fr> d_fr_a, d_fr_b, d_fr_ext;  // 4096, 4096, 8192 per blob
+    DevArray<u32> d_cells;
+    DevArray<u32> d_q;                        // 128 x 4096 x 8 per blob
+    DevArray<unsigned char> d_proofs;
     size_t cap_cells = 0;
-    int* d_cstatus = nullptr;
-    AffPt* d_cpts = nullptr;  // decoded commitments of a proof batch of <= WIDE_COMMIT_CHECK_MAX blobs (wide check)
+    DevArray<int> d_cstatus;
+    DevArray<AffPt> d_cpts;  // decoded commitments of a proof batch of <= WIDE_COMMIT_CHECK_MAX blobs (wide check)
     std::mutex mu;
     // staging for the host-buffer entry points
-    unsigned char* d_blobs = nullptr;
-    u32* d_scalars = nullptr;
-    int* d_status = nullptr;
-    unsigned char* d_out = nullptr;
-    u32* d_z = nullptr;              // n x 32 B big-endian evaluation points
-    u32* d_y = nullptr;              // n x 8 u32 canonical y
-    unsigned char* d_commit = nullptr;  // n x 48 B
-    unsigned char* d_qscratch = nullptr;  // k_quotient_a/b scratch for up to QSPLIT_MAX blobs
+    DevArray<unsigned char> d_blobs;
+    DevArray<u32> d_scalars;
+    DevArray<int> d_status;
+    DevArray<unsigned char> d_out;
+    DevArray<u32> d_z;               // n x 32 B big-endian evaluation points
+    DevArray<u32> d_y;               // n x 8 u32 canonical y
+    DevArray<unsigned char> d_commit;   // n x 48 B
+    DevArray<unsigned char> d_qscratch;   // k_quotient_a/b scratch for up to QSPLIT_MAX blobs
     size_t cap_blobs = 0;
     std::unique_ptr<WorkerPool> pool;  // created by the first batched proof call
     // extra streams for the chunk pipeline of large proof batches (created on first use); chunk k runs on
@@ -302,25 +303,20 @@ struct KzgAmdSettings {
     // between calls (a fresh handle per call cost 1.7 ms of stream / allocation / free round trips)
     std::mutex vmu;                 // one batched verification at a time per settings object (its staging buffers)
     std::vector<uint8_t> vstage;    // host staging of the 2n + 1 compressed points (must outlive the async copy)
-    unsigned char* d_vbytes = nullptr;
-    AffPt* d_vpts = nullptr;
-    int* d_vstat = nullptr;
+    DevArray<unsigned char> d_vbytes;
+    DevArray<AffPt> d_vpts;
+    DevArray<int> d_vstat;
     hipEvent_t ev_decoded = nullptr;  // the points of a verification call are decoded (their membership test may still run)
     size_t vcap = 0;
-    kzgamd::MsmContext* msm_verify = nullptr;
+    MsmPtr msm_verify;
     void ensure_verify(size_t np) {
         if (np <= vcap) return;
-        if (d_vbytes) (void)hipFree(d_vbytes);
-        if (d_vpts) (void)hipFree(d_vpts);
-        if (d_vstat) (void)hipFree(d_vstat);
-        d_vbytes = nullptr;
-        d_vpts = nullptr;
-        d_vstat = nullptr;
         vcap = 0;
+        drop_all(d_vbytes, d_vpts, d_vstat);
         const size_t cap = np < 257 ? 257 : np;
-        CK_HIP(hipMalloc(&d_vbytes, cap * 48));
-        CK_HIP(hipMalloc(&d_vpts, cap * sizeof(AffPt)));
-        CK_HIP(hipMalloc(&d_vstat, cap * sizeof(int)));
+        CK_HIP(d_vbytes.try_ensure(cap * 48));
+        CK_HIP(d_vpts.try_ensure(cap));
+        CK_HIP(d_vstat.try_ensure(cap));
         vcap = cap;
     }
     hipStream_t pipe_stream(size_t k) {
@@ -343,75 +339,60 @@ struct KzgAmdSettings {
     }
     // EIP-7594 cell verification / recovery state, built on first use
     std::vector<uint8_t> mono64_bytes;  // g1_values_monomial[0..64) compressed (the interpolation-polynomial commitment)
-    AffPt* d_mono64 = nullptr;          // ... decoded and subgroup-checked once, as MSM slots
-    ff::Fr* d_rec[4] = {nullptr, nullptr, nullptr, nullptr};  // recovery: four vectors of 8192 field elements per blob
-    u32* d_rec_in = nullptr;         // up to 128 cells per blob (the single call: canonical limbs; a batch: the bytes as given)
-    u32* d_rec_idx = nullptr;        // the single call's cell indices (128)
-    u32* d_rec_info = nullptr;       // a batch: 8 words per blob (ckzg_7594.hip, RecBlob)
+    DevArray<AffPt> d_mono64;           // ... decoded and subgroup-checked once, as MSM slots
+    DevArray<ff::Fr> d_rec[4];       // recovery: four vectors of 8192 field elements per blob
+    DevArray<u32> d_rec_in;          // up to 128 cells per blob (the single call: canonical limbs; a batch: the bytes as given)
+    DevArray<u32> d_rec_idx;         // the single call's cell indices (128)
+    DevArray<u32> d_rec_info;        // a batch: 8 words per blob (ckzg_7594.hip, RecBlob)
     size_t cap_rec = 0;              // blobs d_rec / d_rec_in / d_rec_info hold
-    ff::Fr* d_pow7 = nullptr;        // 7^i and 7^-i, i < 8192 (coset shifts, das.rs:463-491)
-    ff::Fr* d_pow7inv = nullptr;
+    DevArray<ff::Fr> d_pow7;         // 7^i and 7^-i, i < 8192 (coset shifts, das.rs:463-491)
+    DevArray<ff::Fr> d_pow7inv;
     bool fk20_unavailable = false;   // the FK20 table could not be built (no HBM left): batches use the direct form
     // verify_cell_kzg_proof_batch: the cells (canonical limbs), their columns and the powers of r, for k_vcell_agg
-    u32* d_vc_cells = nullptr;
-    u32* d_vc_cols = nullptr;
-    ff::Fr* d_vc_pw = nullptr;
+    DevArray<u32> d_vc_cells;
+    DevArray<u32> d_vc_cols;
+    DevArray<ff::Fr> d_vc_pw;
     size_t cap_vc = 0;
     void ensure_vcells(size_t n) {
         if (n <= cap_vc) return;
-        if (d_vc_cells) (void)hipFree(d_vc_cells);
-        if (d_vc_cols) (void)hipFree(d_vc_cols);
-        if (d_vc_pw) (void)hipFree(d_vc_pw);
-        d_vc_cells = d_vc_cols = nullptr;
-        d_vc_pw = nullptr;
         cap_vc = 0;
+        drop_all(d_vc_cells, d_vc_cols, d_vc_pw);
         const size_t cap = n < 128 ? 128 : n;
-        CK_HIP(hipMalloc(&d_vc_cells, cap * CELL_SIZE * 32));
-        CK_HIP(hipMalloc(&d_vc_cols, (cap + 2 * CELLS_PER_BLOB + 1) * sizeof(u32)));
-        CK_HIP(hipMalloc(&d_vc_pw, cap * sizeof(ff::Fr)));
+        CK_HIP(d_vc_cells.try_ensure(cap * CELL_SIZE * 8));
+        CK_HIP(d_vc_cols.try_ensure(cap + 2 * CELLS_PER_BLOB + 1));
+        CK_HIP(d_vc_pw.try_ensure(cap));
         cap_vc = cap;
     }
     // kzgamd_verify_cell_kzg_proof_batch_many (ckzg_vcells.hip): the cells as the caller passed them, the weights
     // rho^b r_b^i, the tables of k_vcells_agg / k_vcells_fold ([129 partial-row starts | 2 words per slice | the cells
     // grouped by column]), one partial row of 64 sums per slice, and the "an element is >= r" word
     static constexpr size_t VCELLS_SLICE = 8;  // cells per wave of k_vcells_agg (kzgamd_vcells_info)
-    unsigned char* d_vm_cells = nullptr;
-    ff::Fr* d_vm_w = nullptr;
-    u32* d_vm_tab = nullptr;
-    ff::Fr* d_vm_part = nullptr;
-    int* d_vm_status = nullptr;
+    DevArray<unsigned char> d_vm_cells;
+    DevArray<ff::Fr> d_vm_w;
+    DevArray<u32> d_vm_tab;
+    DevArray<ff::Fr> d_vm_part;
+    DevArray<int> d_vm_status;
     size_t cap_vm = 0;
     double vm_ms[8] = {};  // host wall time of the stages of the last such call (kzgamd_vcells_timing)
     static size_t vcells_many_slices(size_t n) { return n / VCELLS_SLICE + 2 * CELLS_PER_BLOB; }  // at most, for n cells
-    void release_vcells_many() {
-        if (d_vm_cells) (void)hipFree(d_vm_cells);
-        if (d_vm_w) (void)hipFree(d_vm_w);
-        if (d_vm_tab) (void)hipFree(d_vm_tab);
-        if (d_vm_part) (void)hipFree(d_vm_part);
-        if (d_vm_status) (void)hipFree(d_vm_status);
-        d_vm_cells = nullptr;
-        d_vm_w = d_vm_part = nullptr;
-        d_vm_tab = nullptr;
-        d_vm_status = nullptr;
-        cap_vm = 0;
-    }
     void ensure_vcells_many(size_t n) {
         if (n <= cap_vm) return;
-        release_vcells_many();
+        cap_vm = 0;
+        drop_all(d_vm_cells, d_vm_w, d_vm_tab, d_vm_part, d_vm_status);
         const size_t cap = n < 128 ? 128 : n, ns = vcells_many_slices(cap);
-        CK_HIP(hipMalloc(&d_vm_cells, cap * CELL_SIZE * 32));
-        CK_HIP(hipMalloc(&d_vm_w, cap * sizeof(ff::Fr)));
-        CK_HIP(hipMalloc(&d_vm_tab, (2 * CELLS_PER_BLOB + 1 + 2 * ns + cap) * sizeof(u32)));
-        CK_HIP(hipMalloc(&d_vm_part, ns * CELL_SIZE * sizeof(ff::Fr)));
-        CK_HIP(hipMalloc(&d_vm_status, sizeof(int)));
+        CK_HIP(d_vm_cells.try_ensure(cap * CELL_SIZE * 32));
+        CK_HIP(d_vm_w.try_ensure(cap));
+        CK_HIP(d_vm_tab.try_ensure(2 * CELLS_PER_BLOB + 1 + 2 * ns + cap));
+        CK_HIP(d_vm_part.try_ensure(ns * CELL_SIZE));
+        CK_HIP(d_vm_status.try_ensure(1));
         cap_vm = cap;
     }
     // the coset tables and the single call's index buffer once; the per-blob buffers for nblobs blobs (kept, grown on demand)
     void ensure_recover(size_t nblobs) {
-        if (!d_pow7inv) {
-            if (!d_rec_idx) CK_HIP(hipMalloc(&d_rec_idx, 128 * sizeof(u32)));
-            if (!d_pow7) CK_HIP(hipMalloc(&d_pow7, 2 * N * sizeof(ff::Fr)));
-            CK_HIP(hipMalloc(&d_pow7inv, 2 * N * sizeof(ff::Fr)));
+        if (!d_pow7inv.p) {
+            CK_HIP(d_rec_idx.try_ensure(128));
+            CK_HIP(d_pow7.try_ensure(2 * N));
+            CK_HIP(d_pow7inv.try_ensure(2 * N));
             std::vector<ff::Fr> p(2 * N), q(2 * N);
             ff::Fr seven = ff::Fr::zero();
             seven.v[0] = 7;
@@ -422,136 +403,61 @@ struct KzgAmdSettings {
                 p[i] = ff::mul(p[i - 1], seven);
                 q[i] = ff::mul(q[i - 1], inv7);
             }
-            CK_HIP(hipMemcpy(d_pow7, p.data(), p.size() * sizeof(ff::Fr), hipMemcpyHostToDevice));
-            CK_HIP(hipMemcpy(d_pow7inv, q.data(), q.size() * sizeof(ff::Fr), hipMemcpyHostToDevice));
+            CK_HIP(hipMemcpy(d_pow7.p, p.data(), p.size() * sizeof(ff::Fr), hipMemcpyHostToDevice));
+            CK_HIP(hipMemcpy(d_pow7inv.p, q.data(), q.size() * sizeof(ff::Fr), hipMemcpyHostToDevice));
         }
         if (nblobs <= cap_rec) return;
-        release_recover();
-        for (int k = 0; k < 4; ++k) CK_HIP(hipMalloc(&d_rec[k], nblobs * 2 * N * sizeof(ff::Fr)));
-        CK_HIP(hipMalloc(&d_rec_in, nblobs * 2 * N * 32));
-        CK_HIP(hipMalloc(&d_rec_info, nblobs * 8 * sizeof(u32)));
-        cap_rec = nblobs;
-    }
-    void release_recover() {
-        for (int k = 0; k < 4; ++k) {
-            if (d_rec[k]) (void)hipFree(d_rec[k]);
-            d_rec[k] = nullptr;
-        }
-        if (d_rec_in) (void)hipFree(d_rec_in);
-        if (d_rec_info) (void)hipFree(d_rec_info);
-        d_rec_in = d_rec_info = nullptr;
         cap_rec = 0;
+        drop_all(d_rec[0], d_rec[1], d_rec[2], d_rec[3], d_rec_in, d_rec_info);
+        for (int k = 0; k < 4; ++k) CK_HIP(d_rec[k].try_ensure(nblobs * 2 * N));
+        CK_HIP(d_rec_in.try_ensure(nblobs * 2 * N * 8));
+        CK_HIP(d_rec_info.try_ensure(nblobs * 8));
+        cap_rec = nblobs;
     }
     std::vector<kzgamd::pairing::G2Jac> g2_monomial;  // [tau^i]G2, i < 65 (host; the pairing checks use [1])
     std::vector<ff::Fr> brp_roots;  // brp_roots_of_unity[0..8192) (host copy, Montgomery)
-    ff::Fr* d_brp_roots = nullptr;  // first 4096 = the blob evaluation domain
+    DevArray<ff::Fr> brp_roots_owned;       // first 4096 = the blob evaluation domain: the root's
+    const ff::Fr* d_brp_roots = nullptr;    // ... as every object reads it (a lane: its parent's)
+    // Streams, events and page-locked memory go by hand; the engine handles and the device arrays free themselves
+    // afterwards (hipFree synchronises the device: a stream that is gone does not matter to it).
     ~KzgAmdSettings() {
         lanes.clear();  // before the handles they borrow go away
         if (h_in) (void)hipHostFree(h_in);
         if (h_res) (void)hipHostFree(h_res);
-        if (is_lane) {
-            msm = nullptr;
-            msm_monomial = msm_xext = nullptr;
-            d_monomial = nullptr;
-            d_brp_roots = nullptr;
-            ntt = nullptr;
-            d_roots8192 = nullptr;
-        }
-        if (d_z) (void)hipFree(d_z);
-        if (d_y) (void)hipFree(d_y);
-        if (d_commit) (void)hipFree(d_commit);
-        if (d_qscratch) (void)hipFree(d_qscratch);
         if (ev_commit) (void)hipEventDestroy(ev_commit);
         if (ev_cells) (void)hipEventDestroy(ev_cells);
-        if (msm_verify) kzgamd::msm_destroy(msm_verify);
         if (ev_decoded) (void)hipEventDestroy(ev_decoded);
-        if (d_mono64) (void)hipFree(d_mono64);
-        if (d_vbytes) (void)hipFree(d_vbytes);
-        if (d_vpts) (void)hipFree(d_vpts);
-        if (d_vstat) (void)hipFree(d_vstat);
         for (int j = 0; j < NPIPE; ++j) {
             if (pipe_ev[j]) (void)hipEventDestroy(pipe_ev[j]);
             if (pipe[j]) (void)hipStreamDestroy(pipe[j]);
         }
-        if (d_brp_roots) (void)hipFree(d_brp_roots);
-        release_recover();
-        if (d_vc_cells) (void)hipFree(d_vc_cells);
-        if (d_vc_cols) (void)hipFree(d_vc_cols);
-        if (d_vc_pw) (void)hipFree(d_vc_pw);
-        release_vcells_many();
-        if (d_rec_idx) (void)hipFree(d_rec_idx);
-        if (d_pow7) (void)hipFree(d_pow7);
-        if (d_pow7inv) (void)hipFree(d_pow7inv);
-        if (d_monomial) (void)hipFree(d_monomial);
-        if (msm_monomial) kzgamd::msm_destroy(msm_monomial);
-        if (msm_xext) kzgamd::msm_destroy(msm_xext);
-        release_fk20();
-        if (ntt) kzgamd_ntt_free(ntt);
-        if (d_roots8192) (void)hipFree(d_roots8192);
-        release_cells();
-        if (d_cstatus) (void)hipFree(d_cstatus);
-        if (d_cpts) (void)hipFree(d_cpts);
         if (stream2 && stream2 != stream) (void)hipStreamDestroy(stream2);
-        if (msm) kzgamd::msm_destroy(msm);
-        if (d_blobs) (void)hipFree(d_blobs);
-        if (d_scalars) (void)hipFree(d_scalars);
-        if (d_status) (void)hipFree(d_status);
-        if (d_out) (void)hipFree(d_out);
         if (stream) (void)hipStreamDestroy(stream);
-    }
-    void release_cells() {
-        if (d_fr_a) (void)hipFree(d_fr_a);
-        if (d_fr_b) (void)hipFree(d_fr_b);
-        if (d_fr_ext) (void)hipFree(d_fr_ext);
-        if (d_cells) (void)hipFree(d_cells);
-        if (d_q) (void)hipFree(d_q);
-        if (d_proofs) (void)hipFree(d_proofs);
-        d_fr_a = d_fr_b = d_fr_ext = nullptr;
-        d_cells = d_q = nullptr;
-        d_proofs = nullptr;
-        cap_cells = 0;
-        cap_q = 0;
     }
     void ensure_cells(size_t nblobs) {
         if (nblobs <= cap_cells) return;
-        release_cells();
-        CK_HIP(hipMalloc(&d_fr_a, nblobs * N * 32));
-        CK_HIP(hipMalloc(&d_fr_b, nblobs * N * 32));
-        CK_HIP(hipMalloc(&d_fr_ext, nblobs * 2 * N * 32));
-        CK_HIP(hipMalloc(&d_cells, nblobs * 2 * N * 32));
-        CK_HIP(hipMalloc(&d_proofs, nblobs * 128 * 48));
+        cap_cells = 0;
+        drop_all(d_fr_a, d_fr_b, d_fr_ext, d_cells, d_q, d_proofs);
+        CK_HIP(d_fr_a.try_ensure(nblobs * N));
+        CK_HIP(d_fr_b.try_ensure(nblobs * N));
+        CK_HIP(d_fr_ext.try_ensure(nblobs * 2 * N));
+        CK_HIP(d_cells.try_ensure(nblobs * 2 * N * 8));
+        CK_HIP(d_proofs.try_ensure(nblobs * 128 * 48));
         cap_cells = nblobs;
     }
     void ensure(size_t nblobs) {
         if (nblobs <= cap_blobs) return;
-        if (d_blobs) (void)hipFree(d_blobs);
-        if (d_scalars) (void)hipFree(d_scalars);
-        if (d_status) (void)hipFree(d_status);
-        if (d_out) (void)hipFree(d_out);
-        if (d_z) (void)hipFree(d_z);
-        if (d_y) (void)hipFree(d_y);
-        if (d_commit) (void)hipFree(d_commit);
-        if (d_cstatus) (void)hipFree(d_cstatus);
-        d_cstatus = nullptr;
-        if (d_cpts) (void)hipFree(d_cpts);
-        d_cpts = nullptr;
-        d_blobs = nullptr;
-        d_scalars = nullptr;
-        d_status = nullptr;
-        d_out = nullptr;
-        d_z = nullptr;
-        d_y = nullptr;
-        d_commit = nullptr;
         cap_blobs = 0;
-        CK_HIP(hipMalloc(&d_blobs, nblobs * BYTES_PER_BLOB));
-        CK_HIP(hipMalloc(&d_scalars, nblobs * BYTES_PER_BLOB));
-        CK_HIP(hipMalloc(&d_status, nblobs * sizeof(int)));
-        CK_HIP(hipMalloc(&d_out, nblobs * 144));  // 48-byte compressed results, or Jacobian for the small-batch path
-        CK_HIP(hipMalloc(&d_z, nblobs * 32));
-        CK_HIP(hipMalloc(&d_y, nblobs * 32));
-        CK_HIP(hipMalloc(&d_commit, nblobs * 48));
-        CK_HIP(hipMalloc(&d_cstatus, nblobs * sizeof(int)));
-        CK_HIP(hipMalloc(&d_cpts, WIDE_COMMIT_CHECK_MAX * sizeof(AffPt)));
+        drop_all(d_blobs, d_scalars, d_status, d_out, d_z, d_y, d_commit, d_cstatus, d_cpts);
+        CK_HIP(d_blobs.try_ensure(nblobs * BYTES_PER_BLOB));
+        CK_HIP(d_scalars.try_ensure(nblobs * BYTES_PER_BLOB / 4));
+        CK_HIP(d_status.try_ensure(nblobs));
+        CK_HIP(d_out.try_ensure(nblobs * 144));  // 48-byte compressed results, or Jacobian for the small-batch path
+        CK_HIP(d_z.try_ensure(nblobs * 8));
+        CK_HIP(d_y.try_ensure(nblobs * 8));
+        CK_HIP(d_commit.try_ensure(nblobs * 48));
+        CK_HIP(d_cstatus.try_ensure(nblobs));
+        CK_HIP(d_cpts.try_ensure(WIDE_COMMIT_CHECK_MAX));
         cap_blobs = nblobs;
     }
 };

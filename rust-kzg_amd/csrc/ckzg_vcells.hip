@@ -146,14 +146,14 @@ void many_g1(blst_p1 out[2], const Bytes48* commitments_bytes, const uint64_t* c
         dev->mono64_bytes.resize(CELL_SIZE * 48);
         compress_on_host(dev->mono64_bytes.data(), cs->g1_values_monomial, CELL_SIZE);
     }
-    const bool have_mono = dev->d_mono64 != nullptr;
+    const bool have_mono = dev->d_mono64.p != nullptr;
     const size_t ndec = have_mono ? n + m : np;
     {
         std::vector<uint8_t> stage(ndec * 48);
         memcpy(stage.data(), proofs_bytes, n * 48);
         memcpy(stage.data() + n * 48, uniq.data(), m * 48);
         if (!have_mono) memcpy(stage.data() + (n + m) * 48, dev->mono64_bytes.data(), CELL_SIZE * 48);
-        vc_decode_begin(dev, stage, ndec, dev->d_mono64, have_mono ? CELL_SIZE : 0);
+        vc_decode_begin(dev, stage, ndec, dev->d_mono64.p, have_mono ? CELL_SIZE : 0);
     }
     // from here on the caller's cells may be on their way to the device and the decode runs: nothing of this call may
     // stay in flight when it returns, however it returns
@@ -224,12 +224,12 @@ void many_g1(blst_p1 out[2], const Bytes48* commitments_bytes, const uint64_t* c
         CK_HIP(on_device.err);
         dev->ensure_recover(1);
         dev->ensure_vcells_many(n);
-        if (!dev->d_roots8192) {
-            CK_HIP(hipMalloc(&dev->d_roots8192, (2 * N + 1) * sizeof(ff::Fr)));
-            CK_HIP(hipMemcpy(dev->d_roots8192, cs->roots_of_unity, (2 * N + 1) * sizeof(ff::Fr), hipMemcpyHostToDevice));
+        if (!dev->d_roots8192.p) {
+            CK_HIP(dev->d_roots8192.try_ensure(2 * N + 1));
+            CK_HIP(hipMemcpy(dev->d_roots8192.p, cs->roots_of_unity, (2 * N + 1) * sizeof(ff::Fr), hipMemcpyHostToDevice));
         }
-        CK_HIP(hipMemsetAsync(dev->d_vm_status, 0, sizeof(int), dev->stream));
-        CK_HIP(hipMemcpyAsync(dev->d_vm_cells, cells, n * BYTES_PER_CELL, hipMemcpyHostToDevice, dev->stream));
+        CK_HIP(hipMemsetAsync(dev->d_vm_status.p, 0, sizeof(int), dev->stream));
+        CK_HIP(hipMemcpyAsync(dev->d_vm_cells.p, cells, n * BYTES_PER_CELL, hipMemcpyHostToDevice, dev->stream));
     }
     tm[1] = ms_since(t_hash);  // the cells handed to the copy engine
     // ... and the tables of the two kernels: the cells grouped by column (a counting sort), each column cut into slices
@@ -285,19 +285,19 @@ void many_g1(blst_p1 out[2], const Bytes48* commitments_bytes, const uint64_t* c
         kzgamd::DeviceGuard on_device(dev->device);
         CK_HIP(on_device.err);
         hipStream_t st = dev->stream;
-        const u32* d_tab = dev->d_vm_tab;
-        CK_HIP(hipMemcpyAsync(dev->d_vm_w, sc.data(), n * sizeof(ff::Fr), hipMemcpyHostToDevice, st));  // row 0 = the weights
-        CK_HIP(hipMemcpyAsync(dev->d_vm_tab, tab.data(), tab.size() * sizeof(u32), hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(k_vcells_agg, dim3((unsigned)nslices), dim3(64), 0, st, dev->d_vm_part, dev->d_vm_status,
-                           (const uint4*)dev->d_vm_cells, d_tab + T_SL, d_tab + T_ORD, (const ff::Fr*)dev->d_vm_w);
-        hipLaunchKernelGGL(k_vcells_fold, dim3((unsigned)CELLS_PER_EXT_BLOB), dim3(64), 0, st, dev->d_rec[0],
-                           (const ff::Fr*)dev->d_vm_part, d_tab);
+        const u32* d_tab = dev->d_vm_tab.p;
+        CK_HIP(hipMemcpyAsync(dev->d_vm_w.p, sc.data(), n * sizeof(ff::Fr), hipMemcpyHostToDevice, st));  // row 0 = the weights
+        CK_HIP(hipMemcpyAsync(dev->d_vm_tab.p, tab.data(), tab.size() * sizeof(u32), hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(k_vcells_agg, dim3((unsigned)nslices), dim3(64), 0, st, dev->d_vm_part.p, dev->d_vm_status.p,
+                           (const uint4*)dev->d_vm_cells.p, d_tab + T_SL, d_tab + T_ORD, (const ff::Fr*)dev->d_vm_w.p);
+        hipLaunchKernelGGL(k_vcells_fold, dim3((unsigned)CELLS_PER_EXT_BLOB), dim3(64), 0, st, dev->d_rec[0].p,
+                           (const ff::Fr*)dev->d_vm_part.p, d_tab);
         CK_HIP(hipGetLastError());
-        if (kzgamd_ntt_fr_device(dev->ntt, dev->d_rec[1], dev->d_rec[0], CELL_SIZE, CELLS_PER_EXT_BLOB, 1, st) != 0)
+        if (kzgamd_ntt_fr_device(dev->ntt.get(), dev->d_rec[1].p, dev->d_rec[0].p, CELL_SIZE, CELLS_PER_EXT_BLOB, 1, st) != 0)
             throw CkErr{C_KZG_ERROR, "ntt"};
-        vc_interp_enqueue(dev->d_rec[2], dev->d_rec[1], dev->d_roots8192, st);
-        CK_HIP(hipMemcpyAsync(interp.data(), dev->d_rec[2], CELL_SIZE * sizeof(ff::Fr), hipMemcpyDeviceToHost, st));
-        CK_HIP(hipMemcpyAsync(&status, dev->d_vm_status, sizeof(int), hipMemcpyDeviceToHost, st));
+        vc_interp_enqueue(dev->d_rec[2].p, dev->d_rec[1].p, dev->d_roots8192.p, st);
+        CK_HIP(hipMemcpyAsync(interp.data(), dev->d_rec[2].p, CELL_SIZE * sizeof(ff::Fr), hipMemcpyDeviceToHost, st));
+        CK_HIP(hipMemcpyAsync(&status, dev->d_vm_status.p, sizeof(int), hipMemcpyDeviceToHost, st));
         CK_HIP(hipStreamSynchronize(st));
     }
     tm[4] = ms_since(t_gpu);  // weights and tables up, k_vcells_agg, k_vcells_fold, transforms, interpolation, 64 coefficients down
@@ -309,9 +309,9 @@ void many_g1(blst_p1 out[2], const Bytes48* commitments_bytes, const uint64_t* c
         kzgamd::DeviceGuard on_device(dev->device);
         CK_HIP(on_device.err);
         CK_HIP(hipEventSynchronize(dev->ev_decoded));
-        if (!dev->msm_verify) dev->msm_verify = kzgamd::msm_create(dev->d_vpts, np, true, false, true, kzgamd::G1_TRUSTED, &dev->opt);
-        else kzgamd::msm_reset_points(dev->msm_verify, dev->d_vpts, np);
-        kzgamd::msm_run_host(dev->msm_verify, pl, sc.data(), np, 2);
+        if (!dev->msm_verify) dev->msm_verify.reset(kzgamd::msm_create(dev->d_vpts.p, np, true, false, true, kzgamd::G1_TRUSTED, &dev->opt));
+        else kzgamd::msm_reset_points(dev->msm_verify.get(), dev->d_vpts.p, np);
+        kzgamd::msm_run_host(dev->msm_verify.get(), pl, sc.data(), np, 2);
     }
     const std::vector<int> stat = vc_decode_status(dev, np);
     tm[5] = ms_since(t_gpu) - tm[4];  // waiting for the decode, the two-row MSM, the status words
@@ -326,10 +326,9 @@ void many_g1(blst_p1 out[2], const Bytes48* commitments_bytes, const uint64_t* c
             std::lock_guard<std::mutex> lk(dev->mu);
             kzgamd::DeviceGuard on_device(dev->device);
             CK_HIP(on_device.err);
-            AffPt* keep = nullptr;
-            CK_HIP(hipMalloc(&keep, CELL_SIZE * sizeof(AffPt)));
-            if (hipMemcpy(keep, dev->d_vpts + n + m, CELL_SIZE * sizeof(AffPt), hipMemcpyDeviceToDevice) == hipSuccess) dev->d_mono64 = keep;
-            else (void)hipFree(keep);
+            DevArray<AffPt> keep;
+            CK_HIP(keep.try_ensure(CELL_SIZE));
+            if (hipMemcpy(keep.p, dev->d_vpts.p + n + m, CELL_SIZE * sizeof(AffPt), hipMemcpyDeviceToDevice) == hipSuccess) dev->d_mono64 = std::move(keep);
         }
     }
     memcpy(out, pl, sizeof pl);

@@ -567,18 +567,18 @@ int enqueue_stages(NttCtx* ctx, Xyzz* bufs[2], Xyzz* tab, size_t n, size_t nbatc
         if (wide) {
             if (s > 0)  // stage 0 has unit twiddles only
                 hipLaunchKernelGGL(k_g1_stage_mul_wide, dim3((unsigned)(2 * bf)), dim3(64), 0, st, tab, src,
-                                   (const RootSplit*)ctx->d_kroots, (u32)n, s, (u32)ctx->W, inverse ? 1 : 0);
+                                   (const RootSplit*)ctx->d_kroots.p, (u32)n, s, (u32)ctx->W, inverse ? 1 : 0);
             hipLaunchKernelGGL(k_g1_stage_bfly_wide, dim3((unsigned)bf), dim3(64), 0, st, dst, src, (const Xyzz*)tab, (u32)n, s,
                                (u32)ctx->W);
         } else if (s > 0 && 2 * bf <= quad_max) {
             hipLaunchKernelGGL(k_g1_stage_chain<4>, grid_for(8 * bf), dim3(block_threads(8 * bf)), 0, st, dst, src, tab,
-                               (const RootSplit*)ctx->d_kroots, (u32)n, s, (u32)ctx->W, inverse ? 1 : 0, 8 * bf);
+                               (const RootSplit*)ctx->d_kroots.p, (u32)n, s, (u32)ctx->W, inverse ? 1 : 0, 8 * bf);
         } else if (s > 0 && 2 * bf <= ctx->g1_pair_max) {
             hipLaunchKernelGGL(k_g1_stage_chain<2>, grid_for(4 * bf), dim3(block_threads(4 * bf)), 0, st, dst, src, tab,
-                               (const RootSplit*)ctx->d_kroots, (u32)n, s, (u32)ctx->W, inverse ? 1 : 0, 4 * bf);
+                               (const RootSplit*)ctx->d_kroots.p, (u32)n, s, (u32)ctx->W, inverse ? 1 : 0, 4 * bf);
         } else {  // stage 0 (unit twiddles: one addition per lane) and the grids that fill the chip on their own
             hipLaunchKernelGGL(k_g1_stage_chain<1>, grid_for(2 * bf), dim3(block_threads(2 * bf)), 0, st, dst, src, tab,
-                               (const RootSplit*)ctx->d_kroots, (u32)n, s, (u32)ctx->W, inverse ? 1 : 0, 2 * bf);
+                               (const RootSplit*)ctx->d_kroots.p, (u32)n, s, (u32)ctx->W, inverse ? 1 : 0, 2 * bf);
         }
     }
     return logn & 1;
@@ -620,45 +620,29 @@ void enqueue_varmul_sum(NttCtx* ctx, Xyzz* out, Xyzz* prod, Xyzz* tab, const Xyz
     }
 }
 
-void ensure_g1(NttCtx* ctx, size_t total, size_t tab_lanes) {
-    if (!ctx->d_kroots) {
-        std::vector<RootSplit> split(ctx->W + 1);
-        for (size_t i = 0; i <= ctx->W; ++i) split[i] = split_scalar(ff::from_mont(ctx->roots[i]));
-        DEV_TRY(hipMalloc(&ctx->d_kroots, (ctx->W + 1) * sizeof(RootSplit)));
-        DEV_TRY(hipMemcpy(ctx->d_kroots, split.data(), (ctx->W + 1) * sizeof(RootSplit), hipMemcpyHostToDevice));
-    }
-    if (total > ctx->cap_g1) {
-        if (ctx->d_p1) (void)hipFree(ctx->d_p1);
-        if (ctx->d_pts) (void)hipFree(ctx->d_pts);
-        ctx->d_p1 = ctx->d_pts = nullptr;
-        ctx->cap_g1 = 0;
-        DEV_TRY(hipMalloc(&ctx->d_p1, total * sizeof(blst_p1)));
-        DEV_TRY(hipMalloc(&ctx->d_pts, 2 * total * sizeof(Xyzz)));  // ping-pong halves
-        ctx->cap_g1 = total;
-    }
-    if (tab_lanes > ctx->cap_tab) {
-        if (ctx->d_tab) (void)hipFree(ctx->d_tab);
-        ctx->d_tab = nullptr;
-        ctx->cap_tab = 0;
-        DEV_TRY(hipMalloc(&ctx->d_tab, tab_lanes * NTAB * sizeof(Xyzz)));
-        ctx->cap_tab = tab_lanes;
-    }
+void ensure_kroots(NttCtx* ctx) {  // the roots as split scalars, once
+    if (ctx->d_kroots.p) return;
+    std::vector<RootSplit> split(ctx->W + 1);
+    for (size_t i = 0; i <= ctx->W; ++i) split[i] = split_scalar(ff::from_mont(ctx->roots[i]));
+    ctx->d_kroots.ensure(ctx->W + 1);
+    DEV_TRY(hipMemcpy(ctx->d_kroots.p, split.data(), (ctx->W + 1) * sizeof(RootSplit), hipMemcpyHostToDevice));
 }
 
 void ensure_g1_tab(NttCtx* ctx, size_t tab_lanes) {
-    if (!ctx->d_kroots) {
-        std::vector<RootSplit> split(ctx->W + 1);
-        for (size_t i = 0; i <= ctx->W; ++i) split[i] = split_scalar(ff::from_mont(ctx->roots[i]));
-        DEV_TRY(hipMalloc(&ctx->d_kroots, (ctx->W + 1) * sizeof(RootSplit)));
-        DEV_TRY(hipMemcpy(ctx->d_kroots, split.data(), (ctx->W + 1) * sizeof(RootSplit), hipMemcpyHostToDevice));
+    ensure_kroots(ctx);
+    ctx->d_tab.ensure(tab_lanes * NTAB * sizeof(Xyzz));
+}
+
+void ensure_g1(NttCtx* ctx, size_t total, size_t tab_lanes) {
+    ensure_kroots(ctx);
+    if (total > ctx->cap_g1) {
+        ctx->cap_g1 = 0;
+        kzgamd::drop_all(ctx->d_p1, ctx->d_pts);
+        ctx->d_p1.ensure(total * sizeof(blst_p1));
+        ctx->d_pts.ensure(2 * total * sizeof(Xyzz));  // ping-pong halves
+        ctx->cap_g1 = total;
     }
-    if (tab_lanes > ctx->cap_tab) {
-        if (ctx->d_tab) (void)hipFree(ctx->d_tab);
-        ctx->d_tab = nullptr;
-        ctx->cap_tab = 0;
-        DEV_TRY(hipMalloc(&ctx->d_tab, tab_lanes * NTAB * sizeof(Xyzz)));
-        ctx->cap_tab = tab_lanes;
-    }
+    ctx->d_tab.ensure(tab_lanes * NTAB * sizeof(Xyzz));
 }
 
 }  // namespace
@@ -680,7 +664,7 @@ static void* fftg1_enqueue(NttCtx* ctx, void* data_v, void* scratch_v, size_t n,
         std::lock_guard<std::mutex> lk(ctx->mu);
         ensure_g1_tab(ctx, tab_v ? 0 : 2 * total);  // with the caller's tables: the split roots only
         Xyzz* bufs[2] = {(Xyzz*)scratch_v, (Xyzz*)data_v};
-        Xyzz* tab = tab_v ? (Xyzz*)tab_v : (Xyzz*)ctx->d_tab;
+        Xyzz* tab = tab_v ? (Xyzz*)tab_v : (Xyzz*)ctx->d_tab.p;
         hipLaunchKernelGGL(k_g1_brp_xyzz, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, bufs[0],
                            (const Xyzz*)data_v, (u32)n, logn, total);
         Xyzz* res = bufs[enqueue_stages(ctx, bufs, tab, n, nbatch, inverse, st)];
@@ -735,11 +719,11 @@ extern "C" int kzgamd_fft_g1_batch(void* vctx, blst_p1* out, const blst_p1* in, 
         const size_t total = n * nbatch, bf = total / 2;
         const int logn = ilog2(n);
         ensure_g1(ctx, total, inverse ? 2 * total : (bf ? 2 * bf : 2));
-        Xyzz* pts = (Xyzz*)ctx->d_pts;
-        Xyzz* tab = (Xyzz*)ctx->d_tab;
+        Xyzz* pts = (Xyzz*)ctx->d_pts.p;
+        Xyzz* tab = (Xyzz*)ctx->d_tab.p;
         hipStream_t st = ctx->stream;
-        DEV_TRY(hipMemcpyAsync(ctx->d_p1, in, total * sizeof(blst_p1), hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(k_g1_load, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, pts, (const ff::Fp*)ctx->d_p1,
+        DEV_TRY(hipMemcpyAsync(ctx->d_p1.p, in, total * sizeof(blst_p1), hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(k_g1_load, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, pts, (const ff::Fp*)ctx->d_p1.p,
                            (u32)n, logn, total);
         Xyzz* bufs[2] = {pts, pts + total};
         Xyzz* res = bufs[enqueue_stages(ctx, bufs, tab, n, nbatch, inverse, st)];
@@ -749,10 +733,10 @@ extern "C" int kzgamd_fft_g1_batch(void* vctx, blst_p1* out, const blst_p1* in, 
             v.v[1] = (u32)((u64)n >> 32);
             enqueue_scale(ctx, res, tab, split_scalar(ff::from_mont(ff::inverse_bgcd(ff::to_mont(v)))), total, st);
         }
-        hipLaunchKernelGGL(k_g1_store, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (ff::Fp*)ctx->d_p1, (const Xyzz*)res,
+        hipLaunchKernelGGL(k_g1_store, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (ff::Fp*)ctx->d_p1.p, (const Xyzz*)res,
                            total);
         DEV_TRY(hipGetLastError());
-        DEV_TRY(hipMemcpyAsync(out, ctx->d_p1, total * sizeof(blst_p1), hipMemcpyDeviceToHost, st));
+        DEV_TRY(hipMemcpyAsync(out, ctx->d_p1.p, total * sizeof(blst_p1), hipMemcpyDeviceToHost, st));
         DEV_TRY(hipStreamSynchronize(st));
     } catch (const kzgamd::DevErr& e) {
         return kzgamd::dev_code(e.e);

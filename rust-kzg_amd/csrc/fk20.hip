@@ -134,7 +134,7 @@ struct Fk20Ctx {
     DevBuf poly, t, f, sc, prod, tab, h, h2, out;
 
     void drop_workspace() {
-        for (DevBuf* b : {&poly, &t, &f, &sc, &prod, &tab, &h, &h2, &out}) b->drop();
+        kzgamd::drop_all(poly, t, f, sc, prod, tab, h, h2, out);
         cap = 0;
     }
     void ensure(size_t npoly) {
@@ -154,8 +154,6 @@ struct Fk20Ctx {
         cap = npoly;
     }
     ~Fk20Ctx() {
-        drop_workspace();
-        x.drop();
         if (msm) kzgamd::msm_destroy(msm);
         if (st) (void)hipStreamDestroy(st);
     }

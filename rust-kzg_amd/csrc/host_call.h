@@ -24,28 +24,62 @@ struct DevErr {
 // what a call returns for a failed HIP call: -(100 + hipError_t)
 inline int dev_code(hipError_t e) { return -(int)e - 100; }
 
-// workspace of a handle: grows when a call needs more, kept until the handle drops it
-struct DevBuf {
-    void* p = nullptr;
-    size_t cap = 0;
-    void ensure(size_t bytes) {
-        if (bytes <= cap) return;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-        DEV_TRY(hipMalloc(&p, bytes));
-        cap = bytes;
+// The one owner of device memory (every handle, every call): `cap` elements of T at `p`, grown when more are asked for,
+// freed by drop() or when the owner goes.  Move-only.  Never a member of an object with static storage duration: its
+// hipFree would run during the runtime's own teardown.
+template <class T>
+struct DevArray {
+    T* p = nullptr;
+    size_t cap = 0;  // elements
+    DevArray() = default;
+    DevArray(const DevArray&) = delete;
+    DevArray& operator=(const DevArray&) = delete;
+    DevArray(DevArray&& o) noexcept : p(o.p), cap(o.cap) {
+        o.p = nullptr;
+        o.cap = 0;
     }
+    DevArray& operator=(DevArray&& o) noexcept {
+        if (this != &o) {
+            drop();
+            p = o.p;
+            cap = o.cap;
+            o.p = nullptr;
+            o.cap = 0;
+        }
+        return *this;
+    }
+    ~DevArray() { drop(); }
+    // for the layers with an error type of their own (HIP_TRY, CK_HIP, the hipError_t chains); after a failure the
+    // array is empty
+    [[nodiscard]] hipError_t try_ensure(size_t n) {
+        if (n <= cap) return hipSuccess;
+        drop();
+        const hipError_t e = hipMalloc((void**)&p, n * sizeof(T));
+        if (e != hipSuccess) {
+            p = nullptr;
+            return e;
+        }
+        cap = n;
+        return hipSuccess;
+    }
+    void ensure(size_t n) { DEV_TRY(try_ensure(n)); }
     void drop() {
         if (p) (void)hipFree(p);
         p = nullptr;
         cap = 0;
     }
-    template <class T>
-    T* as() const {
-        return (T*)p;
+    template <class U>
+    U* as() const {
+        return (U*)p;
     }
 };
+using DevBuf = DevArray<unsigned char>;  // untyped, counted in bytes
+
+// a group of arrays is released as a whole before any of it is allocated again: the peak while it grows is the new size
+template <class... A>
+void drop_all(A&... a) {
+    (a.drop(), ...);
+}
 
 // workspace of one call: freed when the call ends, whichever way
 struct ScopedBuf {

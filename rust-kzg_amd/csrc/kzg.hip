@@ -385,9 +385,6 @@ struct KzgCtx {
     DevBuf gjac, gflags, gsplit, gxyzz, gprod, gtab, gsum, gok;
 
     ~KzgCtx() {
-        for (DevBuf* b : {&polys, &xs, &pw, &q, &r, &r2, &sums, &local, &out, &pts, &aff, &pref, &stat, &xinv, &rho, &rows, &part, &agg,
-                           &gjac, &gflags, &gsplit, &gxyzz, &gprod, &gtab, &gsum, &gok})
-            b->drop();
         if (vmsm) kzgamd::msm_destroy(vmsm);
         if (msm) kzgamd::msm_destroy(msm);
         if (st) (void)hipStreamDestroy(st);

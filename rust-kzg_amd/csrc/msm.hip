@@ -21,6 +21,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <memory>
 #include <mutex>
 #include <optional>
 #include <string>
@@ -32,6 +33,7 @@
 #include "g1grp.hip.h"
 #include "g1_30s.hip.h"
 #include "glv.hip.h"
+#include "host_call.h"
 #include "host_g1.h"
 #include "combine.h"
 #include "config.h"
@@ -44,6 +46,7 @@ using ff::u64;
 using g1::AffPt;
 using WidePt = g1s::WidePt30;  // the wide table's slot: x, y in the limbs of the accumulation chain (g1_30s.hip.h)
 using g1::Xyzz;
+using kzgamd::DevArray;
 
 namespace {
 
@@ -1993,65 +1996,23 @@ int choose_window(size_t n, bool prepared, bool glv, int forced) {
     return best;
 }
 
-template <class T>
-struct DevBuf {
-    T* p = nullptr;
-    size_t cap = 0;
-    void ensure(size_t n) {
-        if (n <= cap) return;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-        HIP_TRY(hipMalloc(&p, n * sizeof(T)));
-        cap = n;
-    }
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-    }
-};
-
 struct Workspace {
-    DevBuf<u32> counts, offsets, sorted, scalars, ranks, tmp, bins, digits, wghist;
-    DevBuf<Xyzz> buckets, lvlA[2], lvlM[2], top, win, dense, wpart;
-    DevBuf<u32> wcount;
-    DevBuf<u32> bcount;  // k_blocksum_hybrid's counters: zeroed when allocated, left at zero by every launch
-    DevBuf<Xyzz> bpart;
-    DevBuf<unsigned char> heavy;
-    DevBuf<u32> heavy_list, nheavy;
-    DevBuf<ff::Fp> out;
+    DevArray<u32> counts, offsets, sorted, scalars, ranks, tmp, bins, digits, wghist;
+    DevArray<Xyzz> buckets, lvlA[2], lvlM[2], top, win, dense, wpart;
+    DevArray<u32> wcount;
+    DevArray<u32> bcount;  // k_blocksum_hybrid's counters: zeroed when allocated, left at zero by every launch
+    DevArray<Xyzz> bpart;
+    DevArray<unsigned char> heavy;
+    DevArray<u32> heavy_list, nheavy;
+    DevArray<ff::Fp> out;
     // the last enqueue that used this workspace: another stream that is handed the same workspace waits for it
     hipEvent_t last_done = nullptr;
     hipStream_t last_stream = nullptr;
-    void release() {
+    Workspace() = default;
+    Workspace(const Workspace&) = delete;
+    Workspace& operator=(const Workspace&) = delete;
+    ~Workspace() {
         if (last_done) (void)hipEventDestroy(last_done);
-        last_done = nullptr;
-        counts.release();
-        digits.release();
-        wghist.release();
-        offsets.release();
-        sorted.release();
-        ranks.release();
-        tmp.release();
-        bins.release();
-        scalars.release();
-        buckets.release();
-        for (int k = 0; k < 2; ++k) {
-            lvlA[k].release();
-            lvlM[k].release();
-        }
-        top.release();
-        dense.release();
-        wpart.release();
-        wcount.release();
-        bcount.release();
-        bpart.release();
-        win.release();
-        heavy.release();
-        heavy_list.release();
-        nheavy.release();
-        out.release();
     }
 };
 
@@ -2113,8 +2074,8 @@ struct kzgamd::MsmContext {
     bool glv = false;  // variable-base engine: scalars split k = k1 + k2*x^2, table = P_i followed by [x^2]P_i
     int c = 0, rows = 0, nwin = 0;
     size_t nb = 0;
-    DevBuf<AffPt> table;  // rows x n (prepared) or n
-    DevBuf<WidePt> wide;  // wide fixed-base table: (rows x n) x 2^(c-1) 128-byte slots, when it fits the budget
+    DevArray<AffPt> table;  // rows x n (prepared) or n
+    DevArray<WidePt> wide;  // wide fixed-base table: (rows x n) x 2^(c-1) 128-byte slots, when it fits the budget
     bool fbw = false;
     bool fbw_glv = false;  // the wide table covers 128-bit half-scalars (rows = ceil(128 / c)); scalars are GLV-split
     Workspace ws;
@@ -2123,7 +2084,7 @@ struct kzgamd::MsmContext {
     // the handle's own stream and the first caller stream; further streams get their own.
     hipStream_t ws_owner = nullptr;
     bool ws_owned = false;
-    std::vector<std::pair<hipStream_t, Workspace*>> ws_extra;
+    std::vector<std::pair<hipStream_t, std::unique_ptr<Workspace>>> ws_extra;
     Workspace& workspace_for(hipStream_t st) {
         if (st == stream) return ws;  // host-buffer entry points (synchronised internally)
         if (!ws_owned) {
@@ -2134,7 +2095,7 @@ struct kzgamd::MsmContext {
         for (auto& e : ws_extra)
             if (e.first == st) return *e.second;
         if (ws_extra.size() >= 23) return ws;  // more streams than workspaces: shared, see WsUse
-        ws_extra.emplace_back(st, new Workspace());
+        ws_extra.emplace_back(st, std::make_unique<Workspace>());
         return *ws_extra.back().second;
     }
     hipStream_t stream = nullptr;
@@ -2183,8 +2144,8 @@ struct kzgamd::MsmContext {
     static constexpr int COMBINE_LANES = 4;
     struct CombineLane {
         hipStream_t st = nullptr;
-        DevBuf<u32> scalars;
-        DevBuf<ff::Fp> out;
+        DevArray<u32> scalars;
+        DevArray<ff::Fp> out;
         unsigned char* h_out = nullptr;  // COMBINE_MAX x 144, page-locked
     };
     CombineQueue<HostCall> comb;  // settings from the tuning keys combine_lanes / combine_gather_min / combine_gather_us
@@ -2194,16 +2155,7 @@ struct kzgamd::MsmContext {
         delete matrix;
         for (auto& l : lanes) {
             if (l.h_out) (void)hipHostFree(l.h_out);
-            l.scalars.release();
-            l.out.release();
             if (l.st) (void)hipStreamDestroy(l.st);
-        }
-        table.release();
-        wide.release();
-        ws.release();
-        for (auto& e : ws_extra) {
-            e.second->release();
-            delete e.second;
         }
         for (auto& e : ev)
             if (e) (void)hipEventDestroy(e);
@@ -2233,15 +2185,15 @@ static void build_wide_table(MsmContext* ctx) {
     const size_t nslots = (size_t)ctx->rows * ctx->n;
     const double gb = (double)nslots * (double)mults * sizeof(WidePt) / 1e9;
     if (budget_gb <= 0 || gb > budget_gb || mults < (size_t)FBW_SEG) return;
-    ctx->wide.ensure(nslots * mults);
+    HIP_TRY(ctx->wide.try_ensure(nslots * mults));
     // tile: up to 2^22 table entries at a time (XYZZ 224 B + prefix 56 B of scratch each)
     size_t tile_slots = ((size_t)1 << 22) / mults;
     if (tile_slots == 0) tile_slots = 1;
     if (tile_slots > nslots) tile_slots = nslots;
-    DevBuf<Xyzz> tmp;
-    DevBuf<fp28::Fe> pref;
-    tmp.ensure(tile_slots * mults);
-    pref.ensure(tile_slots * mults);
+    DevArray<Xyzz> tmp;
+    DevArray<fp28::Fe> pref;
+    HIP_TRY(tmp.try_ensure(tile_slots * mults));
+    HIP_TRY(pref.try_ensure(tile_slots * mults));
     for (size_t s0 = 0; s0 < nslots; s0 += tile_slots) {
         const size_t ns = s0 + tile_slots <= nslots ? tile_slots : nslots - s0;
         const size_t chain_threads = ns * (mults / FBW_SEG), cnt = ns * mults;
@@ -2253,21 +2205,20 @@ static void build_wide_table(MsmContext* ctx) {
     }
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(ctx->stream));
-    tmp.release();
-    pref.release();
+    tmp.drop();
+    pref.drop();
     ctx->fbw = true;
 }
 
 // whether every one of the n bases at d_bases lies in the r-torsion subgroup (one launch on the handle's stream, awaited)
 static bool bases_in_g1(MsmContext* ctx, const AffPt* d_bases, size_t n) {
-    DevBuf<int> bad;
-    bad.ensure(1);
+    DevArray<int> bad;
+    HIP_TRY(bad.try_ensure(1));
     HIP_TRY(hipMemsetAsync(bad.p, 0, sizeof(int), ctx->stream));
     hipLaunchKernelGGL(k_bases_in_g1, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, ctx->stream, d_bases, n, bad.p);
     int nbad = 1;
     HIP_TRY(hipMemcpyAsync(&nbad, bad.p, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
-    bad.release();
     return nbad == 0;
 }
 
@@ -2323,12 +2274,12 @@ MsmContext* msm_create(const void* points, size_t n, bool points_on_device, bool
         ctx->glv = ctx->glv && ctx->opt.t[T_GLV] != 0;
         if (!ctx->glv) as_variable = false;
         // the bases first (row 0 of the table; the variable-base engine appends the [x^2]P images)
-        DevBuf<AffPt> row0;
-        row0.ensure(ctx->glv ? 2 * n : n);
-        DevBuf<ff::Fp> staging;
+        DevArray<AffPt> row0;
+        HIP_TRY(row0.try_ensure(ctx->glv ? 2 * n : n));
+        DevArray<ff::Fp> staging;
         const ff::Fp* src = (const ff::Fp*)points;
         if (!points_are_affpt && !points_on_device) {
-            staging.ensure(2 * n);
+            HIP_TRY(staging.try_ensure(2 * n));
             HIP_TRY(hipMemcpyAsync(staging.p, points, n * 96, hipMemcpyHostToDevice, ctx->stream));
             src = staging.p;
         }
@@ -2376,16 +2327,16 @@ MsmContext* msm_create(const void* points, size_t n, bool points_on_device, bool
             ctx->nwin = ctx->glv ? (127 + ctx->c) / ctx->c : 255 / ctx->c + 1;
         }
         ctx->nb = (size_t)1 << (ctx->c - 1);
-        ctx->table.ensure(ctx->glv ? 2 * n : (size_t)ctx->rows * n);
+        HIP_TRY(ctx->table.try_ensure(ctx->glv ? 2 * n : (size_t)ctx->rows * n));
         HIP_TRY(hipMemcpyAsync(ctx->table.p, row0.p, (ctx->glv ? 2 * n : n) * sizeof(AffPt), hipMemcpyDeviceToDevice, ctx->stream));
         HIP_TRY(hipStreamSynchronize(ctx->stream));
-        row0.release();
+        row0.drop();
         if (prepare && ctx->rows > 1)
             hipLaunchKernelGGL(k_table_rows, dim3((unsigned)((n + 127) / 128)), dim3(128), 0, ctx->stream, ctx->table.p, n,
                                ctx->rows, ctx->c);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipStreamSynchronize(ctx->stream));
-        staging.release();
+        staging.drop();
         if (prepare) build_wide_table(ctx);
         if (ctx->fbw_glv && !ctx->fbw) throw HipErr{hipErrorOutOfMemory, "wide GLV table did not fit the HBM budget it was sized for"};
         if (prepare && verbose) {
@@ -2412,7 +2363,7 @@ void msm_reset_points(MsmContext* ctx, const void* d_affpts, size_t n) {
     ctx->rows = 1;
     ctx->nwin = ctx->glv ? (127 + ctx->c) / ctx->c : 255 / ctx->c + 1;
     ctx->nb = (size_t)1 << (ctx->c - 1);
-    ctx->table.ensure(ctx->glv ? 2 * n : n);
+    HIP_TRY(ctx->table.try_ensure(ctx->glv ? 2 * n : n));
     hipLaunchKernelGGL(k_copy_affpt, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, ctx->table.p,
                        (const AffPt*)d_affpts, n, ctx->glv ? 1 : 0);
     HIP_TRY(hipGetLastError());
@@ -2503,17 +2454,17 @@ static void enqueue_wide(MsmContext* ctx, Workspace& ws, void* d_out, const void
     const size_t spl1_max = ctx->tune.spl1_max > 0 ? (size_t)ctx->tune.spl1_max : 8;
     if (ctx->fbw_glv && nbatch <= spl1_max && npoints == 4096 && !ctx->tune.spl && !ctx->tune.no_wide_tail) spl = 1;
     const size_t lanes = (npoints + spl - 1) / spl * (ctx->fbw_glv ? 2 : 1);
-    ws.buckets.ensure(nbatch * lanes);
-    ws.lvlM[0].ensure(nbatch);
-    if (nbatch <= 16 && lanes % 16 == 0 && lanes >= 1024) ws.lvlA[0].ensure(nbatch * 128);
+    HIP_TRY(ws.buckets.try_ensure(nbatch * lanes));
+    HIP_TRY(ws.lvlM[0].try_ensure(nbatch));
+    if (nbatch <= 16 && lanes % 16 == 0 && lanes >= 1024) HIP_TRY(ws.lvlA[0].try_ensure(nbatch * 128));
     const size_t hybrid_max = ctx->tune.hybrid_max > 0 ? (size_t)ctx->tune.hybrid_max : BSH_MAX;
     const bool hybrid_fold = nbatch <= hybrid_max && nbatch <= BSH_CAP && lanes % (16 * 256) == 0 &&
                              !ctx->tune.no_wide_tail && !ctx->tune.no_hybrid_fold;
     bool bcount_new = false;
     if (hybrid_fold) {
-        ws.bpart.ensure(BSH_CAP * (size_t)BSH_PARTS);
+        HIP_TRY(ws.bpart.try_ensure(BSH_CAP * (size_t)BSH_PARTS));
         if (ws.bcount.cap < BSH_CAP) {
-            ws.bcount.ensure(BSH_CAP);
+            HIP_TRY(ws.bcount.try_ensure(BSH_CAP));
             bcount_new = true;
         }
     }
@@ -2525,13 +2476,13 @@ static void enqueue_wide(MsmContext* ctx, Workspace& ws, void* d_out, const void
         // (zeroed when allocated, left at zero by every launch); k_wide_fold64 (tuning key no_wide_tree): 129 cells x
         // WFOLD parts, a counter per cell — which is more of both
         const size_t need_p = (nbatch * 128 + nbatch) * (size_t)WFOLD, need_c = nbatch * 128 + nbatch;
-        ws.wpart.ensure(need_p);
+        HIP_TRY(ws.wpart.try_ensure(need_p));
         if (ws.wcount.cap < need_c) {
-            ws.wcount.ensure(need_c);
+            HIP_TRY(ws.wcount.try_ensure(need_c));
             wcount_new = true;
         }
     }
-    if (ctx->fbw_glv) ws.digits.ensure(nbatch * npoints * 2 * (size_t)((nwin + 3) & ~3));
+    if (ctx->fbw_glv) HIP_TRY(ws.digits.try_ensure(nbatch * npoints * 2 * (size_t)((nwin + 3) & ~3)));
     if (bcount_new) HIP_TRY(hipMemsetAsync(ws.bcount.p, 0, BSH_CAP * sizeof(u32), stream));
     if (wcount_new) HIP_TRY(hipMemsetAsync(ws.wcount.p, 0, ws.wcount.cap * sizeof(u32), stream));
     if (reserve_only) return;
@@ -2633,8 +2584,8 @@ static void enqueue_buckets(MsmContext* ctx, Workspace& ws, void* d_out, const v
     const size_t nb = ctx->nb;
     const size_t nsets = ctx->prepared ? nbatch : nbatch * (size_t)nwin;
     const size_t set_cap = ctx->prepared ? npoints * (size_t)nwin : (ctx->glv ? 2 * npoints : npoints);
-    ws.offsets.ensure(nsets * (nb + 1));
-    ws.sorted.ensure(nsets * set_cap);
+    HIP_TRY(ws.offsets.try_ensure(nsets * (nb + 1)));
+    HIP_TRY(ws.sorted.try_ensure(nsets * set_cap));
     // entries per accumulation lane, 2^lgc: longer chunks leave fewer pieces per bucket to fold, shorter ones more lanes
     // (A/B in one process with the tiled reduction, median ms, lgc -> time:  2^18: 5 -> 1.36, 6 -> 1.40;  2^19: 5 -> 2.13,
     //  6 -> 2.10;  2^20: 5 -> 3.70, 6 -> 3.57, 7 -> 3.49;  2^21: 6 -> 6.50, 7 -> 6.35, 8 -> 6.52;  2^22: 6 -> 13.28,
@@ -2647,13 +2598,13 @@ static void enqueue_buckets(MsmContext* ctx, Workspace& ws, void* d_out, const v
         if (v >= 2 && v <= 8) lgc = lgc_lo = v;
     }
     const size_t nchunk = (set_cap + ((size_t)1 << lgc_lo) - 1) >> lgc_lo;
-    ws.buckets.ensure(nsets * (nb + nchunk));
+    HIP_TRY(ws.buckets.try_ensure(nsets * (nb + nchunk)));
     const size_t n1 = (nb + 1) / 2, n2 = (n1 + GRP - 1) / GRP;  // level 0 folds at least 2, later levels GRP
-    ws.lvlA[0].ensure(nsets * n1);
-    ws.lvlM[0].ensure(nsets * n1);
-    ws.lvlA[1].ensure(nsets * n2);
-    ws.lvlM[1].ensure(nsets * n2);
-    ws.heavy.ensure(nsets * nb);
+    HIP_TRY(ws.lvlA[0].try_ensure(nsets * n1));
+    HIP_TRY(ws.lvlM[0].try_ensure(nsets * n1));
+    HIP_TRY(ws.lvlA[1].try_ensure(nsets * n2));
+    HIP_TRY(ws.lvlM[1].try_ensure(nsets * n2));
+    HIP_TRY(ws.heavy.try_ensure(nsets * nb));
     // lanes the accumulation wants per set: 90 % of two waves per SIMD over the sets of a launch
     const ChunkSel csel{lgc_lo, lgc, (u32)(118000 / nsets)};
     // two-level sort: coarse bins must fit the LDS counters and a point index 24 bits
@@ -2668,17 +2619,17 @@ static void enqueue_buckets(MsmContext* ctx, Workspace& ws, void* d_out, const v
                            (nb >> fb) * nsets <= MAX_BINS &&
                            npoints * nbatch >= ((size_t)1 << 15);  // below: four more launches than they save
     if (two_level) {
-        ws.tmp.ensure(nsets * set_cap);
-        ws.bins.ensure(3 * MAX_BINS + 8);
+        HIP_TRY(ws.tmp.try_ensure(nsets * set_cap));
+        HIP_TRY(ws.bins.try_ensure(3 * MAX_BINS + 8));
         // per-workgroup histograms and run starts of the partition pass (1024 scalars per workgroup)
-        ws.wghist.ensure(2 * ((npoints * nbatch + 1023) / 1024) * ((nb >> fb) * nsets));
+        HIP_TRY(ws.wghist.try_ensure(2 * ((npoints * nbatch + 1023) / 1024) * ((nb >> fb) * nsets)));
     } else {
-        ws.counts.ensure(nsets * nb);
-        ws.ranks.ensure((size_t)(ctx->glv ? 2 : 1) * nwin * nbatch * npoints);
+        HIP_TRY(ws.counts.try_ensure(nsets * nb));
+        HIP_TRY(ws.ranks.try_ensure((size_t)(ctx->glv ? 2 : 1) * nwin * nbatch * npoints));
     }
     const size_t heavy_cap = nsets * set_cap / HEAVY + 1;  // a heavy bucket holds > HEAVY entries
-    ws.heavy_list.ensure(2 * heavy_cap);
-    ws.nheavy.ensure(1);
+    HIP_TRY(ws.heavy_list.try_ensure(2 * heavy_cap));
+    HIP_TRY(ws.nheavy.try_ensure(1));
     const bool use_top = nsets <= 64;  // many independent sets (batched MSMs) keep plain tree levels busy on their own
     // few chains: run the serial tails limb-parallel, one point operation per wave
     const bool wide_tail = use_top && !ctx->tune.no_wide_tail;
@@ -2709,19 +2660,19 @@ static void enqueue_buckets(MsmContext* ctx, Workspace& ws, void* d_out, const v
             int logNb = 0;
             while (((size_t)1 << logNb) < nb) ++logNb;
             top_stride = (size_t)logNb + 2;
-            ws.lvlA[0].ensure(nsets * (size_t)(((logNb + DIGIT_BITS - 1) / DIGIT_BITS) * 32));
-            ws.dense.ensure(nsets * nb);
+            HIP_TRY(ws.lvlA[0].try_ensure(nsets * (size_t)(((logNb + DIGIT_BITS - 1) / DIGIT_BITS) * 32)));
+            HIP_TRY(ws.dense.try_ensure(nsets * nb));
             if (tiled_digits) {
-                ws.lvlA[1].ensure(nsets * (nb >> 5));  // group sums
-                ws.lvlM[1].ensure(nsets * (nb >> 4));  // per-tile column sums: ntiles x 32 (16-row tiles: nb / 16)
+                HIP_TRY(ws.lvlA[1].try_ensure(nsets * (nb >> 5)));  // group sums
+                HIP_TRY(ws.lvlM[1].try_ensure(nsets * (nb >> 4)));  // per-tile column sums: ntiles x 32 (16-row tiles: nb / 16)
                 const size_t cells = nsets * (size_t)(((logNb + DIGIT_BITS - 1) / DIGIT_BITS) * 32 + logNb + 2);
-                ws.wpart.ensure(cells * WSPLIT);
-                ws.wcount.ensure(cells);
+                HIP_TRY(ws.wpart.try_ensure(cells * WSPLIT));
+                HIP_TRY(ws.wcount.try_ensure(cells));
             }
         }
         if (use_top) {
-            ws.top.ensure(nsets * top_stride);
-            ws.win.ensure(nsets);
+            HIP_TRY(ws.top.try_ensure(nsets * top_stride));
+            HIP_TRY(ws.win.try_ensure(nsets));
         }
     }
     if (reserve_only) return;
@@ -2749,7 +2700,7 @@ static void enqueue_buckets(MsmContext* ctx, Workspace& ws, void* d_out, const v
         const bool keep_hist = staged && !ctx->tune.scatter_atomics;
         u32 *wg_hist = nullptr, *wg_off = nullptr;
         if (keep_hist) {
-            ws.wghist.ensure(2 * (size_t)gpart * nbins);
+            HIP_TRY(ws.wghist.try_ensure(2 * (size_t)gpart * nbins));
             wg_hist = ws.wghist.p;
             wg_off = wg_hist + (size_t)gpart * nbins;
         }
@@ -3069,8 +3020,8 @@ static void msm_run_combined_batch(MsmContext* ctx, MsmContext::CombineLane& lan
             std::lock_guard<std::mutex> lk(ctx->mu);  // enqueue only: the wait below runs beside the other lane's enqueue
             if (!lane.st) HIP_TRY(hipStreamCreateWithFlags(&lane.st, hipStreamNonBlocking));
             if (!lane.h_out) HIP_TRY(hipHostMalloc((void**)&lane.h_out, MsmContext::COMBINE_MAX * 144, hipHostMallocDefault));
-            lane.scalars.ensure(nb * np * 8 + 8);
-            lane.out.ensure(nb * 3 + 3);
+            HIP_TRY(lane.scalars.try_ensure(nb * np * 8 + 8));
+            HIP_TRY(lane.out.try_ensure(nb * 3 + 3));
             try {
                 bool all_slots = true;
                 for (size_t j = 0; j < nb; ++j) all_slots = all_slots && batch[j]->slot != nullptr;
@@ -3133,15 +3084,15 @@ void msm_run_host(MsmContext* ctx, void* out, const void* scalars, size_t npoint
     std::lock_guard<std::mutex> lk(ctx->mu);
     DeviceGuard on_device(ctx->device);
     HIP_TRY(on_device.err);
-    ctx->ws.scalars.ensure(nbatch * npoints * 8 + 8);
-    ctx->ws.out.ensure(nbatch * 3 + 3);
+    HIP_TRY(ctx->ws.scalars.try_ensure(nbatch * npoints * 8 + 8));
+    HIP_TRY(ctx->ws.out.try_ensure(nbatch * 3 + 3));
     if (npoints * nbatch)
         HIP_TRY(hipMemcpyAsync(ctx->ws.scalars.p, scalars, nbatch * npoints * 32, hipMemcpyHostToDevice, ctx->stream));
     if (!ctx->prepared && npoints > 0) {
         // variable-base engine: the ~255 Horner doublings are one serial chain; a CPU core runs that chain
         // several times faster than a single GPU lane, and the result goes to the host anyway
         const int nwin = ctx->nwin;
-        ctx->ws.out.ensure(nbatch * (size_t)nwin * 3);
+        HIP_TRY(ctx->ws.out.try_ensure(nbatch * (size_t)nwin * 3));
         msm_enqueue(ctx, ctx->ws.out.p, ctx->ws.scalars.p, npoints, nbatch, 1, ctx->stream, OUT_WINDOWS);
         std::vector<blst_p1> win(nbatch * (size_t)nwin);
         HIP_TRY(hipMemcpyAsync(win.data(), ctx->ws.out.p, win.size() * 144, hipMemcpyDeviceToHost, ctx->stream));

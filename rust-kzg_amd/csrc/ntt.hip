@@ -394,9 +394,9 @@ void upload_plan(NttCtx* ctx, int kind, int T) {
         pd.rd[r][5] = (u32)(pl.rounds[r].part | pl.rounds[r].unit << 1 | pl.rounds[r].twist << 2);
     }
     // tab[..][4] of u16 = {idxA, idxB, lds(idxA), lds(idxB)} is read as uint2 {idxA | idxB << 16, ldsA | ldsB << 16}
-    DEV_TRY(hipMalloc(&pd.d_tab, pl.tab.size() * sizeof(uint16_t)));
-    DEV_TRY(hipMemcpy(pd.d_tab, pl.tab.data(), pl.tab.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-    ctx->plans[kind * 16 + T] = pd;
+    pd.d_tab.ensure(pl.tab.size() * sizeof(uint16_t));
+    DEV_TRY(hipMemcpy(pd.d_tab.p, pl.tab.data(), pl.tab.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
+    ctx->plans[kind * 16 + T] = std::move(pd);
 }
 
 void launch_pass(NttCtx* ctx, int kind, int T, Fr* d_out, const Fr* d_in, PassParams& P, unsigned grid, hipStream_t stream) {
@@ -412,7 +412,7 @@ void launch_pass(NttCtx* ctx, int kind, int T, Fr* d_out, const Fr* d_in, PassPa
         P.rd[r].barrier = pd.rd[r][4];
         P.rd[r].flags = pd.rd[r][5];
     }
-    P.tab = (const uint2*)pd.d_tab;
+    P.tab = (const uint2*)pd.d_tab.p;
     const size_t lds = (size_t)TILE * sizeof(u32) * fr29::L;
 #define KZG_LAUNCH(K, V) hipLaunchKernelGGL((k_ntt_pass<K, V>), dim3(grid), dim3(NT), lds, stream, d_out, d_in, P)
 #define KZG_LAUNCH_V(K) KZG_LAUNCH(K, 1)
@@ -447,14 +447,14 @@ void ntt_enqueue(NttCtx* ctx, Fr* d_out, const Fr* d_in, size_t n, size_t nbatch
     // (n^-1 in blst Montgomery form) * 2^5
     if (mode == SCALE_INV_TWIST) {
         P.epilogue = 2;
-        P.post = (const Fe*)ctx->d_roots;  // roots_of_unity[i] * 2^261, natural order, W + 1 entries
+        P.post = (const Fe*)ctx->d_roots.p;  // roots_of_unity[i] * 2^261, natural order, W + 1 entries
         P.post_stride = (u32)(ctx->W / (2 * n));
     } else if (inverse || mode == SCALE_FWD_NINV) {
         P.epilogue = 1;
         P.scale = times32(inv_len(n));
     }
     P.total = n * nbatch;
-    P.tw = (const Fe*)(inverse ? ctx->d_tw_inv : ctx->d_tw_fwd);
+    P.tw = (const Fe*)(inverse ? ctx->d_tw_inv.p : ctx->d_tw_fwd.p);
     if (logn <= LOGT) {
         // the whole transform in one pass; a tile takes 4096 / n consecutive transforms
         P.last = 1;
@@ -520,8 +520,8 @@ void* kzgamd::ntt_create(unsigned scale, const kzgamd::Options& opt) {
         // the butterflies multiply with (36 bytes per root instead of 32, ~27 instructions less per butterfly)
         std::vector<Fe> tw(ctx->W + 1);
         for (size_t i = 0; i <= ctx->W; ++i) tw[i] = fr29::unpack(times32(ctx->roots[i]));
-        DEV_TRY(hipMalloc(&ctx->d_roots, (ctx->W + 1) * sizeof(Fe)));
-        DEV_TRY(hipMemcpy(ctx->d_roots, tw.data(), (ctx->W + 1) * sizeof(Fe), hipMemcpyHostToDevice));
+        ctx->d_roots.ensure((ctx->W + 1) * sizeof(Fe));
+        DEV_TRY(hipMemcpy(ctx->d_roots.p, tw.data(), (ctx->W + 1) * sizeof(Fe), hipMemcpyHostToDevice));
         // stage-major copies for the butterfly kernels: [(2^s - 1) + j] = w_{2^(s+1)}^j = roots[j * (W >> (s+1))],
         // s < scale, and the same with the inverse roots (roots[W - idx]); W - 1 entries each
         if (scale > 0) {
@@ -532,10 +532,10 @@ void* kzgamd::ntt_create(unsigned scale, const kzgamd::Options& opt) {
                     sm[((size_t)1 << s) - 1 + j] = tw[idx];
                     smi[((size_t)1 << s) - 1 + j] = tw[ctx->W - idx];
                 }
-            DEV_TRY(hipMalloc(&ctx->d_tw_fwd, ctx->W * sizeof(Fe)));
-            DEV_TRY(hipMalloc(&ctx->d_tw_inv, ctx->W * sizeof(Fe)));
-            DEV_TRY(hipMemcpy(ctx->d_tw_fwd, sm.data(), ctx->W * sizeof(Fe), hipMemcpyHostToDevice));
-            DEV_TRY(hipMemcpy(ctx->d_tw_inv, smi.data(), ctx->W * sizeof(Fe), hipMemcpyHostToDevice));
+            ctx->d_tw_fwd.ensure(ctx->W * sizeof(Fe));
+            ctx->d_tw_inv.ensure(ctx->W * sizeof(Fe));
+            DEV_TRY(hipMemcpy(ctx->d_tw_fwd.p, sm.data(), ctx->W * sizeof(Fe), hipMemcpyHostToDevice));
+            DEV_TRY(hipMemcpy(ctx->d_tw_inv.p, smi.data(), ctx->W * sizeof(Fe), hipMemcpyHostToDevice));
         }
         // every plan the passes can ask for (35 tables of <= 48 KiB), built once: launches never allocate
         for (int T = 0; T <= nttplan::LOGT; ++T) upload_plan(ctx, KIND_A1, T);
@@ -589,19 +589,19 @@ void run_combined_batch(NttCtx* ctx, NttCtx::CombLane& lane, const std::vector<N
         kzgamd::DeviceGuard on_device(ctx->device);
         DEV_TRY(on_device.err);
         // each on its own test: an allocation that failed is tried again by the next batch, not taken for made
-        const size_t cap = NttCtx::COMB_MAX * NttCtx::COMB_NMAX * sizeof(Fr);
+        const size_t cap = NttCtx::COMB_MAX * NttCtx::COMB_NMAX;
         if (!lane.st) DEV_TRY(hipStreamCreateWithFlags(&lane.st, hipStreamNonBlocking));
-        if (!lane.d_in) DEV_TRY(hipMalloc(&lane.d_in, cap));
-        if (!lane.d_out) DEV_TRY(hipMalloc(&lane.d_out, cap));
-        if (!lane.d_tmp) DEV_TRY(hipMalloc(&lane.d_tmp, cap));
+        lane.d_in.ensure(cap);
+        lane.d_out.ensure(cap);
+        lane.d_tmp.ensure(cap);
         SlotPtrs sp;
         for (size_t j = 0; j < NttCtx::COMB_MAX; ++j) sp.p[j] = j < nb ? (uint4*)batch[j]->slot : nullptr;
         const size_t per = n * 2, total = nb * per;  // 16-byte words per request
         const unsigned grid = (unsigned)((total + 255) / 256);
-        hipLaunchKernelGGL(k_slots_gather, dim3(grid), dim3(256), 0, lane.st, (uint4*)lane.d_in, sp, per, nb);
-        if (kind == 2) das_enqueue(ctx, lane.d_out, lane.d_in, lane.d_tmp, n, nb, lane.st);
-        else ntt_enqueue(ctx, lane.d_out, lane.d_in, n, nb, kind == 1, lane.st);
-        hipLaunchKernelGGL(k_slots_scatter, dim3(grid), dim3(256), 0, lane.st, sp, (const uint4*)lane.d_out, per, nb);
+        hipLaunchKernelGGL(k_slots_gather, dim3(grid), dim3(256), 0, lane.st, (uint4*)lane.d_in.p, sp, per, nb);
+        if (kind == 2) das_enqueue(ctx, lane.d_out.p, lane.d_in.p, lane.d_tmp.p, n, nb, lane.st);
+        else ntt_enqueue(ctx, lane.d_out.p, lane.d_in.p, n, nb, kind == 1, lane.st);
+        hipLaunchKernelGGL(k_slots_scatter, dim3(grid), dim3(256), 0, lane.st, sp, (const uint4*)lane.d_out.p, per, nb);
         DEV_TRY(hipGetLastError());
         DEV_TRY(hipStreamSynchronize(lane.st));
     } catch (const kzgamd::DevErr& e) {
@@ -646,9 +646,9 @@ extern "C" int ntt_fr(void* vctx, blst_fr* out, const blst_fr* in, size_t n, int
         kzgamd::DeviceGuard on_device(ctx->device);
         DEV_TRY(on_device.err);
         ctx->ensure(n);
-        DEV_TRY(hipMemcpyAsync(ctx->d_a, in, n * sizeof(Fr), hipMemcpyHostToDevice, ctx->stream));
-        ntt_enqueue(ctx, ctx->d_b, ctx->d_a, n, 1, inverse != 0, ctx->stream);
-        DEV_TRY(hipMemcpyAsync(out, ctx->d_b, n * sizeof(Fr), hipMemcpyDeviceToHost, ctx->stream));
+        DEV_TRY(hipMemcpyAsync(ctx->d_a.p, in, n * sizeof(Fr), hipMemcpyHostToDevice, ctx->stream));
+        ntt_enqueue(ctx, ctx->d_b.p, ctx->d_a.p, n, 1, inverse != 0, ctx->stream);
+        DEV_TRY(hipMemcpyAsync(out, ctx->d_b.p, n * sizeof(Fr), hipMemcpyDeviceToHost, ctx->stream));
         DEV_TRY(hipStreamSynchronize(ctx->stream));
     } catch (const kzgamd::DevErr& e) {
         return kzgamd::dev_code(e.e);
@@ -670,9 +670,9 @@ void das_enqueue(NttCtx* ctx, Fr* d_odds, const Fr* d_evens, Fr* d_tmp, size_t n
         memset(&P, 0, sizeof(P));
         P.n = (u32)n;
         P.total = n * nbatch;
-        P.tw = (const Fe*)ctx->d_tw_inv;
-        P.tw2 = (const Fe*)ctx->d_tw_fwd;
-        P.post = (const Fe*)ctx->d_roots;
+        P.tw = (const Fe*)ctx->d_tw_inv.p;
+        P.tw2 = (const Fe*)ctx->d_tw_fwd.p;
+        P.post = (const Fe*)ctx->d_roots.p;
         P.post_stride = (u32)(ctx->W / (2 * n));
         P.epilogue = 1;
         P.scale = times32(inv_len(n));
@@ -701,9 +701,9 @@ extern "C" int das_fft_extension(void* vctx, blst_fr* odds, const blst_fr* evens
         kzgamd::DeviceGuard on_device(ctx->device);
         DEV_TRY(on_device.err);
         ctx->ensure(2 * n);
-        DEV_TRY(hipMemcpyAsync(ctx->d_a, evens, n * sizeof(Fr), hipMemcpyHostToDevice, ctx->stream));
-        das_enqueue(ctx, ctx->d_a + n, ctx->d_a, ctx->d_b, n, 1, ctx->stream);
-        DEV_TRY(hipMemcpyAsync(odds, ctx->d_a + n, n * sizeof(Fr), hipMemcpyDeviceToHost, ctx->stream));
+        DEV_TRY(hipMemcpyAsync(ctx->d_a.p, evens, n * sizeof(Fr), hipMemcpyHostToDevice, ctx->stream));
+        das_enqueue(ctx, ctx->d_a.p + n, ctx->d_a.p, ctx->d_b.p, n, 1, ctx->stream);
+        DEV_TRY(hipMemcpyAsync(odds, ctx->d_a.p + n, n * sizeof(Fr), hipMemcpyDeviceToHost, ctx->stream));
         DEV_TRY(hipStreamSynchronize(ctx->stream));
     } catch (const kzgamd::DevErr& e) {
         return kzgamd::dev_code(e.e);

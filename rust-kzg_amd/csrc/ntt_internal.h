@@ -13,10 +13,22 @@
 
 // device copy of one tile plan (ntt_plan.h): the per-thread element table of every round + per-round constants
 struct NttPlanDev {
-    void* d_tab = nullptr;
+    kzgamd::DevBuf d_tab;
     int nrounds = 0;
     unsigned rd[12][6];  // element bit, its LDS position bit, pos, M, barrier_after, flags (fused DAS plans)
 };
+
+namespace kzgamd {
+struct Options;
+// one scalar (a root, n^-1, an FK20 coefficient) split for the two lanes of a G1 scalar multiplication: the 127-bit
+// magnitudes of its GLV halves (glv.hip.h) and their signs
+struct RootSplit {
+    ff::u32 k[2][4];
+    ff::u32 neg[2];
+    ff::u32 pad[2];
+};
+static_assert(sizeof(RootSplit) == 48, "RootSplit");
+}  // namespace kzgamd
 
 struct NttCtx {
     using Fr = ff::Fr;
@@ -24,17 +36,16 @@ struct NttCtx {
     int device = 0;
     unsigned scale = 0;
     size_t W = 0;
-    void* d_roots = nullptr;  // W + 1 twiddles in the 2^261 domain as 9 x 29-bit limbs (Fr transforms), natural order
-    void *d_tw_fwd = nullptr, *d_tw_inv = nullptr;  // the same, stage-major (forward roots / inverse roots)
+    kzgamd::DevBuf d_roots;  // W + 1 twiddles in the 2^261 domain as 9 x 29-bit limbs (Fr transforms), natural order
+    kzgamd::DevBuf d_tw_fwd, d_tw_inv;  // the same, stage-major (forward roots / inverse roots)
     std::vector<Fr> roots;  // host copy, blst Montgomery form
     hipStream_t stream = nullptr;
     std::mutex mu;
-    Fr *d_a = nullptr, *d_b = nullptr;
-    size_t cap = 0;
+    kzgamd::DevArray<Fr> d_a, d_b;
     // G1-valued transforms (fftg1.hip): the roots as GLV-split scalars, staging and work buffers
-    void* d_kroots = nullptr;  // (W + 1) x RootSplit
-    void *d_p1 = nullptr, *d_pts = nullptr, *d_tab = nullptr;
-    size_t cap_g1 = 0, cap_tab = 0;
+    kzgamd::DevArray<kzgamd::RootSplit> d_kroots;  // W + 1
+    kzgamd::DevBuf d_p1, d_pts, d_tab;  // blst_p1 / g1::Xyzz, in bytes
+    size_t cap_g1 = 0;                  // points d_p1 / d_pts hold
     // G1 stages (fftg1.hip) by their number of half-butterflies: up to g1_wide_max a wave each (limb-parallel), up to
     // g1_quad_max four lanes each, up to g1_pair_max two lanes each, one lane each above
     // (tuning keys g1_wide_max / g1_quad_max / g1_pair_max, read at creation; 0 disables a form)
@@ -58,7 +69,7 @@ struct NttCtx {
     static constexpr int COMB_SLOTS = 40, COMB_LANES = 2;
     struct CombLane {
         hipStream_t st = nullptr;
-        Fr *d_in = nullptr, *d_out = nullptr, *d_tmp = nullptr;  // COMB_MAX x COMB_NMAX elements each
+        kzgamd::DevArray<Fr> d_in, d_out, d_tmp;  // COMB_MAX x COMB_NMAX elements each
     };
     kzgamd::CombineQueue<HostCall> comb;  // COMB_LANES leaders, batches of COMB_MAX, no gather wait
     CombLane lanes[COMB_LANES];
@@ -66,47 +77,19 @@ struct NttCtx {
     bool combine = true;  // tuning key combine
 
     ~NttCtx() {
-        for (auto& l : lanes) {
-            if (l.d_in) (void)hipFree(l.d_in);
-            if (l.d_out) (void)hipFree(l.d_out);
-            if (l.d_tmp) (void)hipFree(l.d_tmp);
+        for (auto& l : lanes)
             if (l.st) (void)hipStreamDestroy(l.st);
-        }
-        if (d_roots) (void)hipFree(d_roots);
-        if (d_tw_fwd) (void)hipFree(d_tw_fwd);
-        if (d_tw_inv) (void)hipFree(d_tw_inv);
-        if (d_a) (void)hipFree(d_a);
-        if (d_b) (void)hipFree(d_b);
-        if (d_kroots) (void)hipFree(d_kroots);
-        if (d_p1) (void)hipFree(d_p1);
-        if (d_pts) (void)hipFree(d_pts);
-        if (d_tab) (void)hipFree(d_tab);
         if (stream) (void)hipStreamDestroy(stream);
-        for (auto& kv : plans)
-            if (kv.second.d_tab) (void)hipFree(kv.second.d_tab);
     }
     void ensure(size_t n) {
-        if (n <= cap) return;
-        if (d_a) (void)hipFree(d_a);
-        if (d_b) (void)hipFree(d_b);
-        d_a = d_b = nullptr;
-        cap = 0;
-        DEV_TRY(hipMalloc(&d_a, n * sizeof(Fr)));
-        DEV_TRY(hipMalloc(&d_b, n * sizeof(Fr)));
-        cap = n;
+        if (n <= d_a.cap && n <= d_b.cap) return;
+        kzgamd::drop_all(d_a, d_b);
+        d_a.ensure(n);
+        d_b.ensure(n);
     }
 };
 
 namespace kzgamd {
-struct Options;
-// one scalar (a root, n^-1, an FK20 coefficient) split for the two lanes of a G1 scalar multiplication: the 127-bit
-// magnitudes of its GLV halves (glv.hip.h) and their signs
-struct RootSplit {
-    ff::u32 k[2][4];
-    ff::u32 neg[2];
-    ff::u32 pad[2];
-};
-static_assert(sizeof(RootSplit) == 48, "RootSplit");
 // ntt.hip: what kzgamd_ntt_new_ex calls once the configuration is resolved (config.h); NULL on failure
 void* ntt_create(unsigned scale, const Options& opt);
 // fftg1.hip: G1 transforms of device-resident g1::Xyzz data, see there

@@ -56,9 +56,8 @@ struct PolyCtx {
     DevBuf roots, idx, tab, zc, mask;
     bool roots_ready = false;
 
-    std::vector<DevBuf*> bufs() { return {&a, &b, &c, &out, &f, &g, &xs, &pw, &sums, &flag, &roots, &idx, &tab, &zc, &mask}; }
+    std::vector<const DevBuf*> bufs() const { return {&a, &b, &c, &out, &f, &g, &xs, &pw, &sums, &flag, &roots, &idx, &tab, &zc, &mask}; }
     ~PolyCtx() {
-        for (DevBuf* d : bufs()) d->drop();
         if (st) (void)hipStreamDestroy(st);
     }
 };
@@ -73,7 +72,7 @@ inline void ntt_on_stream(PolyCtx* pc, Fr* out, const Fr* in, size_t n, size_t n
 inline size_t slice_of(PolyCtx* pc, size_t npoly, size_t bytes_per_poly) {
     size_t free_b = 0, total_b = 0, held = 0;
     DEV_TRY(hipMemGetInfo(&free_b, &total_b));
-    for (DevBuf* d : pc->bufs()) held += d->cap;
+    for (const DevBuf* d : pc->bufs()) held += d->cap;
     size_t per = (free_b + held) / 8 / (bytes_per_poly ? bytes_per_poly : 1);
     if (per == 0) per = 1;
     return per < npoly ? per : npoly;

@@ -781,25 +781,38 @@ def test_host_call_frame_maps_errors_and_releases_the_handle(tmp_path):
     body that returns one, of a void body, of DevErr{hipErrorOutOfMemory} (-102), of std::bad_alloc (-2) and of an int
     thrown through kzgamd::foreign (-1099); run_call runs the body on the handle's device with its lock held,
     synchronises once on either way out and leaves the lock free after every throwing body; DevBuf grows and drops,
-    ScopedBuf frees; create_handle gives dev_code or -4 and deletes what did not make it."""
+    ScopedBuf frees; create_handle gives dev_code or -4 and deletes what did not make it.  DevArray, the one owner of
+    device memory: typed growth in elements, freed at scope exit and once only after drop(), moves, a failed hipMalloc
+    (try_ensure returns the code and leaves the array empty), a group released as a whole before any of it is allocated
+    (drop_all), and a creation whose init throws after ensure — nothing leaks, with no destructor naming a buffer.  Built
+    with the address and undefined-behaviour sanitizers as a plain executable."""
     import shutil
 
     cxx = shutil.which("g++") or shutil.which("clang++") or "/opt/rocm/lib/llvm/bin/clang++"
     rocm = os.environ.get("ROCM_PATH", "/opt/rocm")
     src = tmp_path / "hostcall.cpp"
     src.write_text(r'''
+#include <cstdint>
 #include <cstdio>
 #include <new>
+#include <string>
+#include <utility>
 #include "host_call.h"
-// the HIP runtime of this program: every call succeeds and is counted, no device anywhere
-static int syncs = 0, frees = 0, mallocs = 0, device = 0;
+// the HIP runtime of this program: every call succeeds and is counted, no device anywhere; hipMalloc and hipFree are
+// logged in order ('M' / 'F'), and the fail_at-th hipMalloc from now (1 = the next) fails with hipErrorOutOfMemory
+static int syncs = 0, frees = 0, mallocs = 0, device = 0, fail_at = 0;
+static size_t last_bytes = 0;
+static std::string order;
 extern "C" {
 hipError_t hipGetDevice(int* d) { *d = device; return hipSuccess; }
 hipError_t hipSetDevice(int d) { device = d; return hipSuccess; }
 hipError_t hipGetLastError(void) { return hipSuccess; }
 hipError_t hipStreamSynchronize(hipStream_t) { ++syncs; return hipSuccess; }
-hipError_t hipMalloc(void** p, size_t n) { ++mallocs; *p = ::operator new(n); return hipSuccess; }
-hipError_t hipFree(void* p) { ++frees; ::operator delete(p); return hipSuccess; }
+hipError_t hipMalloc(void** p, size_t n) {
+    if (fail_at > 0 && --fail_at == 0) { order += 'X'; return hipErrorOutOfMemory; }
+    ++mallocs; order += 'M'; last_bytes = n; *p = ::operator new(n); return hipSuccess;
+}
+hipError_t hipFree(void* p) { ++frees; order += 'F'; ::operator delete(p); return hipSuccess; }
 }
 static int fails = 0;
 #define EXPECT(c) do { if (!(c)) { printf("FAILED line %d: %s\n", __LINE__, #c); ++fails; } } while (0)
@@ -811,7 +824,7 @@ struct Handle {
     bool made = false;
     static int live;
     Handle() { ++live; }
-    ~Handle() { --live; buf.drop(); }
+    ~Handle() { --live; }  // the buffer frees itself
 };
 int Handle::live = 0;
 // the handle's lock is free again: a second call would not block
@@ -862,6 +875,75 @@ int main() {
         EXPECT(s.p && mallocs == 3);
     }
     EXPECT(frees == 3);
+    // DevArray: typed growth, counted in elements
+    {
+        DevArray<uint32_t> a;
+        a.ensure(100);
+        uint32_t* first = a.p;
+        EXPECT(a.cap == 100 && last_bytes == 400 && mallocs == 4 && frees == 3);
+        a.ensure(50);
+        EXPECT(a.p == first && a.cap == 100 && mallocs == 4 && frees == 3);
+        order.clear();
+        a.ensure(200);
+        EXPECT(a.cap == 200 && last_bytes == 800 && mallocs == 5 && frees == 4 && order == "FM");
+        EXPECT(a.as<unsigned char>() == (unsigned char*)a.p);
+    }
+    EXPECT(frees == 5 && mallocs == 5);  // leaving the scope frees without drop()
+    {
+        DevArray<uint32_t> a;
+        a.ensure(4);
+        a.drop();
+        EXPECT(!a.p && a.cap == 0 && frees == 6);
+        a.drop();  // idempotent
+        EXPECT(frees == 6);
+    }
+    EXPECT(frees == 6 && mallocs == 6);  // drop() then the destructor: freed once
+    // moves
+    {
+        DevArray<uint32_t> a;
+        a.ensure(8);
+        uint32_t* block = a.p;
+        DevArray<uint32_t> b(std::move(a));
+        EXPECT(!a.p && a.cap == 0 && b.p == block && b.cap == 8 && frees == 6);
+        DevArray<uint32_t> c;
+        c.ensure(16);
+        EXPECT(mallocs == 8);
+        c = std::move(b);  // onto a full buffer: its old block goes
+        EXPECT(frees == 7 && c.p == block && c.cap == 8 && !b.p && b.cap == 0);
+    }
+    EXPECT(frees == 8 && mallocs == 8);  // the pair freed once in total
+    static_assert(!std::is_copy_constructible_v<DevArray<int>> && !std::is_copy_assignable_v<DevArray<int>>, "move-only");
+    // a failed hipMalloc
+    {
+        DevArray<uint32_t> a;
+        fail_at = 1;
+        EXPECT(a.try_ensure(10) == hipErrorOutOfMemory && a.p == nullptr && a.cap == 0);
+        a.ensure(10);
+        fail_at = 1;
+        EXPECT(a.try_ensure(20) == hipErrorOutOfMemory && a.p == nullptr && a.cap == 0);  // the old block went first
+        fail_at = 1;
+        EXPECT(status_of([&] { a.ensure(20); }) == -102 && a.p == nullptr && a.cap == 0);
+    }
+    EXPECT(frees == 9 && mallocs == 9 && fail_at == 0);
+    // a group: released as a whole before any of it is allocated
+    {
+        DevArray<uint32_t> a;
+        DevArray<unsigned char> b;
+        auto grow = [&](size_t n) -> hipError_t {
+            drop_all(a, b);
+            hipError_t e = a.try_ensure(n);
+            if (e == hipSuccess) e = b.try_ensure(n);
+            return e;
+        };
+        EXPECT(grow(4) == hipSuccess);
+        order.clear();
+        EXPECT(grow(8) == hipSuccess && order == "FFMM");
+        order.clear();
+        fail_at = 2;
+        EXPECT(grow(16) == hipErrorOutOfMemory && order == "FFMX");
+        EXPECT(a.p && a.cap == 16 && !b.p && b.cap == 0);  // the first block is still owned ...
+    }
+    EXPECT(mallocs == 14 && frees == 14);  // ... and freed once at scope exit
     EXPECT(blocks(0) == 0 && blocks(1) == 1 && blocks(256) == 1 && blocks(257) == 2 && blocks(65, 64) == 2);
     EXPECT(next_pow2(0) == 1 && next_pow2(1) == 1 && next_pow2(3) == 4 && next_pow2(4096) == 4096 && next_pow2(4097) == 8192);
     // the frame of a creation
@@ -874,12 +956,17 @@ int main() {
     err = 0;
     EXPECT(!create_handle<Handle>(5, &err, [](Handle*) { throw std::bad_alloc(); }) && err == -4);
     EXPECT(Handle::live == 1 && device == 0 && mallocs == frees);  // what did not make it was deleted
+    order.clear();
+    err = 0;
+    EXPECT(!create_handle<Handle>(5, &err, [](Handle* c) { c->buf.ensure(8); throw std::bad_alloc(); }) && err == -4);
+    EXPECT(order == "MF" && mallocs == frees && Handle::live == 1);  // ~Handle names no buffer: the member freed itself
     printf("fails %d\n", fails);
     return fails != 0;
 }
 ''')
     exe = tmp_path / "hostcall"
-    subprocess.check_call([cxx, "-O1", "-std=c++17", "-D__HIP_PLATFORM_AMD__", "-I", os.path.join(ROOT, "rust-kzg_amd", "csrc"),
+    subprocess.check_call([cxx, "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+                           "-D__HIP_PLATFORM_AMD__", "-I", os.path.join(ROOT, "rust-kzg_amd", "csrc"),
                            "-I", os.path.join(rocm, "include"), str(src), "-o", str(exe), "-lpthread"])
     res = subprocess.run([str(exe)], capture_output=True, text=True)
     assert res.returncode == 0 and "fails 0" in res.stdout, res.stdout + res.stderr

@@ -5,7 +5,8 @@ back: the reference's contract is load_trusted_setup -> use -> free_trusted_setu
 (kzg-bench/src/tests/c_bindings.rs:490-544 loads and frees a settings object per test; blst/src/eip_4844.rs:111-161).
 
 * `test_load_use_free_returns_hbm_and_host_memory`: hipMemGetInfo and the process's resident / locked host memory are
-  recorded, then 20 x (load -> commitment, proof, cells of a batch and of one blob = all three tables -> a 16-thread
+  recorded, then 20 x (load -> commitment, proof, cells of a batch and of one blob = all three tables -> one recovery,
+  one cell verification, one of two batches and one blob-proof batch verification = their buffers -> a 16-thread
   burst of single-blob calls = lanes and coalescing queues -> free); after EVERY cycle the free HBM is back within
   a few MB of the baseline and the host memory does not grow.  Two of the cycles take the default table budget (the
   full 137 + 43 + 77 GB), the others 6 GB per table so that the test stays inside its minute.
@@ -93,6 +94,14 @@ def test_load_use_free_returns_hbm_and_host_memory(kzg, oracle, oracle_settings)
             cells, proofs = kzg.compute_cells_and_kzg_proofs_batch(b"".join(blobs[:4]), 4, s)
             c1, p1 = kzg.compute_cells_and_kzg_proofs(blobs[0], s)
             assert cells[:262144] == c1 and proofs[:6144] == p1
+            # the recovery, cell-verification and batch-verification buffers: one call each
+            half = list(range(1, 128, 2))
+            rc, rp = kzg.recover_cells_and_kzg_proofs(half, b"".join(c1[2048 * i:2048 * (i + 1)] for i in half), s)
+            assert rc == c1 and rp == p1
+            one = (c0 * 128, list(range(128)), c1, p1)
+            assert kzg.verify_cell_kzg_proof_batch(*one, s) is True
+            assert kzg.verify_cell_kzg_proof_batch_many([one, one], s) == (True, [True, True])
+            assert kzg.verify_blob_kzg_proof_batch(blobs[:4], cs[:4], ps, s) is True
             if check:
                 assert [c0] + cs[1:4] == want_c and cs[0] == c0
                 assert ps == want_p and p0 == want_p[0]
