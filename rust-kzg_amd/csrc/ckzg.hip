@@ -872,10 +872,10 @@ KzgAmdSettings* make_lane(KzgAmdSettings* parent) {
     ln->apply_options(parent->opt);
     ln->device = parent->device;
     kzgamd::DeviceGuard on_device(parent->device);
-    CK_HIP(on_device.err);
+    DEV_TRY(on_device.err);
     // ONE stream per lane: the runtime deals streams round-robin onto its (by default four) hardware queues, and a
     // second, idle stream per lane would put every lane's working stream on the same two queues
-    CK_HIP(hipStreamCreateWithFlags(&ln->stream, hipStreamNonBlocking));
+    DEV_TRY(hipStreamCreateWithFlags(&ln->stream, hipStreamNonBlocking));
     ln->stream2 = ln->stream;
     ln->msm = parent->msm;
     // the MSM workspace of this lane's stream, sized now for every batch size a lane runs: no call on a lane allocates
@@ -958,10 +958,10 @@ void load_impl(CKZGSettings* out, const uint8_t* g1_mono, size_t n1m, const uint
     (void)hipGetDevice(&cur_dev);
     kzgamd::DeviceGuard placed(opt.device >= 0 ? opt.device : cur_dev);  // the caller's device is restored on return
     try {
-        CK_HIP(placed.err);
-        CK_HIP(hipGetDevice(&dev->device));
+        DEV_TRY(placed.err);
+        DEV_TRY(hipGetDevice(&dev->device));
         dev->slots.emplace(BYTES_PER_BLOB, KzgAmdSettings::NSLOTS, kzgamd::SlotGrowth::AllAtOnce, kzgamd::PinnedMapped{dev->device});
-        CK_HIP(hipStreamCreateWithFlags(&dev->stream, hipStreamNonBlocking));
+        DEV_TRY(hipStreamCreateWithFlags(&dev->stream, hipStreamNonBlocking));
         // stream2 carries the long one-lane latency chains that nothing waits for until the end of a call (the
         // commitment checks of a proof batch: 1.9 ms): a low-priority stream gets a hardware queue of its own — on a
         // queue shared with a pipeline stream it held that stream's chunk back until it was done (kernel trace of a
@@ -969,7 +969,7 @@ void load_impl(CKZGSettings* out, const uint8_t* g1_mono, size_t n1m, const uint
         {
             int least = 0, greatest = 0;
             if (hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess) least = 0;
-            CK_HIP(hipStreamCreateWithPriority(&dev->stream2, hipStreamNonBlocking, least));
+            DEV_TRY(hipStreamCreateWithPriority(&dev->stream2, hipStreamNonBlocking, least));
         }
         // bytes: [0,N) monomial, [N,2N) Lagrange in bit-reversed order (reverse_bit_order, eip_4844.rs:1070)
         std::vector<uint8_t> stage(2 * N * 48);
@@ -979,33 +979,33 @@ void load_impl(CKZGSettings* out, const uint8_t* g1_mono, size_t n1m, const uint
         DevArray<AffPt> d_pts;
         DevArray<int> d_bad;
         DevArray<ff::Fp> d_p1;  // 2N Jacobian points
-        CK_HIP(d_bytes.try_ensure(stage.size()));
-        CK_HIP(d_pts.try_ensure(2 * N));
-        CK_HIP(d_bad.try_ensure(1));
-        CK_HIP(d_p1.try_ensure(2 * N * 3));
-        CK_HIP(hipMemcpyAsync(d_bytes.p, stage.data(), stage.size(), hipMemcpyHostToDevice, dev->stream));
-        CK_HIP(hipMemsetAsync(d_bad.p, 0, sizeof(int), dev->stream));
+        d_bytes.ensure(stage.size());
+        d_pts.ensure(2 * N);
+        d_bad.ensure(1);
+        d_p1.ensure(2 * N * 3);
+        DEV_TRY(hipMemcpyAsync(d_bytes.p, stage.data(), stage.size(), hipMemcpyHostToDevice, dev->stream));
+        DEV_TRY(hipMemsetAsync(d_bad.p, 0, sizeof(int), dev->stream));
         hipLaunchKernelGGL(k_uncompress, dim3((unsigned)((2 * N + 127) / 128)), dim3(128), 0, dev->stream, d_pts.p, d_bad.p,
                            d_bytes.p, 2 * N);
         hipLaunchKernelGGL(k_affpt_to_blst_p1, dim3((unsigned)((2 * N + 255) / 256)), dim3(256), 0, dev->stream, d_p1.p,
                            d_pts.p, 2 * N);
         int bad = 0;
-        CK_HIP(hipMemcpyAsync(&bad, d_bad.p, sizeof(int), hipMemcpyDeviceToHost, dev->stream));
-        CK_HIP(hipStreamSynchronize(dev->stream));
+        DEV_TRY(hipMemcpyAsync(&bad, d_bad.p, sizeof(int), hipMemcpyDeviceToHost, dev->stream));
+        DEV_TRY(hipStreamSynchronize(dev->stream));
         CK_REQUIRE(bad == 0, "Invalid G1 point in trusted setup");
 
         out->g1_values_monomial = leak_array<blst_p1>(N);
         out->g1_values_lagrange_brp = leak_array<blst_p1>(N);
-        CK_HIP(hipMemcpy(out->g1_values_monomial, d_p1.p, N * 144, hipMemcpyDeviceToHost));
-        CK_HIP(hipMemcpy(out->g1_values_lagrange_brp, d_p1.p + 3 * N, N * 144, hipMemcpyDeviceToHost));
+        DEV_TRY(hipMemcpy(out->g1_values_monomial, d_p1.p, N * 144, hipMemcpyDeviceToHost));
+        DEV_TRY(hipMemcpy(out->g1_values_lagrange_brp, d_p1.p + 3 * N, N * 144, hipMemcpyDeviceToHost));
 
         // fixed-base MSM table over the bit-reversed Lagrange points (FsKZGSettings::new ->
         // prepare_msm, blst/src/types/kzg_settings.rs:109-123)
         dev->opt.device = -1;  // dev->device names the GPU from here on
         dev->msm_owned.reset(kzgamd::msm_create(d_pts.p + N, N, true, true, true, kzgamd::G1_TRUSTED, &dev->opt));
         dev->msm = dev->msm_owned.get();
-        CK_HIP(dev->d_monomial.try_ensure(N));
-        CK_HIP(hipMemcpy(dev->d_monomial.p, d_pts.p, N * sizeof(AffPt), hipMemcpyDeviceToDevice));
+        dev->d_monomial.ensure(N);
+        DEV_TRY(hipMemcpy(dev->d_monomial.p, d_pts.p, N * sizeof(AffPt), hipMemcpyDeviceToDevice));
 
         // is_trusted_setup_in_lagrange_form (eip_4844.rs:1005-1020), the reference's own test: a file whose
         // "Lagrange" section is the monomial setup satisfies e(L_1, G2_0) == e(L_0, G2_1) (L_1 = tau * L_0).
@@ -1033,9 +1033,9 @@ void load_impl(CKZGSettings* out, const uint8_t* g1_mono, size_t n1m, const uint
             dev->brp_roots[i] = roots[reverse_bits(i, 13)];
             memcpy(&out->brp_roots_of_unity[i], &dev->brp_roots[i], 32);
         }
-        CK_HIP(dev->brp_roots_owned.try_ensure(N));
+        dev->brp_roots_owned.ensure(N);
         dev->d_brp_roots = dev->brp_roots_owned.p;
-        CK_HIP(hipMemcpy(dev->brp_roots_owned.p, dev->brp_roots.data(), N * sizeof(ff::Fr), hipMemcpyHostToDevice));
+        DEV_TRY(hipMemcpy(dev->brp_roots_owned.p, dev->brp_roots.data(), N * sizeof(ff::Fr), hipMemcpyHostToDevice));
         // FK20 columns of the settings struct (FsKZGSettings::new, blst/src/types/kzg_settings.rs:84-101): for every
         // offset < 64 the size-128 G1 transform of [ s^(N - 64 - 1 - offset - 64 i) ]_{i < 63}, identity, 64 x identity;
         // x_ext_fft_columns[row][offset] = transform[row].  This library's own cell proofs do not use them (they are
@@ -1080,7 +1080,7 @@ namespace {
 
 void commit_enqueue(KzgAmdSettings* dev, void* d_out, int* d_status, const void* d_blobs, u32* d_scalars, size_t n,
                     hipStream_t stream, int out_mode = kzgamd::OUT_COMPRESSED, const BlobPtrs* ptrs = nullptr) {
-    CK_HIP(hipMemsetAsync(d_status, 0, n * sizeof(int), stream));
+    DEV_TRY(hipMemsetAsync(d_status, 0, n * sizeof(int), stream));
     if (ptrs)  // a lane batch: one (page-locked host) pointer per blob
         hipLaunchKernelGGL(k_blob_to_scalars_ptrs, dim3((unsigned)((n * N + 255) / 256)), dim3(256), 0, stream, d_scalars,
                            d_status, *ptrs, n);
@@ -1113,10 +1113,10 @@ void prove_enqueue(KzgAmdSettings* dev, size_t off, size_t n, hipStream_t stream
     int* stat = dev->d_status.p + off;
     const u32* bl = (const u32*)(dev->d_blobs.p + off * BYTES_PER_BLOB);
     const u32* zv = (const u32*)(dev->d_z.p + off * 8);
-    CK_HIP(hipMemsetAsync(stat, 0, n * sizeof(int), stream));
+    DEV_TRY(hipMemsetAsync(stat, 0, n * sizeof(int), stream));
     if (n <= QSPLIT_MAX) {
         // a few blobs: QS workgroups per blob, two phases (k_quotient alone is 0.4 ms of latency per call)
-        CK_HIP(dev->d_qscratch.try_ensure(QSPLIT_MAX * QSCR_BYTES));
+        dev->d_qscratch.ensure(QSPLIT_MAX * QSCR_BYTES);
         hipLaunchKernelGGL(k_quotient_init, dim3(1), dim3(64), 0, stream, dev->d_qscratch.p, n);
         hipLaunchKernelGGL(k_quotient_a, dim3((unsigned)(n * QS)), dim3(QT), 0, stream, dev->d_qscratch.p, stat, bl, zv,
                            (const ff::Fr*)dev->d_brp_roots);
@@ -1198,14 +1198,14 @@ void prove_batch(KZGProof* proofs, Bytes32* ys, const Blob* blobs, const Bytes32
                  KzgAmdSettings* dev, Bytes32* zs_out, bool commitments_checked_elsewhere) {
     std::lock_guard<std::mutex> lk(dev->mu);
     kzgamd::DeviceGuard on_device(dev->device);
-    CK_HIP(on_device.err);
+    DEV_TRY(on_device.err);
     dev->ensure(n);
     std::vector<Bytes32> zbuf;
     std::vector<int> cstat;
     const bool derive = zs == nullptr;
     // The blobs are in pageable memory: the copy call below returns when they are staged (~1.5 ms for 256 blobs).
     // When the challenges have to be derived, the hashing threads are started first and run beside it.
-    if (!derive) CK_HIP(hipMemcpyAsync(dev->d_blobs.p, blobs, n * BYTES_PER_BLOB, hipMemcpyHostToDevice, dev->stream));
+    if (!derive) DEV_TRY(hipMemcpyAsync(dev->d_blobs.p, blobs, n * BYTES_PER_BLOB, hipMemcpyHostToDevice, dev->stream));
     // Commitment validity (decode + subgroup) only decides BadArgs at the end; nothing downstream depends
     // on it.  A few commitments: on the host while the GPU proves (a serial 381-bit chain is ~7x faster on
     // a CPU core than in one GPU lane); a batch: one lane each on a second stream.
@@ -1220,12 +1220,12 @@ void prove_batch(KZGProof* proofs, Bytes32* ys, const Blob* blobs, const Bytes32
     if (derive) {
         cstat.assign(n, 0);
         if (!host_check && !commitments_checked_elsewhere) {
-            CK_HIP(hipMemcpyAsync(dev->d_commit.p, commitments, n * 48, hipMemcpyHostToDevice, dev->stream2));
+            DEV_TRY(hipMemcpyAsync(dev->d_commit.p, commitments, n * 48, hipMemcpyHostToDevice, dev->stream2));
             if (device_sha) {
-                if (!dev->ev_commit) CK_HIP(hipEventCreateWithFlags(&dev->ev_commit, hipEventDisableTiming));
-                CK_HIP(hipEventRecord(dev->ev_commit, dev->stream2));
+                if (!dev->ev_commit) DEV_TRY(hipEventCreateWithFlags(&dev->ev_commit, hipEventDisableTiming));
+                DEV_TRY(hipEventRecord(dev->ev_commit, dev->stream2));
             }
-            CK_HIP(hipMemsetAsync(dev->d_cstatus.p, 0, n * sizeof(int), dev->stream2));
+            DEV_TRY(hipMemsetAsync(dev->d_cstatus.p, 0, n * sizeof(int), dev->stream2));
             // up to 512 commitments: square root and membership test limb-parallel (0.3 + 0.25 ms instead of 1.7 ms of
             // single-lane chain; a wave per point is ~9x the instructions of a lane per point, which a larger batch,
             // whose MSM hides the chain anyway, should not pay)
@@ -1261,14 +1261,14 @@ void prove_batch(KZGProof* proofs, Bytes32* ys, const Blob* blobs, const Bytes32
         for (size_t k = 0; k < nchunks; ++k) {
             const size_t off = k * chunk, cn = off + chunk <= n ? chunk : n - off;
             hipStream_t cs = dev->pipe_stream(k);
-            CK_HIP(hipMemcpyAsync(dev->d_blobs.p + off * BYTES_PER_BLOB, blobs + off, cn * BYTES_PER_BLOB, hipMemcpyHostToDevice, cs));
-            if (k < (size_t)KzgAmdSettings::NPIPE) CK_HIP(hipStreamWaitEvent(cs, dev->ev_commit, 0));
+            DEV_TRY(hipMemcpyAsync(dev->d_blobs.p + off * BYTES_PER_BLOB, blobs + off, cn * BYTES_PER_BLOB, hipMemcpyHostToDevice, cs));
+            if (k < (size_t)KzgAmdSettings::NPIPE) DEV_TRY(hipStreamWaitEvent(cs, dev->ev_commit, 0));
             launch_challenge_sha256((u32*)(dev->d_z.p + off * 8), (const u32*)(dev->d_blobs.p + off * BYTES_PER_BLOB),
                                     (const u32*)(dev->d_commit.p + off * 48), cn, dev->cfg_sha_lanes, cs);
             prove_enqueue(dev, off, cn, cs, proofs == nullptr, out_mode);
         }
         dev->pipe_join();  // dev->stream now waits for every chunk
-        CK_HIP(hipMemcpyAsync(zbuf.data(), dev->d_z.p, n * 32, hipMemcpyDeviceToHost, dev->stream));
+        DEV_TRY(hipMemcpyAsync(zbuf.data(), dev->d_z.p, n * 32, hipMemcpyDeviceToHost, dev->stream));
     } else if (derive && nth > 1 && n >= 2 * PROVE_CHUNK) {
         // blobs per pipeline chunk (median ms per call, chunk 64 / 128 / 256: 256 blobs 6.63 / 6.25 / 6.41, 512 blobs
         // 11.0 / 9.1 / 9.7, 1024 blobs 19.0 / 16.5 / 16.2)
@@ -1335,7 +1335,7 @@ void prove_batch(KZGProof* proofs, Bytes32* ys, const Blob* blobs, const Bytes32
                 std::this_thread::yield();
             for (size_t i = off; i < off + cn; ++i) all_ok = all_ok && blob_ok[i];
             if (!all_ok || copy_err.load()) break;
-            CK_HIP(hipMemcpyAsync(dev->d_z.p + off * 8, zs + off, cn * 32, hipMemcpyHostToDevice, cs[k]));
+            DEV_TRY(hipMemcpyAsync(dev->d_z.p + off * 8, zs + off, cn * 32, hipMemcpyHostToDevice, cs[k]));
             prove_enqueue(dev, off, cn, cs[k], proofs == nullptr, out_mode);
         }
         copier.join();
@@ -1357,7 +1357,7 @@ void prove_batch(KZGProof* proofs, Bytes32* ys, const Blob* blobs, const Bytes32
                 }
             };
             if (nth == 1) {
-                CK_HIP(hipMemcpyAsync(dev->d_blobs.p, blobs, n * BYTES_PER_BLOB, hipMemcpyHostToDevice, dev->stream));
+                DEV_TRY(hipMemcpyAsync(dev->d_blobs.p, blobs, n * BYTES_PER_BLOB, hipMemcpyHostToDevice, dev->stream));
                 work(0);
             } else {
                 // hash on the pool while this thread stages the blobs (pageable memory: the copy call returns when
@@ -1376,7 +1376,7 @@ void prove_batch(KZGProof* proofs, Bytes32* ys, const Blob* blobs, const Bytes32
                 } joiner{copier};
                 dev->pool->run(nth, work);
                 copier.join();
-                CK_HIP(ce);
+                DEV_TRY(ce);
             }
             for (size_t i = 0; i < n; ++i)
                 if (!blob_ok[i]) {
@@ -1385,7 +1385,7 @@ void prove_batch(KZGProof* proofs, Bytes32* ys, const Blob* blobs, const Bytes32
                     throw CkErr{C_KZG_BADARGS, "Invalid scalar"};
                 }
         }
-        CK_HIP(hipMemcpyAsync(dev->d_z.p, zs, n * 32, hipMemcpyHostToDevice, dev->stream));
+        DEV_TRY(hipMemcpyAsync(dev->d_z.p, zs, n * 32, hipMemcpyHostToDevice, dev->stream));
         prove_enqueue(dev, 0, n, dev->stream, proofs == nullptr, out_mode);
     }
     // commitment check on the host, while the GPU works (the copies below block until it is done)
@@ -1406,16 +1406,16 @@ void prove_batch(KZGProof* proofs, Bytes32* ys, const Blob* blobs, const Bytes32
     std::vector<int> status(n);
     std::vector<u32> ylimbs(n * 8);
     blst_p1 jac[HOST_COMPRESS_MAX];
-    CK_HIP(hipMemcpyAsync(status.data(), dev->d_status.p, n * sizeof(int), hipMemcpyDeviceToHost, dev->stream));
-    CK_HIP(hipMemcpyAsync(ylimbs.data(), dev->d_y.p, n * 32, hipMemcpyDeviceToHost, dev->stream));
-    if (host_compress) CK_HIP(hipMemcpyAsync(jac, dev->d_out.p, n * 144, hipMemcpyDeviceToHost, dev->stream));
-    else if (proofs) CK_HIP(hipMemcpyAsync(proofs, dev->d_out.p, n * 48, hipMemcpyDeviceToHost, dev->stream));
-    CK_HIP(hipStreamSynchronize(dev->stream));
+    DEV_TRY(hipMemcpyAsync(status.data(), dev->d_status.p, n * sizeof(int), hipMemcpyDeviceToHost, dev->stream));
+    DEV_TRY(hipMemcpyAsync(ylimbs.data(), dev->d_y.p, n * 32, hipMemcpyDeviceToHost, dev->stream));
+    if (host_compress) DEV_TRY(hipMemcpyAsync(jac, dev->d_out.p, n * 144, hipMemcpyDeviceToHost, dev->stream));
+    else if (proofs) DEV_TRY(hipMemcpyAsync(proofs, dev->d_out.p, n * 48, hipMemcpyDeviceToHost, dev->stream));
+    DEV_TRY(hipStreamSynchronize(dev->stream));
     if (zs_out) memcpy(zs_out, zs, n * 32);
     if (derive) {
         if (!host_check && !commitments_checked_elsewhere) {
-            CK_HIP(hipMemcpyAsync(cstat.data(), dev->d_cstatus.p, n * sizeof(int), hipMemcpyDeviceToHost, dev->stream2));
-            CK_HIP(hipStreamSynchronize(dev->stream2));
+            DEV_TRY(hipMemcpyAsync(cstat.data(), dev->d_cstatus.p, n * sizeof(int), hipMemcpyDeviceToHost, dev->stream2));
+            DEV_TRY(hipStreamSynchronize(dev->stream2));
         }
         for (size_t i = 0; i < n; ++i) CK_REQUIRE(cstat[i] == 0, "Invalid commitment");
     }
@@ -1538,7 +1538,7 @@ void commit_lane_batch(KzgAmdSettings* dev, const std::vector<CommitReq*>& reqs)
     const size_t n = reqs.size();
     std::lock_guard<std::mutex> lk(dev->mu);
     kzgamd::DeviceGuard on_device(dev->device);
-    CK_HIP(on_device.err);
+    DEV_TRY(on_device.err);
     dev->ensure(KzgAmdSettings::LANE_MAX_BLOBS);
     dev->ensure_pinned();
     const bool host_compress = n <= HOST_COMPRESS_MAX;
@@ -1557,8 +1557,8 @@ void commit_lane_batch(KzgAmdSettings* dev, const std::vector<CommitReq*>& reqs)
     auto enqueue_all = [&] {
         commit_enqueue(dev, dev->d_out.p, dev->d_status.p, nullptr, dev->d_scalars.p, n, dev->stream,
                        host_compress ? kzgamd::OUT_JACOBIAN : kzgamd::OUT_COMPRESSED, &ptrs);
-        CK_HIP(hipMemcpyAsync(hs, dev->d_status.p, n * sizeof(int), hipMemcpyDeviceToHost, dev->stream));
-        CK_HIP(hipMemcpyAsync(ho, dev->d_out.p, n * (host_compress ? 144 : 48), hipMemcpyDeviceToHost, dev->stream));
+        DEV_TRY(hipMemcpyAsync(hs, dev->d_status.p, n * sizeof(int), hipMemcpyDeviceToHost, dev->stream));
+        DEV_TRY(hipMemcpyAsync(ho, dev->d_out.p, n * (host_compress ? 144 : 48), hipMemcpyDeviceToHost, dev->stream));
     };
     // (Replaying this sequence as one captured graph per batch size was measured: 19.4 k vs 18.9 k commitments/s at 16
     // threads, 3 991 vs 4 040 /s for one — nothing; the call-by-call form stays.  profiles/NOTES.md §9.)
@@ -1568,7 +1568,7 @@ void commit_lane_batch(KzgAmdSettings* dev, const std::vector<CommitReq*>& reqs)
         (void)hipStreamSynchronize(dev->stream);  // whatever was enqueued still reads the callers' slots
         throw;
     }
-    CK_HIP(hipStreamSynchronize(dev->stream));
+    DEV_TRY(hipStreamSynchronize(dev->stream));
     for (size_t i = 0; i < n; ++i) {
         if (hs[i] != 0) {
             reqs[i]->rc = C_KZG_BADARGS;  // "Invalid scalar"
@@ -1613,7 +1613,7 @@ extern "C" C_KZG_RET kzgamd_blob_to_kzg_commitment_batch(KZGCommitment* out, con
         KzgAmdSettings* dev = lane.use;
         std::lock_guard<std::mutex> lk(dev->mu);
         kzgamd::DeviceGuard on_device(dev->device);
-        CK_HIP(on_device.err);
+        DEV_TRY(on_device.err);
         dev->ensure(n);
         const bool host_compress = n <= HOST_COMPRESS_MAX;
         if (n >= 2 * COMMIT_CHUNK) {
@@ -1638,23 +1638,23 @@ extern "C" C_KZG_RET kzgamd_blob_to_kzg_commitment_batch(KZGCommitment* out, con
             for (size_t k = 0; off < n; ++k) {
                 const size_t cn = k == 0 ? first : (off + chunk <= n ? chunk : n - off);
                 hipStream_t cs = dev->pipe_stream(k);
-                CK_HIP(hipMemcpyAsync(dev->d_blobs.p + off * BYTES_PER_BLOB, blobs + off, cn * BYTES_PER_BLOB, hipMemcpyHostToDevice, cs));
+                DEV_TRY(hipMemcpyAsync(dev->d_blobs.p + off * BYTES_PER_BLOB, blobs + off, cn * BYTES_PER_BLOB, hipMemcpyHostToDevice, cs));
                 commit_enqueue(dev, dev->d_out.p + off * 48, dev->d_status.p + off, dev->d_blobs.p + off * BYTES_PER_BLOB,
                                dev->d_scalars.p + off * N * 8, cn, cs, kzgamd::OUT_COMPRESSED);
                 off += cn;
             }
             dev->pipe_join();
         } else {
-            CK_HIP(hipMemcpyAsync(dev->d_blobs.p, blobs, n * BYTES_PER_BLOB, hipMemcpyHostToDevice, dev->stream));
+            DEV_TRY(hipMemcpyAsync(dev->d_blobs.p, blobs, n * BYTES_PER_BLOB, hipMemcpyHostToDevice, dev->stream));
             commit_enqueue(dev, dev->d_out.p, dev->d_status.p, dev->d_blobs.p, dev->d_scalars.p, n, dev->stream,
                            host_compress ? kzgamd::OUT_JACOBIAN : kzgamd::OUT_COMPRESSED);
         }
         std::vector<int> status(n);
         blst_p1 jac[HOST_COMPRESS_MAX];
-        CK_HIP(hipMemcpyAsync(status.data(), dev->d_status.p, n * sizeof(int), hipMemcpyDeviceToHost, dev->stream));
-        if (host_compress) CK_HIP(hipMemcpyAsync(jac, dev->d_out.p, n * 144, hipMemcpyDeviceToHost, dev->stream));
-        else CK_HIP(hipMemcpyAsync(out, dev->d_out.p, n * 48, hipMemcpyDeviceToHost, dev->stream));
-        CK_HIP(hipStreamSynchronize(dev->stream));
+        DEV_TRY(hipMemcpyAsync(status.data(), dev->d_status.p, n * sizeof(int), hipMemcpyDeviceToHost, dev->stream));
+        if (host_compress) DEV_TRY(hipMemcpyAsync(jac, dev->d_out.p, n * 144, hipMemcpyDeviceToHost, dev->stream));
+        else DEV_TRY(hipMemcpyAsync(out, dev->d_out.p, n * 48, hipMemcpyDeviceToHost, dev->stream));
+        DEV_TRY(hipStreamSynchronize(dev->stream));
         for (size_t i = 0; i < n; ++i) CK_REQUIRE(status[i] == 0, "Invalid scalar");
         if (host_compress) compress_on_host(out[0].bytes, jac, n);
     });
@@ -1683,7 +1683,7 @@ extern "C" C_KZG_RET kzgamd_blob_to_kzg_commitment_device(void* d_out, void* d_s
     if (n == 0) return C_KZG_OK;
     return guarded([&] {
         kzgamd::DeviceGuard on_device(dev->device);
-        CK_HIP(on_device.err);
+        DEV_TRY(on_device.err);
         commit_enqueue(dev, d_out, (int*)d_status, d_blobs, (u32*)d_scratch, n, (hipStream_t)stream);
     });
 }
@@ -1696,7 +1696,7 @@ extern "C" C_KZG_RET kzgamd_settings_reserve(const CKZGSettings* s, size_t n, vo
     if (n == 0) return C_KZG_OK;
     return guarded([&] {
         kzgamd::DeviceGuard on_device(dev->device);
-        CK_HIP(on_device.err);
+        DEV_TRY(on_device.err);
         {
             kzgamd::MsmLock locked(dev->msm);
             kzgamd::msm_enqueue(dev->msm, nullptr, nullptr, N, n, 0, (hipStream_t)stream, kzgamd::OUT_COMPRESSED, true);
@@ -1722,13 +1722,13 @@ extern "C" C_KZG_RET kzgamd_compute_blob_kzg_proof_device(void* d_proofs, void* 
     if (n == 0) return C_KZG_OK;
     return guarded([&] {
         kzgamd::DeviceGuard on_device(dev->device);
-        CK_HIP(on_device.err);
+        DEV_TRY(on_device.err);
         hipStream_t st = (hipStream_t)stream;
         u32* scal = (u32*)d_scratch;
         u32* z = scal + n * N * 8;
         u32* y = z + n * 8;
         int* stat = (int*)d_status;
-        CK_HIP(hipMemsetAsync(stat, 0, n * sizeof(int), st));
+        DEV_TRY(hipMemsetAsync(stat, 0, n * sizeof(int), st));
         launch_challenge_sha256(z, (const u32*)d_blobs, (const u32*)d_commitments, n, dev->cfg_sha_lanes, st);
         hipLaunchKernelGGL(k_check_commitments, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, stat,
                            (const unsigned char*)d_commitments, n);
@@ -1738,7 +1738,7 @@ extern "C" C_KZG_RET kzgamd_compute_blob_kzg_proof_device(void* d_proofs, void* 
             kzgamd::MsmLock locked(dev->msm);
             kzgamd::msm_enqueue(dev->msm, d_proofs, scal, N, n, 0, st, kzgamd::OUT_COMPRESSED);
         }
-        CK_HIP(hipGetLastError());
+        DEV_TRY(hipGetLastError());
     });
 }
 
@@ -1774,7 +1774,7 @@ void proof_lane_batch(KzgAmdSettings* root, const std::vector<ProofReq*>& reqs, 
     const C_KZG_RET rc = guarded([&] {
         std::lock_guard<std::mutex> lk(dev->mu);
         kzgamd::DeviceGuard on_device(dev->device);
-        CK_HIP(on_device.err);
+        DEV_TRY(on_device.err);
         dev->ensure(KzgAmdSettings::LANE_MAX_BLOBS);
         dev->ensure_pinned();
         constexpr size_t LB = KzgAmdSettings::LANE_MAX_BLOBS;
@@ -1797,17 +1797,17 @@ void proof_lane_batch(KzgAmdSettings* root, const std::vector<ProofReq*>& reqs, 
         try {
             hipLaunchKernelGGL(k_gather_blobs, dim3((unsigned)((n * (BYTES_PER_BLOB / 16) + 255) / 256)), dim3(256), 0, dev->stream,
                                reinterpret_cast<uint4*>(dev->d_blobs.p), ptrs, n);
-            CK_HIP(hipMemcpyAsync(dev->d_z.p, hz, n * 32, hipMemcpyHostToDevice, dev->stream));
+            DEV_TRY(hipMemcpyAsync(dev->d_z.p, hz, n * 32, hipMemcpyHostToDevice, dev->stream));
             prove_enqueue(dev, 0, n, dev->stream, false, kzgamd::OUT_JACOBIAN);
-            CK_HIP(hipMemcpyAsync(hs, dev->d_status.p, n * sizeof(int), hipMemcpyDeviceToHost, dev->stream));
-            CK_HIP(hipMemcpyAsync(hy, dev->d_y.p, n * 32, hipMemcpyDeviceToHost, dev->stream));
-            CK_HIP(hipMemcpyAsync(ho, dev->d_out.p, n * 144, hipMemcpyDeviceToHost, dev->stream));
+            DEV_TRY(hipMemcpyAsync(hs, dev->d_status.p, n * sizeof(int), hipMemcpyDeviceToHost, dev->stream));
+            DEV_TRY(hipMemcpyAsync(hy, dev->d_y.p, n * 32, hipMemcpyDeviceToHost, dev->stream));
+            DEV_TRY(hipMemcpyAsync(ho, dev->d_out.p, n * 144, hipMemcpyDeviceToHost, dev->stream));
         } catch (...) {
             (void)hipStreamSynchronize(dev->stream);  // whatever was enqueued still reads the callers' slots
             throw;
         }
         if (leader) leader->side_work();  // while the GPU works
-        CK_HIP(hipStreamSynchronize(dev->stream));
+        DEV_TRY(hipStreamSynchronize(dev->stream));
         uint8_t cb[LB * 48];
         compress_on_host(cb, reinterpret_cast<const blst_p1*>(ho), n);
         for (size_t i = 0; i < n; ++i) {

@@ -184,8 +184,8 @@ bool prepare_cell_proofs(KzgAmdSettings* dev, const CKZGSettings* cs, size_t n) 
 
 void ensure_roots8192(KzgAmdSettings* dev, const CKZGSettings* cs) {
     if (dev->d_roots8192.p) return;
-    CK_HIP(dev->d_roots8192.try_ensure(2 * N + 1));
-    CK_HIP(hipMemcpy(dev->d_roots8192.p, cs->roots_of_unity, (2 * N + 1) * sizeof(ff::Fr), hipMemcpyHostToDevice));
+    dev->d_roots8192.ensure(2 * N + 1);
+    DEV_TRY(hipMemcpy(dev->d_roots8192.p, cs->roots_of_unity, (2 * N + 1) * sizeof(ff::Fr), hipMemcpyHostToDevice));
 }
 
 // compute_cells_and_kzg_proofs (kzg/src/das.rs:244-292) for n blobs; cells / proofs may be null (not both)
@@ -193,7 +193,7 @@ void cells_and_proofs(uint8_t* cells, KZGProof* proofs, const Blob* blobs, size_
                       KzgAmdSettings* dev) {
     std::lock_guard<std::mutex> lk(dev->mu);
     kzgamd::DeviceGuard on_device(dev->device);
-    CK_HIP(on_device.err);
+    DEV_TRY(on_device.err);
     ensure_roots8192(dev, cs);
     const bool fk20 = proofs && prepare_cell_proofs(dev, cs, n);
     dev->ensure(n);
@@ -201,8 +201,8 @@ void cells_and_proofs(uint8_t* cells, KZGProof* proofs, const Blob* blobs, size_
     if (proofs && fk20) dev->ensure_fk20(n);
     if (proofs && !fk20) dev->ensure_q(n);
     hipStream_t st = dev->stream;
-    CK_HIP(hipMemcpyAsync(dev->d_blobs.p, blobs, n * BYTES_PER_BLOB, hipMemcpyHostToDevice, st));
-    CK_HIP(hipMemsetAsync(dev->d_status.p, 0, n * sizeof(int), st));
+    DEV_TRY(hipMemcpyAsync(dev->d_blobs.p, blobs, n * BYTES_PER_BLOB, hipMemcpyHostToDevice, st));
+    DEV_TRY(hipMemsetAsync(dev->d_status.p, 0, n * sizeof(int), st));
     hipLaunchKernelGGL(k_blob_to_fr_brp, dim3((unsigned)((n * N + 255) / 256)), dim3(256), 0, st, dev->d_fr_a.p, dev->d_status.p,
                        (const u32*)dev->d_blobs.p, n);
     // poly_lagrange_to_monomial: inverse NTT of the bit-reversed evaluations
@@ -222,20 +222,20 @@ void cells_and_proofs(uint8_t* cells, KZGProof* proofs, const Blob* blobs, size_
     // engine is idle during FK20 (256 blobs: 67 MB, ~2.5 ms that used to follow the proofs on the same stream).
     const bool side_copy = cells && proofs && dev->stream2 && dev->stream2 != st;
     if (side_copy) {
-        if (!dev->ev_cells) CK_HIP(hipEventCreateWithFlags(&dev->ev_cells, hipEventDisableTiming));
-        CK_HIP(hipEventRecord(dev->ev_cells, st));
+        if (!dev->ev_cells) DEV_TRY(hipEventCreateWithFlags(&dev->ev_cells, hipEventDisableTiming));
+        DEV_TRY(hipEventRecord(dev->ev_cells, st));
     }
     std::vector<int> status(n);
     try {
         if (proofs) enqueue_cell_proofs(dev, n, st, fk20);
         if (side_copy) {
-            CK_HIP(hipStreamWaitEvent(dev->stream2, dev->ev_cells, 0));
-            CK_HIP(hipMemcpyAsync(cells, dev->d_fr_ext.p, n * 2 * N * 32, hipMemcpyDeviceToHost, dev->stream2));
+            DEV_TRY(hipStreamWaitEvent(dev->stream2, dev->ev_cells, 0));
+            DEV_TRY(hipMemcpyAsync(cells, dev->d_fr_ext.p, n * 2 * N * 32, hipMemcpyDeviceToHost, dev->stream2));
         } else if (cells) {
-            CK_HIP(hipMemcpyAsync(cells, dev->d_fr_ext.p, n * 2 * N * 32, hipMemcpyDeviceToHost, st));
+            DEV_TRY(hipMemcpyAsync(cells, dev->d_fr_ext.p, n * 2 * N * 32, hipMemcpyDeviceToHost, st));
         }
-        if (proofs) CK_HIP(hipMemcpyAsync(proofs, dev->d_proofs.p, n * 128 * 48, hipMemcpyDeviceToHost, st));
-        CK_HIP(hipMemcpyAsync(status.data(), dev->d_status.p, n * sizeof(int), hipMemcpyDeviceToHost, st));
+        if (proofs) DEV_TRY(hipMemcpyAsync(proofs, dev->d_proofs.p, n * 128 * 48, hipMemcpyDeviceToHost, st));
+        DEV_TRY(hipMemcpyAsync(status.data(), dev->d_status.p, n * sizeof(int), hipMemcpyDeviceToHost, st));
     } catch (...) {
         // a copy into the caller's `cells` / `proofs` (or into `status`) may be in flight on either stream: nothing of it
         // may outlive this call
@@ -244,8 +244,8 @@ void cells_and_proofs(uint8_t* cells, KZGProof* proofs, const Blob* blobs, size_
         throw;
     }
     const hipError_t e1 = hipStreamSynchronize(st);
-    if (side_copy) CK_HIP(hipStreamSynchronize(dev->stream2));  // also on the way out of a failure: `cells` is the caller's
-    CK_HIP(e1);
+    if (side_copy) DEV_TRY(hipStreamSynchronize(dev->stream2));  // also on the way out of a failure: `cells` is the caller's
+    DEV_TRY(e1);
     for (size_t i = 0; i < n; ++i) CK_REQUIRE(status[i] == 0, "Invalid scalar");
 }
 
@@ -434,25 +434,25 @@ void decode_points_begin(KzgAmdSettings* dev, const std::vector<uint8_t>& bytes,
                          size_t ntail = 0) {
     std::lock_guard<std::mutex> lk(dev->mu);
     kzgamd::DeviceGuard on_device(dev->device);
-    CK_HIP(on_device.err);
+    DEV_TRY(on_device.err);
     dev->ensure_verify(np + ntail);
     dev->vstage = bytes;
     hipStream_t st = dev->stream2;
-    CK_HIP(hipMemcpyAsync(dev->d_vbytes.p, dev->vstage.data(), np * 48, hipMemcpyHostToDevice, st));
-    CK_HIP(hipMemsetAsync(dev->d_vstat.p, 0, (np + ntail) * sizeof(int), st));
-    CK_HIP(hipMemsetAsync(dev->d_vpts.p, 0, np * sizeof(AffPt), st));
-    if (ntail) CK_HIP(hipMemcpyAsync(dev->d_vpts.p + np, tail, ntail * sizeof(AffPt), hipMemcpyDeviceToDevice, st));
-    if (!dev->ev_decoded) CK_HIP(hipEventCreateWithFlags(&dev->ev_decoded, hipEventDisableTiming));
+    DEV_TRY(hipMemcpyAsync(dev->d_vbytes.p, dev->vstage.data(), np * 48, hipMemcpyHostToDevice, st));
+    DEV_TRY(hipMemsetAsync(dev->d_vstat.p, 0, (np + ntail) * sizeof(int), st));
+    DEV_TRY(hipMemsetAsync(dev->d_vpts.p, 0, np * sizeof(AffPt), st));
+    if (ntail) DEV_TRY(hipMemcpyAsync(dev->d_vpts.p + np, tail, ntail * sizeof(AffPt), hipMemcpyDeviceToDevice, st));
+    if (!dev->ev_decoded) DEV_TRY(hipEventCreateWithFlags(&dev->ev_decoded, hipEventDisableTiming));
     decode_check_enqueue(dev->d_vpts.p, dev->d_vstat.p, (const unsigned char*)dev->d_vbytes.p, np, st, dev->cfg_wide_check, dev->ev_decoded);
-    CK_HIP(hipGetLastError());
+    DEV_TRY(hipGetLastError());
 }
 std::vector<int> decode_points_status(KzgAmdSettings* dev, size_t np) {
     std::lock_guard<std::mutex> lk(dev->mu);
     kzgamd::DeviceGuard on_device(dev->device);
-    CK_HIP(on_device.err);
+    DEV_TRY(on_device.err);
     std::vector<int> stat(np);
-    CK_HIP(hipMemcpyAsync(stat.data(), dev->d_vstat.p, np * sizeof(int), hipMemcpyDeviceToHost, dev->stream2));
-    CK_HIP(hipStreamSynchronize(dev->stream2));
+    DEV_TRY(hipMemcpyAsync(stat.data(), dev->d_vstat.p, np * sizeof(int), hipMemcpyDeviceToHost, dev->stream2));
+    DEV_TRY(hipStreamSynchronize(dev->stream2));
     return stat;
 }
 
@@ -559,22 +559,22 @@ void verify_cells(bool* ok, const Bytes48* commitments_bytes, const uint64_t* ce
     {
         std::lock_guard<std::mutex> lk(dev->mu);
         kzgamd::DeviceGuard on_device(dev->device);
-        CK_HIP(on_device.err);
+        DEV_TRY(on_device.err);
         dev->ensure_recover(1);
         dev->ensure_vcells(n);
         ensure_roots8192(dev, cs);
         hipStream_t st = dev->stream;
-        CK_HIP(hipMemcpyAsync(dev->d_vc_cells.p, cf.data(), n * CELL_SIZE * 32, hipMemcpyHostToDevice, st));
-        CK_HIP(hipMemcpyAsync(dev->d_vc_cols.p, cols32.data(), cols32.size() * sizeof(u32), hipMemcpyHostToDevice, st));
-        CK_HIP(hipMemcpyAsync(dev->d_vc_pw.p, pws.data(), n * sizeof(ff::Fr), hipMemcpyHostToDevice, st));
+        DEV_TRY(hipMemcpyAsync(dev->d_vc_cells.p, cf.data(), n * CELL_SIZE * 32, hipMemcpyHostToDevice, st));
+        DEV_TRY(hipMemcpyAsync(dev->d_vc_cols.p, cols32.data(), cols32.size() * sizeof(u32), hipMemcpyHostToDevice, st));
+        DEV_TRY(hipMemcpyAsync(dev->d_vc_pw.p, pws.data(), n * sizeof(ff::Fr), hipMemcpyHostToDevice, st));
         hipLaunchKernelGGL(k_vcell_agg, dim3((unsigned)(CELLS_PER_EXT_BLOB * CELL_SIZE / 256)), dim3(256), 0, st, dev->d_rec[0].p,
                            (const u32*)dev->d_vc_cells.p, (const u32*)dev->d_vc_cols.p, (const ff::Fr*)dev->d_vc_pw.p);
         if (kzgamd_ntt_fr_device(dev->ntt.get(), dev->d_rec[1].p, dev->d_rec[0].p, CELL_SIZE, CELLS_PER_EXT_BLOB, 1, st) != 0)
             throw CkErr{C_KZG_ERROR, "ntt"};
         hipLaunchKernelGGL(k_vcell_interp, dim3((unsigned)CELL_SIZE), dim3((unsigned)CELLS_PER_EXT_BLOB), 0, st, dev->d_rec[2].p,
                            (const ff::Fr*)dev->d_rec[1].p, (const ff::Fr*)dev->d_roots8192.p);
-        CK_HIP(hipMemcpyAsync(interp.data(), dev->d_rec[2].p, CELL_SIZE * sizeof(ff::Fr), hipMemcpyDeviceToHost, st));
-        CK_HIP(hipStreamSynchronize(st));
+        DEV_TRY(hipMemcpyAsync(interp.data(), dev->d_rec[2].p, CELL_SIZE * sizeof(ff::Fr), hipMemcpyDeviceToHost, st));
+        DEV_TRY(hipStreamSynchronize(st));
     }
     for (size_t k = 0; k < CELL_SIZE; ++k) interp[k] = ff::to_mont(interp[k]);  // the kernels work on canonical values
     for (size_t k = 0; k < CELL_SIZE; ++k) sc[np + n + m + k] = ff::neg(interp[k]);
@@ -583,8 +583,8 @@ void verify_cells(bool* ok, const Bytes48* commitments_bytes, const uint64_t* ce
     try {
         std::lock_guard<std::mutex> lk(dev->mu);
         kzgamd::DeviceGuard on_device(dev->device);
-        CK_HIP(on_device.err);
-        CK_HIP(hipEventSynchronize(dev->ev_decoded));
+        DEV_TRY(on_device.err);
+        DEV_TRY(hipEventSynchronize(dev->ev_decoded));
         if (!dev->msm_verify) dev->msm_verify.reset(kzgamd::msm_create(dev->d_vpts.p, np, true, false, true, kzgamd::G1_TRUSTED, &dev->opt));
         else kzgamd::msm_reset_points(dev->msm_verify.get(), dev->d_vpts.p, np);
         kzgamd::msm_run_host(dev->msm_verify.get(), out, sc.data(), np, 2);
@@ -602,9 +602,9 @@ void verify_cells(bool* ok, const Bytes48* commitments_bytes, const uint64_t* ce
         if (mono_ok) {
             std::lock_guard<std::mutex> lk(dev->mu);
             kzgamd::DeviceGuard on_device(dev->device);
-            CK_HIP(on_device.err);
+            DEV_TRY(on_device.err);
             DevArray<AffPt> keep;
-            CK_HIP(keep.try_ensure(CELL_SIZE));
+            keep.ensure(CELL_SIZE);
             if (hipMemcpy(keep.p, dev->d_vpts.p + n + m, CELL_SIZE * sizeof(AffPt), hipMemcpyDeviceToDevice) == hipSuccess) dev->d_mono64 = std::move(keep);
         }
     }
@@ -649,7 +649,7 @@ void recover_cells(Cell* recovered_cells, KZGProof* recovered_proofs, const uint
     const ff::Fr* roots = reinterpret_cast<const ff::Fr*>(cs->roots_of_unity);
     std::lock_guard<std::mutex> lk(dev->mu);
     kzgamd::DeviceGuard on_device(dev->device);
-    CK_HIP(on_device.err);
+    DEV_TRY(on_device.err);
     dev->ensure(1);
     dev->ensure_cells(1);
     dev->ensure_recover(1);
@@ -663,9 +663,9 @@ void recover_cells(Cell* recovered_cells, KZGProof* recovered_proofs, const uint
         hipLaunchKernelGGL(k_fr_mul, dim3((unsigned)(E / 256)), dim3(256), 0, st, out, a, b, E);
     };
     // the provided evaluations in bit-reversed order, missing ones zero
-    CK_HIP(hipMemsetAsync(A, 0, E * sizeof(ff::Fr), st));
-    CK_HIP(hipMemcpyAsync(dev->d_rec_in.p, cf.data(), ncells * CELL_SIZE * 32, hipMemcpyHostToDevice, st));
-    CK_HIP(hipMemcpyAsync(dev->d_rec_idx.p, idx32.data(), ncells * sizeof(u32), hipMemcpyHostToDevice, st));
+    DEV_TRY(hipMemsetAsync(A, 0, E * sizeof(ff::Fr), st));
+    DEV_TRY(hipMemcpyAsync(dev->d_rec_in.p, cf.data(), ncells * CELL_SIZE * 32, hipMemcpyHostToDevice, st));
+    DEV_TRY(hipMemcpyAsync(dev->d_rec_idx.p, idx32.data(), ncells * sizeof(u32), hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(k_rec_scatter, dim3((unsigned)((ncells * CELL_SIZE + 255) / 256)), dim3(256), 0, st, A,
                        (const u32*)dev->d_rec_in.p, (const u32*)dev->d_rec_idx.p, ncells, ncells != CELLS_PER_EXT_BLOB);
     std::vector<ff::Fr> vanishing;  // must outlive the copy below
@@ -678,7 +678,7 @@ void recover_cells(Cell* recovered_cells, KZGProof* recovered_proofs, const uint
         const std::vector<ff::Fr> shortp = vanishing_from_roots(rts);
         vanishing.assign(E, ff::Fr::zero());
         for (size_t i = 0; i < shortp.size(); ++i) vanishing[i * CELL_SIZE] = shortp[i];
-        CK_HIP(hipMemcpyAsync(B, vanishing.data(), E * sizeof(ff::Fr), hipMemcpyHostToDevice, st));
+        DEV_TRY(hipMemcpyAsync(B, vanishing.data(), E * sizeof(ff::Fr), hipMemcpyHostToDevice, st));
         ntt(C, B, 0);                      // vanishing_poly_eval
         mul(A, A, C);                      // extended_evaluation_times_zero
         ntt(D, A, 1);                      // ..._coeffs
@@ -693,7 +693,7 @@ void recover_cells(Cell* recovered_cells, KZGProof* recovered_proofs, const uint
         ntt(A, D, 0);                      // its 8192 evaluations, natural order
         hipLaunchKernelGGL(k_cells_out, dim3((unsigned)(E / 256)), dim3(256), 0, st, reinterpret_cast<u32*>(dev->d_fr_ext.p),
                            (const ff::Fr*)A, (size_t)1);
-        CK_HIP(hipMemcpyAsync(recovered_cells, dev->d_fr_ext.p, E * 32, hipMemcpyDeviceToHost, st));
+        DEV_TRY(hipMemcpyAsync(recovered_cells, dev->d_fr_ext.p, E * 32, hipMemcpyDeviceToHost, st));
     } else {
         memcpy(recovered_cells, cells, E * 32);
         if (recovered_proofs) ntt(D, A, 1);  // poly_lagrange_to_monomial of the given cells (:186-188)
@@ -703,11 +703,11 @@ void recover_cells(Cell* recovered_cells, KZGProof* recovered_proofs, const uint
         ensure_roots8192(dev, cs);
         if (!dev->msm_monomial) dev->msm_monomial.reset(kzgamd::msm_create(dev->d_monomial.p, N, true, true, true, kzgamd::G1_TRUSTED, &dev->opt));
         dev->ensure_q(1);
-        CK_HIP(hipMemcpyAsync(dev->d_fr_b.p, D, N * sizeof(ff::Fr), hipMemcpyDeviceToDevice, st));
+        DEV_TRY(hipMemcpyAsync(dev->d_fr_b.p, D, N * sizeof(ff::Fr), hipMemcpyDeviceToDevice, st));
         enqueue_cell_proofs(dev, 1, st, false);
-        CK_HIP(hipMemcpyAsync(recovered_proofs, dev->d_proofs.p, CELLS_PER_EXT_BLOB * 48, hipMemcpyDeviceToHost, st));
+        DEV_TRY(hipMemcpyAsync(recovered_proofs, dev->d_proofs.p, CELLS_PER_EXT_BLOB * 48, hipMemcpyDeviceToHost, st));
     }
-    CK_HIP(hipStreamSynchronize(st));
+    DEV_TRY(hipStreamSynchronize(st));
 }
 
 // Blobs per stage of a recovery batch: the workspace is ~2.6 MB per blob, plus 16 MB of quotient vectors per blob in
@@ -759,7 +759,7 @@ void recover_cells_batch(Cell* recovered_cells, KZGProof* recovered_proofs, cons
 
     std::lock_guard<std::mutex> lk(dev->mu);
     kzgamd::DeviceGuard on_device(dev->device);
-    CK_HIP(on_device.err);
+    DEV_TRY(on_device.err);
     ensure_roots8192(dev, cs);
     const bool fk20 = recovered_proofs && prepare_cell_proofs(dev, cs, n);
     // equal stages, so that none of them is a small remainder
@@ -771,7 +771,7 @@ void recover_cells_batch(Cell* recovered_cells, KZGProof* recovered_proofs, cons
     if (recovered_proofs && !fk20) dev->ensure_q(per);
     hipStream_t st = dev->stream;
     const bool side_copy = recovered_proofs && dev->stream2 && dev->stream2 != st;
-    if (side_copy && !dev->ev_cells) CK_HIP(hipEventCreateWithFlags(&dev->ev_cells, hipEventDisableTiming));
+    if (side_copy && !dev->ev_cells) DEV_TRY(hipEventCreateWithFlags(&dev->ev_cells, hipEventDisableTiming));
     const size_t E = 2 * N;
     ff::Fr *A = dev->d_rec[0].p, *D = dev->d_rec[1].p, *Zs = dev->d_rec[2].p, *Zc = dev->d_rec[3].p;
     const RecBlob* d_info = reinterpret_cast<const RecBlob*>(dev->d_rec_info.p);
@@ -784,8 +784,8 @@ void recover_cells_batch(Cell* recovered_cells, KZGProof* recovered_proofs, cons
             if (kzgamd_ntt_fr_device(dev->ntt.get(), out, in, E, m, inverse, st) != 0) throw CkErr{C_KZG_ERROR, "ntt"};
         };
         try {
-            CK_HIP(hipMemcpyAsync(dev->d_rec_info.p, sinfo.data(), m * sizeof(RecBlob), hipMemcpyHostToDevice, st));
-            CK_HIP(hipMemcpyAsync(dev->d_rec_in.p, cells + c0, ncells * BYTES_PER_CELL, hipMemcpyHostToDevice, st));
+            DEV_TRY(hipMemcpyAsync(dev->d_rec_info.p, sinfo.data(), m * sizeof(RecBlob), hipMemcpyHostToDevice, st));
+            DEV_TRY(hipMemcpyAsync(dev->d_rec_in.p, cells + c0, ncells * BYTES_PER_CELL, hipMemcpyHostToDevice, st));
             hipLaunchKernelGGL(k_rec_vanishing, dim3((unsigned)(m * 128 / 64)), dim3(64), 0, st, Zs, Zc, d_info,
                                (const ff::Fr*)dev->d_roots8192.p, seven64, m);
             hipLaunchKernelGGL(k_rec_scatter_batch, dim3(grid), dim3(256), 0, st, A, (const u32*)dev->d_rec_in.p, d_info,
@@ -799,18 +799,18 @@ void recover_cells_batch(Cell* recovered_cells, KZGProof* recovered_proofs, cons
                                recovered_proofs ? dev->d_fr_b.p : (ff::Fr*)nullptr, m);          // reconstructed_poly_coeff
             ntt(A, D, 0);                                                                     // its evaluations, natural order
             hipLaunchKernelGGL(k_cells_out, dim3(grid), dim3(256), 0, st, reinterpret_cast<u32*>(dev->d_fr_ext.p), (const ff::Fr*)A, m);
-            CK_HIP(hipGetLastError());
+            DEV_TRY(hipGetLastError());
             uint8_t* out_cells = recovered_cells[s0 * CELLS_PER_EXT_BLOB].bytes;
-            if (side_copy) CK_HIP(hipEventRecord(dev->ev_cells, st));
+            if (side_copy) DEV_TRY(hipEventRecord(dev->ev_cells, st));
             if (recovered_proofs) enqueue_cell_proofs(dev, m, st, fk20);
             if (side_copy) {
-                CK_HIP(hipStreamWaitEvent(dev->stream2, dev->ev_cells, 0));
-                CK_HIP(hipMemcpyAsync(out_cells, dev->d_fr_ext.p, m * E * 32, hipMemcpyDeviceToHost, dev->stream2));
+                DEV_TRY(hipStreamWaitEvent(dev->stream2, dev->ev_cells, 0));
+                DEV_TRY(hipMemcpyAsync(out_cells, dev->d_fr_ext.p, m * E * 32, hipMemcpyDeviceToHost, dev->stream2));
             } else {
-                CK_HIP(hipMemcpyAsync(out_cells, dev->d_fr_ext.p, m * E * 32, hipMemcpyDeviceToHost, st));
+                DEV_TRY(hipMemcpyAsync(out_cells, dev->d_fr_ext.p, m * E * 32, hipMemcpyDeviceToHost, st));
             }
             if (recovered_proofs)
-                CK_HIP(hipMemcpyAsync(recovered_proofs + s0 * CELLS_PER_EXT_BLOB, dev->d_proofs.p, m * CELLS_PER_EXT_BLOB * 48,
+                DEV_TRY(hipMemcpyAsync(recovered_proofs + s0 * CELLS_PER_EXT_BLOB, dev->d_proofs.p, m * CELLS_PER_EXT_BLOB * 48,
                                       hipMemcpyDeviceToHost, st));
         } catch (...) {
             // a copy into the caller's buffers may be in flight on either stream: nothing of it may outlive this call
@@ -820,8 +820,8 @@ void recover_cells_batch(Cell* recovered_cells, KZGProof* recovered_proofs, cons
         }
         // the next stage overwrites the workspace; both streams drain first (also on the way out of a failure)
         const hipError_t e1 = hipStreamSynchronize(st);
-        if (side_copy) CK_HIP(hipStreamSynchronize(dev->stream2));
-        CK_HIP(e1);
+        if (side_copy) DEV_TRY(hipStreamSynchronize(dev->stream2));
+        DEV_TRY(e1);
     }
 }
 

@@ -53,16 +53,12 @@ using MsmPtr = std::unique_ptr<kzgamd::MsmContext, MsmDeleter>;
 using NttPtr = std::unique_ptr<void, NttDeleter>;
 
 
-// ---- errors (thrown across the three translation units, caught by guarded())
+// ---- the verdicts of this layer: a bad argument, a failed host allocation (thrown across the translation units, caught
+// by guarded()).  A failed device call is a kzgamd::DevErr (DEV_TRY, host_call.h), here as in every layer.
 struct CkErr {
     C_KZG_RET rc;
     std::string what;
 };
-#define CK_HIP(x)                                                                         \
-    do {                                                                                  \
-        hipError_t _e = (x);                                                              \
-        if (_e != hipSuccess) throw CkErr{C_KZG_ERROR, std::string(#x) + ": " + hipGetErrorString(_e)}; \
-    } while (0)
 #define CK_REQUIRE(cond, msg)                      \
     do {                                           \
         if (!(cond)) throw CkErr{C_KZG_BADARGS, msg}; \
@@ -197,14 +193,14 @@ struct KzgAmdSettings {
         if (nblobs <= cap_fk) return;
         cap_fk = 0;
         drop_all(d_fk_a, d_fk_b, d_fk_h, d_fk_h2);
-        CK_HIP(d_fk_a.try_ensure(nblobs * 8192));
-        CK_HIP(d_fk_b.try_ensure(nblobs * 8192));
-        CK_HIP(d_fk_h.try_ensure(nblobs * 128));
-        CK_HIP(d_fk_h2.try_ensure(nblobs * 128));
+        d_fk_a.ensure(nblobs * 8192);
+        d_fk_b.ensure(nblobs * 8192);
+        d_fk_h.ensure(nblobs * 128);
+        d_fk_h2.ensure(nblobs * 128);
         cap_fk = nblobs;
     }
     // the 128 quotient vectors per blob of the direct cell-proof path (16 MB per blob)
-    void ensure_q(size_t nblobs) { CK_HIP(d_q.try_ensure(nblobs * 128 * N * 8)); }
+    void ensure_q(size_t nblobs) { d_q.ensure(nblobs * 128 * N * 8); }
     // Lanes: the reference's callers share one settings object between rayon workers (kzg/src/eip_4844.rs:781-805).
     // A host-buffer call of a few blobs takes the first idle lane — a settings object of its own for everything a call
     // mutates (streams, staging buffers, mutex) that BORROWS the tables and engine handles of its parent — so that up to
@@ -259,8 +255,8 @@ struct KzgAmdSettings {
     unsigned char* h_res = nullptr;  // per blob: 144 B result + 32 B y + 4 B status + 4 B commitment status
     void ensure_pinned() {
         if (h_in) return;
-        CK_HIP(hipHostMalloc((void**)&h_in, LANE_MAX_BLOBS * BYTES_PER_BLOB, hipHostMallocDefault));
-        CK_HIP(hipHostMalloc((void**)&h_res, LANE_MAX_BLOBS * 256, hipHostMallocDefault));
+        DEV_TRY(hipHostMalloc((void**)&h_in, LANE_MAX_BLOBS * BYTES_PER_BLOB, hipHostMallocDefault));
+        DEV_TRY(hipHostMalloc((void**)&h_res, LANE_MAX_BLOBS * 256, hipHostMallocDefault));
     }
     // Page-locked blob slots for the callers of the coalesced entry points: a caller copies its blob into a slot on its
     // own thread (in parallel with the other callers) before it queues its request; the batch's kernels read the
@@ -314,9 +310,9 @@ struct KzgAmdSettings {
         vcap = 0;
         drop_all(d_vbytes, d_vpts, d_vstat);
         const size_t cap = np < 257 ? 257 : np;
-        CK_HIP(d_vbytes.try_ensure(cap * 48));
-        CK_HIP(d_vpts.try_ensure(cap));
-        CK_HIP(d_vstat.try_ensure(cap));
+        d_vbytes.ensure(cap * 48);
+        d_vpts.ensure(cap);
+        d_vstat.ensure(cap);
         vcap = cap;
     }
     hipStream_t pipe_stream(size_t k) {
@@ -358,9 +354,9 @@ struct KzgAmdSettings {
         cap_vc = 0;
         drop_all(d_vc_cells, d_vc_cols, d_vc_pw);
         const size_t cap = n < 128 ? 128 : n;
-        CK_HIP(d_vc_cells.try_ensure(cap * CELL_SIZE * 8));
-        CK_HIP(d_vc_cols.try_ensure(cap + 2 * CELLS_PER_BLOB + 1));
-        CK_HIP(d_vc_pw.try_ensure(cap));
+        d_vc_cells.ensure(cap * CELL_SIZE * 8);
+        d_vc_cols.ensure(cap + 2 * CELLS_PER_BLOB + 1);
+        d_vc_pw.ensure(cap);
         cap_vc = cap;
     }
     // kzgamd_verify_cell_kzg_proof_batch_many (ckzg_vcells.hip): the cells as the caller passed them, the weights
@@ -380,19 +376,19 @@ struct KzgAmdSettings {
         cap_vm = 0;
         drop_all(d_vm_cells, d_vm_w, d_vm_tab, d_vm_part, d_vm_status);
         const size_t cap = n < 128 ? 128 : n, ns = vcells_many_slices(cap);
-        CK_HIP(d_vm_cells.try_ensure(cap * CELL_SIZE * 32));
-        CK_HIP(d_vm_w.try_ensure(cap));
-        CK_HIP(d_vm_tab.try_ensure(2 * CELLS_PER_BLOB + 1 + 2 * ns + cap));
-        CK_HIP(d_vm_part.try_ensure(ns * CELL_SIZE));
-        CK_HIP(d_vm_status.try_ensure(1));
+        d_vm_cells.ensure(cap * CELL_SIZE * 32);
+        d_vm_w.ensure(cap);
+        d_vm_tab.ensure(2 * CELLS_PER_BLOB + 1 + 2 * ns + cap);
+        d_vm_part.ensure(ns * CELL_SIZE);
+        d_vm_status.ensure(1);
         cap_vm = cap;
     }
     // the coset tables and the single call's index buffer once; the per-blob buffers for nblobs blobs (kept, grown on demand)
     void ensure_recover(size_t nblobs) {
         if (!d_pow7inv.p) {
-            CK_HIP(d_rec_idx.try_ensure(128));
-            CK_HIP(d_pow7.try_ensure(2 * N));
-            CK_HIP(d_pow7inv.try_ensure(2 * N));
+            d_rec_idx.ensure(128);
+            d_pow7.ensure(2 * N);
+            d_pow7inv.ensure(2 * N);
             std::vector<ff::Fr> p(2 * N), q(2 * N);
             ff::Fr seven = ff::Fr::zero();
             seven.v[0] = 7;
@@ -403,15 +399,15 @@ struct KzgAmdSettings {
                 p[i] = ff::mul(p[i - 1], seven);
                 q[i] = ff::mul(q[i - 1], inv7);
             }
-            CK_HIP(hipMemcpy(d_pow7.p, p.data(), p.size() * sizeof(ff::Fr), hipMemcpyHostToDevice));
-            CK_HIP(hipMemcpy(d_pow7inv.p, q.data(), q.size() * sizeof(ff::Fr), hipMemcpyHostToDevice));
+            DEV_TRY(hipMemcpy(d_pow7.p, p.data(), p.size() * sizeof(ff::Fr), hipMemcpyHostToDevice));
+            DEV_TRY(hipMemcpy(d_pow7inv.p, q.data(), q.size() * sizeof(ff::Fr), hipMemcpyHostToDevice));
         }
         if (nblobs <= cap_rec) return;
         cap_rec = 0;
         drop_all(d_rec[0], d_rec[1], d_rec[2], d_rec[3], d_rec_in, d_rec_info);
-        for (int k = 0; k < 4; ++k) CK_HIP(d_rec[k].try_ensure(nblobs * 2 * N));
-        CK_HIP(d_rec_in.try_ensure(nblobs * 2 * N * 8));
-        CK_HIP(d_rec_info.try_ensure(nblobs * 8));
+        for (int k = 0; k < 4; ++k) d_rec[k].ensure(nblobs * 2 * N);
+        d_rec_in.ensure(nblobs * 2 * N * 8);
+        d_rec_info.ensure(nblobs * 8);
         cap_rec = nblobs;
     }
     std::vector<kzgamd::pairing::G2Jac> g2_monomial;  // [tau^i]G2, i < 65 (host; the pairing checks use [1])
@@ -438,26 +434,26 @@ struct KzgAmdSettings {
         if (nblobs <= cap_cells) return;
         cap_cells = 0;
         drop_all(d_fr_a, d_fr_b, d_fr_ext, d_cells, d_q, d_proofs);
-        CK_HIP(d_fr_a.try_ensure(nblobs * N));
-        CK_HIP(d_fr_b.try_ensure(nblobs * N));
-        CK_HIP(d_fr_ext.try_ensure(nblobs * 2 * N));
-        CK_HIP(d_cells.try_ensure(nblobs * 2 * N * 8));
-        CK_HIP(d_proofs.try_ensure(nblobs * 128 * 48));
+        d_fr_a.ensure(nblobs * N);
+        d_fr_b.ensure(nblobs * N);
+        d_fr_ext.ensure(nblobs * 2 * N);
+        d_cells.ensure(nblobs * 2 * N * 8);
+        d_proofs.ensure(nblobs * 128 * 48);
         cap_cells = nblobs;
     }
     void ensure(size_t nblobs) {
         if (nblobs <= cap_blobs) return;
         cap_blobs = 0;
         drop_all(d_blobs, d_scalars, d_status, d_out, d_z, d_y, d_commit, d_cstatus, d_cpts);
-        CK_HIP(d_blobs.try_ensure(nblobs * BYTES_PER_BLOB));
-        CK_HIP(d_scalars.try_ensure(nblobs * BYTES_PER_BLOB / 4));
-        CK_HIP(d_status.try_ensure(nblobs));
-        CK_HIP(d_out.try_ensure(nblobs * 144));  // 48-byte compressed results, or Jacobian for the small-batch path
-        CK_HIP(d_z.try_ensure(nblobs * 8));
-        CK_HIP(d_y.try_ensure(nblobs * 8));
-        CK_HIP(d_commit.try_ensure(nblobs * 48));
-        CK_HIP(d_cstatus.try_ensure(nblobs));
-        CK_HIP(d_cpts.try_ensure(WIDE_COMMIT_CHECK_MAX));
+        d_blobs.ensure(nblobs * BYTES_PER_BLOB);
+        d_scalars.ensure(nblobs * BYTES_PER_BLOB / 4);
+        d_status.ensure(nblobs);
+        d_out.ensure(nblobs * 144);  // 48-byte compressed results, or Jacobian for the small-batch path
+        d_z.ensure(nblobs * 8);
+        d_y.ensure(nblobs * 8);
+        d_commit.ensure(nblobs * 48);
+        d_cstatus.ensure(nblobs);
+        d_cpts.ensure(WIDE_COMMIT_CHECK_MAX);
         cap_blobs = nblobs;
     }
 };
@@ -588,15 +584,23 @@ inline bool fr_from_be32_checked(ff::Fr& out, const uint8_t* in) {  // FsFr::fro
     return borrow != 0;
 }
 
+// the text of a failed call on stderr under KZGAMD_DEBUG: read when a call fails, not once per process, so that a caller
+// (or a test) can turn the texts on for one call
+inline void debug_text(const char* what, const char* detail = nullptr) {
+    if (getenv("KZGAMD_DEBUG") != nullptr) fprintf(stderr, "kzg_mi355x: %s%s%s\n", what, detail ? ": " : "", detail ? detail : "");
+}
+
 template <class F>
 C_KZG_RET guarded(F&& f) {
     try {
         f();
         return C_KZG_OK;
     } catch (const CkErr& e) {
-        // read when a call fails, not once per process: a caller (or a test) can turn the texts on for one call
-        if (getenv("KZGAMD_DEBUG") != nullptr) fprintf(stderr, "kzg_mi355x: %s\n", e.what.c_str());
+        debug_text(e.what.c_str());
         return e.rc == C_KZG_MALLOC ? C_KZG_MALLOC : C_KZG_BADARGS;  // the reference maps every failure to BadArgs
+    } catch (const kzgamd::DevErr& e) {  // of this layer or of an engine below it (MSM, NTT, fft_g1)
+        debug_text(e.what, hipGetErrorString(e.e));
+        return C_KZG_BADARGS;
     } catch (const std::bad_alloc&) {
         return C_KZG_MALLOC;
     } catch (...) {

@@ -221,15 +221,15 @@ void many_g1(blst_p1 out[2], const Bytes48* commitments_bytes, const uint64_t* c
     {
         std::lock_guard<std::mutex> lk(dev->mu);
         kzgamd::DeviceGuard on_device(dev->device);
-        CK_HIP(on_device.err);
+        DEV_TRY(on_device.err);
         dev->ensure_recover(1);
         dev->ensure_vcells_many(n);
         if (!dev->d_roots8192.p) {
-            CK_HIP(dev->d_roots8192.try_ensure(2 * N + 1));
-            CK_HIP(hipMemcpy(dev->d_roots8192.p, cs->roots_of_unity, (2 * N + 1) * sizeof(ff::Fr), hipMemcpyHostToDevice));
+            dev->d_roots8192.ensure(2 * N + 1);
+            DEV_TRY(hipMemcpy(dev->d_roots8192.p, cs->roots_of_unity, (2 * N + 1) * sizeof(ff::Fr), hipMemcpyHostToDevice));
         }
-        CK_HIP(hipMemsetAsync(dev->d_vm_status.p, 0, sizeof(int), dev->stream));
-        CK_HIP(hipMemcpyAsync(dev->d_vm_cells.p, cells, n * BYTES_PER_CELL, hipMemcpyHostToDevice, dev->stream));
+        DEV_TRY(hipMemsetAsync(dev->d_vm_status.p, 0, sizeof(int), dev->stream));
+        DEV_TRY(hipMemcpyAsync(dev->d_vm_cells.p, cells, n * BYTES_PER_CELL, hipMemcpyHostToDevice, dev->stream));
     }
     tm[1] = ms_since(t_hash);  // the cells handed to the copy engine
     // ... and the tables of the two kernels: the cells grouped by column (a counting sort), each column cut into slices
@@ -283,22 +283,22 @@ void many_g1(blst_p1 out[2], const Bytes48* commitments_bytes, const uint64_t* c
     {
         std::lock_guard<std::mutex> lk(dev->mu);
         kzgamd::DeviceGuard on_device(dev->device);
-        CK_HIP(on_device.err);
+        DEV_TRY(on_device.err);
         hipStream_t st = dev->stream;
         const u32* d_tab = dev->d_vm_tab.p;
-        CK_HIP(hipMemcpyAsync(dev->d_vm_w.p, sc.data(), n * sizeof(ff::Fr), hipMemcpyHostToDevice, st));  // row 0 = the weights
-        CK_HIP(hipMemcpyAsync(dev->d_vm_tab.p, tab.data(), tab.size() * sizeof(u32), hipMemcpyHostToDevice, st));
+        DEV_TRY(hipMemcpyAsync(dev->d_vm_w.p, sc.data(), n * sizeof(ff::Fr), hipMemcpyHostToDevice, st));  // row 0 = the weights
+        DEV_TRY(hipMemcpyAsync(dev->d_vm_tab.p, tab.data(), tab.size() * sizeof(u32), hipMemcpyHostToDevice, st));
         hipLaunchKernelGGL(k_vcells_agg, dim3((unsigned)nslices), dim3(64), 0, st, dev->d_vm_part.p, dev->d_vm_status.p,
                            (const uint4*)dev->d_vm_cells.p, d_tab + T_SL, d_tab + T_ORD, (const ff::Fr*)dev->d_vm_w.p);
         hipLaunchKernelGGL(k_vcells_fold, dim3((unsigned)CELLS_PER_EXT_BLOB), dim3(64), 0, st, dev->d_rec[0].p,
                            (const ff::Fr*)dev->d_vm_part.p, d_tab);
-        CK_HIP(hipGetLastError());
+        DEV_TRY(hipGetLastError());
         if (kzgamd_ntt_fr_device(dev->ntt.get(), dev->d_rec[1].p, dev->d_rec[0].p, CELL_SIZE, CELLS_PER_EXT_BLOB, 1, st) != 0)
             throw CkErr{C_KZG_ERROR, "ntt"};
         vc_interp_enqueue(dev->d_rec[2].p, dev->d_rec[1].p, dev->d_roots8192.p, st);
-        CK_HIP(hipMemcpyAsync(interp.data(), dev->d_rec[2].p, CELL_SIZE * sizeof(ff::Fr), hipMemcpyDeviceToHost, st));
-        CK_HIP(hipMemcpyAsync(&status, dev->d_vm_status.p, sizeof(int), hipMemcpyDeviceToHost, st));
-        CK_HIP(hipStreamSynchronize(st));
+        DEV_TRY(hipMemcpyAsync(interp.data(), dev->d_rec[2].p, CELL_SIZE * sizeof(ff::Fr), hipMemcpyDeviceToHost, st));
+        DEV_TRY(hipMemcpyAsync(&status, dev->d_vm_status.p, sizeof(int), hipMemcpyDeviceToHost, st));
+        DEV_TRY(hipStreamSynchronize(st));
     }
     tm[4] = ms_since(t_gpu);  // weights and tables up, k_vcells_agg, k_vcells_fold, transforms, interpolation, 64 coefficients down
     CK_REQUIRE(status == 0, "Invalid scalar");
@@ -307,8 +307,8 @@ void many_g1(blst_p1 out[2], const Bytes48* commitments_bytes, const uint64_t* c
     {
         std::lock_guard<std::mutex> lk(dev->mu);
         kzgamd::DeviceGuard on_device(dev->device);
-        CK_HIP(on_device.err);
-        CK_HIP(hipEventSynchronize(dev->ev_decoded));
+        DEV_TRY(on_device.err);
+        DEV_TRY(hipEventSynchronize(dev->ev_decoded));
         if (!dev->msm_verify) dev->msm_verify.reset(kzgamd::msm_create(dev->d_vpts.p, np, true, false, true, kzgamd::G1_TRUSTED, &dev->opt));
         else kzgamd::msm_reset_points(dev->msm_verify.get(), dev->d_vpts.p, np);
         kzgamd::msm_run_host(dev->msm_verify.get(), pl, sc.data(), np, 2);
@@ -325,9 +325,9 @@ void many_g1(blst_p1 out[2], const Bytes48* commitments_bytes, const uint64_t* c
         if (mono_ok) {
             std::lock_guard<std::mutex> lk(dev->mu);
             kzgamd::DeviceGuard on_device(dev->device);
-            CK_HIP(on_device.err);
+            DEV_TRY(on_device.err);
             DevArray<AffPt> keep;
-            CK_HIP(keep.try_ensure(CELL_SIZE));
+            keep.ensure(CELL_SIZE);
             if (hipMemcpy(keep.p, dev->d_vpts.p + n + m, CELL_SIZE * sizeof(AffPt), hipMemcpyDeviceToDevice) == hipSuccess) dev->d_mono64 = std::move(keep);
         }
     }

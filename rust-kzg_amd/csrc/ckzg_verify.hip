@@ -19,7 +19,7 @@ namespace ckz {
 void verify_g1_begin(const Bytes48* commitments, const Bytes48* proofs, size_t n, KzgAmdSettings* dev) {
     std::lock_guard<std::mutex> lk(dev->mu);
     kzgamd::DeviceGuard on_device(dev->device);
-    CK_HIP(on_device.err);
+    DEV_TRY(on_device.err);
     const size_t np = 2 * n + 1;
     dev->ensure_verify(np);
     // device: [proofs | commitments | generator], decoded and checked
@@ -32,12 +32,12 @@ void verify_g1_begin(const Bytes48* commitments, const Bytes48* proofs, size_t n
         0x6c, 0x55, 0xe8, 0x3f, 0xf9, 0x7a, 0x1a, 0xef, 0xfb, 0x3a, 0xf0, 0x0a, 0xdb, 0x22, 0xc6, 0xbb};
     memcpy(dev->vstage.data() + 2 * n * 48, G1_GENERATOR_COMPRESSED, 48);
     hipStream_t st = dev->stream2;
-    CK_HIP(hipMemcpyAsync(dev->d_vbytes.p, dev->vstage.data(), dev->vstage.size(), hipMemcpyHostToDevice, st));
-    CK_HIP(hipMemsetAsync(dev->d_vstat.p, 0, np * sizeof(int), st));
-    CK_HIP(hipMemsetAsync(dev->d_vpts.p, 0, np * sizeof(AffPt), st));
-    if (!dev->ev_decoded) CK_HIP(hipEventCreateWithFlags(&dev->ev_decoded, hipEventDisableTiming));
+    DEV_TRY(hipMemcpyAsync(dev->d_vbytes.p, dev->vstage.data(), dev->vstage.size(), hipMemcpyHostToDevice, st));
+    DEV_TRY(hipMemsetAsync(dev->d_vstat.p, 0, np * sizeof(int), st));
+    DEV_TRY(hipMemsetAsync(dev->d_vpts.p, 0, np * sizeof(AffPt), st));
+    if (!dev->ev_decoded) DEV_TRY(hipEventCreateWithFlags(&dev->ev_decoded, hipEventDisableTiming));
     decode_check_enqueue(dev->d_vpts.p, dev->d_vstat.p, (const unsigned char*)dev->d_vbytes.p, np, st, dev->cfg_wide_check, dev->ev_decoded);
-    CK_HIP(hipGetLastError());
+    DEV_TRY(hipGetLastError());
 }
 }  // namespace ckz
 namespace {
@@ -55,7 +55,7 @@ void verify_g1_finish(blst_p1* proof_lincomb, blst_p1* rhs, const Bytes48* commi
     }
     std::lock_guard<std::mutex> lk(dev->mu);
     kzgamd::DeviceGuard on_device(dev->device);
-    CK_HIP(on_device.err);
+    DEV_TRY(on_device.err);
     const size_t np = 2 * n + 1;
     hipStream_t st = dev->stream2;
     // host, meanwhile: r = hash_to_bls_field(sha256(domain | 4096 | n | (C_i | z_i | y_i | proof_i)...)), powers of r
@@ -99,7 +99,7 @@ void verify_g1_finish(blst_p1* proof_lincomb, blst_p1* rhs, const Bytes48* commi
     blst_p1 out[2];
     if (scalars_ok) {
         try {
-            CK_HIP(hipEventSynchronize(dev->ev_decoded));
+            DEV_TRY(hipEventSynchronize(dev->ev_decoded));
             if (!dev->msm_verify) dev->msm_verify.reset(kzgamd::msm_create(dev->d_vpts.p, np, true, false, true, kzgamd::G1_TRUSTED, &dev->opt));
             else kzgamd::msm_reset_points(dev->msm_verify.get(), dev->d_vpts.p, np);
             kzgamd::msm_run_host(dev->msm_verify.get(), out, sc.data(), np, 2);
@@ -109,8 +109,8 @@ void verify_g1_finish(blst_p1* proof_lincomb, blst_p1* rhs, const Bytes48* commi
         }
     }
     std::vector<int> stat(np);
-    CK_HIP(hipMemcpyAsync(stat.data(), dev->d_vstat.p, np * sizeof(int), hipMemcpyDeviceToHost, st));
-    CK_HIP(hipStreamSynchronize(st));
+    DEV_TRY(hipMemcpyAsync(stat.data(), dev->d_vstat.p, np * sizeof(int), hipMemcpyDeviceToHost, st));
+    DEV_TRY(hipStreamSynchronize(st));
     CK_REQUIRE(scalars_ok, "Invalid scalar");
     for (size_t i = 0; i < np; ++i) CK_REQUIRE(stat[i] != 1, "Invalid G1 encoding");
     for (size_t i = 0; i < n; ++i) CK_REQUIRE(stat[i] == 0, "Invalid proof");

@@ -713,7 +713,7 @@ extern "C" int kzgamd_fft_g1_batch(void* vctx, blst_p1* out, const blst_p1* in, 
     if (n == 0 || (n & (n - 1))) return 2;  // "A list with power-of-two length expected"
     if (nbatch == 0) return 0;
     std::lock_guard<std::mutex> lk(ctx->mu);
-    try {
+    return kzgamd::status_of([&] {
         kzgamd::DeviceGuard on_device(ctx->device);
         DEV_TRY(on_device.err);
         const size_t total = n * nbatch, bf = total / 2;
@@ -738,10 +738,7 @@ extern "C" int kzgamd_fft_g1_batch(void* vctx, blst_p1* out, const blst_p1* in, 
         DEV_TRY(hipGetLastError());
         DEV_TRY(hipMemcpyAsync(out, ctx->d_p1.p, total * sizeof(blst_p1), hipMemcpyDeviceToHost, st));
         DEV_TRY(hipStreamSynchronize(st));
-    } catch (const kzgamd::DevErr& e) {
-        return kzgamd::dev_code(e.e);
-    }
-    return 0;
+    });
 }
 
 extern "C" int fft_g1(void* vctx, blst_p1* out, const blst_p1* in, size_t n, int inverse) {

@@ -231,10 +231,8 @@ void run_pass(Fk20Ctx* fk, blst_p1* out, const blst_fr* polys, size_t cnt, int o
         kzgamd::g1_varmul_sum_device(fk->ntt, d_h, fk->prod.p, d_tab, fk->x.p, k2 * l, (const RootSplit*)fk->sc.p, nprod, l, st);
     } else {
         // h_ext[poly][j] = sum_i scalars[poly][j][i] * X[j][i]: cnt * k2 MSMs of l points, base set j of the table
-        kzgamd::foreign([&] {
-            kzgamd::MsmLock locked(fk->msm);
-            kzgamd::msm_enqueue(fk->msm, d_h, fk->sc.p, l, npos, 1, st, kzgamd::OUT_XYZZ, false, k2);
-        });
+        kzgamd::MsmLock locked(fk->msm);
+        kzgamd::msm_enqueue(fk->msm, d_h, fk->sc.p, l, npos, 1, st, kzgamd::OUT_XYZZ, false, k2);
     }
     // h = ifft_g1(h_ext) (its k2^-1 is in the scalars), upper half cleared, proofs = fft_g1(h)
     Xyzz* h = (Xyzz*)kzgamd::fftg1_device_tab(fk->ntt, d_h, d_h2, k2, cnt, 1, st, d_tab);

@@ -1,5 +1,6 @@
-// The host-side frame of the generic handles (Poly, ZeroPoly, KZG, FK20, the NTT handle) and of the handle-less group
-// multiplication: one error type, the device buffers, and the frames a call and a handle creation run in.
+// The host side of every layer: the one error type of a failed device call and the one owner of device memory (the MSM
+// engine and the c-kzg layer included), and the frames a call and a handle creation run in for the generic handles (Poly,
+// ZeroPoly, KZG, FK20, the NTT handle) and the handle-less group multiplication.
 // Host-only: nothing here launches a kernel.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -12,17 +13,19 @@
 
 namespace kzgamd {
 
+// a failed device call, in every layer: the code, and what was being done (a string literal, never allocated)
 struct DevErr {
     hipError_t e;
+    const char* what = "";
 };
-#define DEV_TRY(x)                                     \
-    do {                                               \
-        hipError_t _e = (x);                           \
-        if (_e != hipSuccess) throw kzgamd::DevErr{_e}; \
+#define DEV_TRY(x)                                         \
+    do {                                                   \
+        hipError_t _e = (x);                               \
+        if (_e != hipSuccess) throw kzgamd::DevErr{_e, #x}; \
     } while (0)
 
 // what a call returns for a failed HIP call: -(100 + hipError_t)
-inline int dev_code(hipError_t e) { return -(int)e - 100; }
+inline int dev_code(hipError_t e) { return -(100 + (int)e); }
 
 // The one owner of device memory (every handle, every call): `cap` elements of T at `p`, grown when more are asked for,
 // freed by drop() or when the owner goes.  Move-only.  Never a member of an object with static storage duration: its
@@ -49,20 +52,15 @@ struct DevArray {
         return *this;
     }
     ~DevArray() { drop(); }
-    // for the layers with an error type of their own (HIP_TRY, CK_HIP, the hipError_t chains); after a failure the
-    // array is empty
-    [[nodiscard]] hipError_t try_ensure(size_t n) {
-        if (n <= cap) return hipSuccess;
+    // after a failure the array is empty
+    void ensure(size_t n) {
+        if (n <= cap) return;
         drop();
-        const hipError_t e = hipMalloc((void**)&p, n * sizeof(T));
-        if (e != hipSuccess) {
-            p = nullptr;
-            return e;
-        }
+        void* q = nullptr;
+        DEV_TRY(hipMalloc(&q, n * sizeof(T)));
+        p = (T*)q;
         cap = n;
-        return hipSuccess;
     }
-    void ensure(size_t n) { DEV_TRY(try_ensure(n)); }
     void drop() {
         if (p) (void)hipFree(p);
         p = nullptr;
@@ -129,19 +127,6 @@ int status_of(F&& body) {
         return dev_code(e.e);
     } catch (...) {
         return -2;
-    }
-}
-
-// a call into code that throws types of its own (msm_enqueue: HipErr): whatever it throws leaves as a DevErr, so the
-// call returns dev_code(hipErrorUnknown) = -1099
-template <class F>
-void foreign(F&& f) {
-    try {
-        f();
-    } catch (const DevErr&) {
-        throw;
-    } catch (...) {
-        throw DevErr{hipErrorUnknown};
     }
 }
 

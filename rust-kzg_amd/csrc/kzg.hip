@@ -393,10 +393,8 @@ struct KzgCtx {
 
 // nbatch MSMs of npoints scalars (Montgomery, stride npoints) over the first setup points, Jacobian out, on the stream
 void msm_on_stream(KzgCtx* kz, void* d_out, const void* d_scalars, size_t npoints, size_t nbatch) {
-    kzgamd::foreign([&] {
-        kzgamd::MsmLock locked(kz->msm);
-        kzgamd::msm_enqueue(kz->msm, d_out, d_scalars, npoints, nbatch, 1, kz->st, kzgamd::OUT_JACOBIAN);
-    });
+    kzgamd::MsmLock locked(kz->msm);
+    kzgamd::msm_enqueue(kz->msm, d_out, d_scalars, npoints, nbatch, 1, kz->st, kzgamd::OUT_JACOBIAN);
 }
 
 // the quotients and remainders of the pairs [pair0, pair0 + npairs) into kz->q (stride len - n) and kz->r (stride n)
@@ -857,10 +855,10 @@ int batch_g1(KzgCtx* kz, blst_p1 lp[2], const blst_p1* commitments, const blst_p
             hipLaunchKernelGGL(k_kzg_batch_fold, dim3(blocks(n)), dim3(256), 0, st, kz->agg.as<Fr>(), (const Fr*)part, n, nblocks);
         DEV_TRY(hipGetLastError());
         msm_on_stream(kz, out + 9, kz->agg.p, n, 1);  // [A(s)]G
-        kzgamd::foreign([&] {
+        {
             kzgamd::MsmLock locked(kz->vmsm);
             kzgamd::msm_enqueue(kz->vmsm, out + 3, kz->rows.p, np, 2, 1, st, kzgamd::OUT_JACOBIAN);  // P, row L
-        });
+        }
         hipLaunchKernelGGL(k_kzg_g1_sub, dim3(1), dim3(64), 0, st, out, (const ff::Fp*)(out + 6), (const ff::Fp*)(out + 9), (size_t)1);
         DEV_TRY(hipGetLastError());
         DEV_TRY(hipMemcpyAsync(lp, out, 2 * sizeof(blst_p1), hipMemcpyDeviceToHost, st));

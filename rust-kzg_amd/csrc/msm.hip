@@ -47,6 +47,7 @@ using g1::AffPt;
 using WidePt = g1s::WidePt30;  // the wide table's slot: x, y in the limbs of the accumulation chain (g1_30s.hip.h)
 using g1::Xyzz;
 using kzgamd::DevArray;
+using kzgamd::DevErr;
 
 namespace {
 
@@ -58,16 +59,6 @@ constexpr double FBW_DEFAULT_GB = 160.0;  // default HBM budget of one wide fixe
 // accumulation is a latency chain of `chunk` mixed additions
 
 // ---------------------------------------------------------------- helpers
-struct HipErr {
-    hipError_t e;
-    const char* what;
-};
-#define HIP_TRY(x)                                  \
-    do {                                            \
-        hipError_t _e = (x);                        \
-        if (_e != hipSuccess) throw HipErr{_e, #x}; \
-    } while (0)
-
 RustError ok_error() { return RustError{0, nullptr}; }
 RustError make_error(int code, const std::string& msg) {
     char* m = (char*)malloc(msg.size() + 1);
@@ -2128,7 +2119,7 @@ struct kzgamd::MsmContext {
         size_t npoints;
         unsigned char* slot = nullptr;
         bool failed = false;
-        HipErr err{hipSuccess, ""};
+        DevErr err{hipSuccess};
         HostCall(void* o, const void* s, size_t np) : out(o), scalars(s), npoints(np) {}
     };
     static constexpr size_t COMBINE_MAX = 32;
@@ -2175,7 +2166,7 @@ namespace kzgamd {
 static void require_device() {
     int cnt = 0;
     hipError_t e = hipGetDeviceCount(&cnt);
-    if (e != hipSuccess || cnt <= 0) throw HipErr{e == hipSuccess ? hipErrorNoDevice : e, "no gfx950 device visible"};
+    if (e != hipSuccess || cnt <= 0) throw DevErr{e == hipSuccess ? hipErrorNoDevice : e, "no gfx950 device visible"};
 }
 
 // Wide table: built tile by tile (chain of multiples as XYZZ -> batch-inverted affine slots).
@@ -2185,15 +2176,15 @@ static void build_wide_table(MsmContext* ctx) {
     const size_t nslots = (size_t)ctx->rows * ctx->n;
     const double gb = (double)nslots * (double)mults * sizeof(WidePt) / 1e9;
     if (budget_gb <= 0 || gb > budget_gb || mults < (size_t)FBW_SEG) return;
-    HIP_TRY(ctx->wide.try_ensure(nslots * mults));
+    ctx->wide.ensure(nslots * mults);
     // tile: up to 2^22 table entries at a time (XYZZ 224 B + prefix 56 B of scratch each)
     size_t tile_slots = ((size_t)1 << 22) / mults;
     if (tile_slots == 0) tile_slots = 1;
     if (tile_slots > nslots) tile_slots = nslots;
     DevArray<Xyzz> tmp;
     DevArray<fp28::Fe> pref;
-    HIP_TRY(tmp.try_ensure(tile_slots * mults));
-    HIP_TRY(pref.try_ensure(tile_slots * mults));
+    tmp.ensure(tile_slots * mults);
+    pref.ensure(tile_slots * mults);
     for (size_t s0 = 0; s0 < nslots; s0 += tile_slots) {
         const size_t ns = s0 + tile_slots <= nslots ? tile_slots : nslots - s0;
         const size_t chain_threads = ns * (mults / FBW_SEG), cnt = ns * mults;
@@ -2203,8 +2194,8 @@ static void build_wide_table(MsmContext* ctx) {
         hipLaunchKernelGGL(k_fbw_affine, dim3((unsigned)((inv_threads + 127) / 128)), dim3(128), 0, ctx->stream,
                            ctx->wide.p + s0 * mults, (const Xyzz*)tmp.p, pref.p, cnt);
     }
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    DEV_TRY(hipGetLastError());
+    DEV_TRY(hipStreamSynchronize(ctx->stream));
     tmp.drop();
     pref.drop();
     ctx->fbw = true;
@@ -2213,12 +2204,12 @@ static void build_wide_table(MsmContext* ctx) {
 // whether every one of the n bases at d_bases lies in the r-torsion subgroup (one launch on the handle's stream, awaited)
 static bool bases_in_g1(MsmContext* ctx, const AffPt* d_bases, size_t n) {
     DevArray<int> bad;
-    HIP_TRY(bad.try_ensure(1));
-    HIP_TRY(hipMemsetAsync(bad.p, 0, sizeof(int), ctx->stream));
+    bad.ensure(1);
+    DEV_TRY(hipMemsetAsync(bad.p, 0, sizeof(int), ctx->stream));
     hipLaunchKernelGGL(k_bases_in_g1, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, ctx->stream, d_bases, n, bad.p);
     int nbad = 1;
-    HIP_TRY(hipMemcpyAsync(&nbad, bad.p, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    DEV_TRY(hipMemcpyAsync(&nbad, bad.p, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    DEV_TRY(hipStreamSynchronize(ctx->stream));
     return nbad == 0;
 }
 
@@ -2233,16 +2224,16 @@ MsmContext* msm_create(const void* points, size_t n, bool points_on_device, bool
             ctx->opt = *opt;
         } else {
             std::string err;
-            if (!Options::resolve(ctx->opt, nullptr, &err)) throw HipErr{hipErrorInvalidValue, "KZGAMD_TUNING does not parse"};
+            if (!Options::resolve(ctx->opt, nullptr, &err)) throw DevErr{hipErrorInvalidValue, "KZGAMD_TUNING does not parse"};
         }
         ctx->tune = MsmTuning::from(ctx->opt);
         // the handle lives on opt.device when one is named; the caller's current device is restored on the way out
         int cur_dev = 0;
-        HIP_TRY(hipGetDevice(&cur_dev));
+        DEV_TRY(hipGetDevice(&cur_dev));
         DeviceGuard placed(ctx->opt.device >= 0 ? ctx->opt.device : cur_dev);
-        HIP_TRY(placed.err);
-        HIP_TRY(hipGetDevice(&ctx->device));
-        HIP_TRY(hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking));
+        DEV_TRY(placed.err);
+        DEV_TRY(hipGetDevice(&ctx->device));
+        DEV_TRY(hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking));
         ctx->n = n;
         ctx->prepared = prepare;
         ctx->comb.max_leaders = ctx->tune.combine_lanes;
@@ -2275,15 +2266,15 @@ MsmContext* msm_create(const void* points, size_t n, bool points_on_device, bool
         if (!ctx->glv) as_variable = false;
         // the bases first (row 0 of the table; the variable-base engine appends the [x^2]P images)
         DevArray<AffPt> row0;
-        HIP_TRY(row0.try_ensure(ctx->glv ? 2 * n : n));
+        row0.ensure(ctx->glv ? 2 * n : n);
         DevArray<ff::Fp> staging;
         const ff::Fp* src = (const ff::Fp*)points;
         if (!points_are_affpt && !points_on_device) {
-            HIP_TRY(staging.try_ensure(2 * n));
-            HIP_TRY(hipMemcpyAsync(staging.p, points, n * 96, hipMemcpyHostToDevice, ctx->stream));
+            staging.ensure(2 * n);
+            DEV_TRY(hipMemcpyAsync(staging.p, points, n * 96, hipMemcpyHostToDevice, ctx->stream));
             src = staging.p;
         }
-        if (points_are_affpt && !points_on_device) throw HipErr{hipErrorInvalidValue, "AffPt input must be device-resident"};
+        if (points_are_affpt && !points_on_device) throw DevErr{hipErrorInvalidValue, "AffPt input must be device-resident"};
         auto bases_in = [&](int with_images) {
             if (points_are_affpt)
                 hipLaunchKernelGGL(k_copy_affpt, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, row0.p,
@@ -2327,18 +2318,18 @@ MsmContext* msm_create(const void* points, size_t n, bool points_on_device, bool
             ctx->nwin = ctx->glv ? (127 + ctx->c) / ctx->c : 255 / ctx->c + 1;
         }
         ctx->nb = (size_t)1 << (ctx->c - 1);
-        HIP_TRY(ctx->table.try_ensure(ctx->glv ? 2 * n : (size_t)ctx->rows * n));
-        HIP_TRY(hipMemcpyAsync(ctx->table.p, row0.p, (ctx->glv ? 2 * n : n) * sizeof(AffPt), hipMemcpyDeviceToDevice, ctx->stream));
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        ctx->table.ensure(ctx->glv ? 2 * n : (size_t)ctx->rows * n);
+        DEV_TRY(hipMemcpyAsync(ctx->table.p, row0.p, (ctx->glv ? 2 * n : n) * sizeof(AffPt), hipMemcpyDeviceToDevice, ctx->stream));
+        DEV_TRY(hipStreamSynchronize(ctx->stream));
         row0.drop();
         if (prepare && ctx->rows > 1)
             hipLaunchKernelGGL(k_table_rows, dim3((unsigned)((n + 127) / 128)), dim3(128), 0, ctx->stream, ctx->table.p, n,
                                ctx->rows, ctx->c);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        DEV_TRY(hipGetLastError());
+        DEV_TRY(hipStreamSynchronize(ctx->stream));
         staging.drop();
         if (prepare) build_wide_table(ctx);
-        if (ctx->fbw_glv && !ctx->fbw) throw HipErr{hipErrorOutOfMemory, "wide GLV table did not fit the HBM budget it was sized for"};
+        if (ctx->fbw_glv && !ctx->fbw) throw DevErr{hipErrorOutOfMemory, "wide GLV table did not fit the HBM budget it was sized for"};
         if (prepare && verbose) {
             // the shape a handle ended up with depends on the HBM that was free: say so when asked
             const double gb = ctx->fbw ? (double)ctx->rows * (double)n * (double)ctx->nb * sizeof(WidePt) / 1e9 : 0.0;
@@ -2354,20 +2345,20 @@ MsmContext* msm_create(const void* points, size_t n, bool points_on_device, bool
 }
 
 void msm_reset_points(MsmContext* ctx, const void* d_affpts, size_t n) {
-    if (!ctx || ctx->prepared) throw HipErr{hipErrorInvalidValue, "msm_reset_points: not a variable-base handle"};
+    if (!ctx || ctx->prepared) throw DevErr{hipErrorInvalidValue, "msm_reset_points: not a variable-base handle"};
     std::lock_guard<std::mutex> lk(ctx->mu);
     DeviceGuard on_device(ctx->device);
-    HIP_TRY(on_device.err);
+    DEV_TRY(on_device.err);
     ctx->n = n;
     ctx->c = choose_window(n, false, ctx->glv, ctx->window_forced);
     ctx->rows = 1;
     ctx->nwin = ctx->glv ? (127 + ctx->c) / ctx->c : 255 / ctx->c + 1;
     ctx->nb = (size_t)1 << (ctx->c - 1);
-    HIP_TRY(ctx->table.try_ensure(ctx->glv ? 2 * n : n));
+    ctx->table.ensure(ctx->glv ? 2 * n : n);
     hipLaunchKernelGGL(k_copy_affpt, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, ctx->table.p,
                        (const AffPt*)d_affpts, n, ctx->glv ? 1 : 0);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(ctx->stream));  // the caller's buffer may be reused as soon as this returns
+    DEV_TRY(hipGetLastError());
+    DEV_TRY(hipStreamSynchronize(ctx->stream));  // the caller's buffer may be reused as soon as this returns
 }
 
 void msm_destroy(MsmContext* ctx) {
@@ -2391,7 +2382,7 @@ void g1_compress_xyzz(void* d_out48, const void* d_xyzz, size_t count, hipStream
     if (!count) return;
     hipLaunchKernelGGL(k_final, dim3((unsigned)((count + 63) / 64)), dim3(64), 0, stream, (const Xyzz*)nullptr,
                        (const Xyzz*)d_xyzz, d_out48, count, 1, 1, 1, OUT_COMPRESSED);
-    HIP_TRY(hipGetLastError());
+    DEV_TRY(hipGetLastError());
 }
 
 // Workspaces are per stream, but streams can outnumber them (and the handle's own stream shares the first one):
@@ -2418,11 +2409,11 @@ static hipEvent_t* profile_begin(MsmContext* ctx, hipStream_t stream) {
     if (!ctx->profile || ctx->ev_used + 4 > MsmContext::EV_MAX) return nullptr;
     while (ctx->ev.size() < ctx->ev_used + 4) {
         hipEvent_t e;
-        HIP_TRY(hipEventCreate(&e));
+        DEV_TRY(hipEventCreate(&e));
         ctx->ev.push_back(e);
     }
     hipEvent_t* pev = &ctx->ev[ctx->ev_used];
-    HIP_TRY(hipEventRecord(pev[0], stream));
+    DEV_TRY(hipEventRecord(pev[0], stream));
     return pev;
 }
 
@@ -2454,17 +2445,17 @@ static void enqueue_wide(MsmContext* ctx, Workspace& ws, void* d_out, const void
     const size_t spl1_max = ctx->tune.spl1_max > 0 ? (size_t)ctx->tune.spl1_max : 8;
     if (ctx->fbw_glv && nbatch <= spl1_max && npoints == 4096 && !ctx->tune.spl && !ctx->tune.no_wide_tail) spl = 1;
     const size_t lanes = (npoints + spl - 1) / spl * (ctx->fbw_glv ? 2 : 1);
-    HIP_TRY(ws.buckets.try_ensure(nbatch * lanes));
-    HIP_TRY(ws.lvlM[0].try_ensure(nbatch));
-    if (nbatch <= 16 && lanes % 16 == 0 && lanes >= 1024) HIP_TRY(ws.lvlA[0].try_ensure(nbatch * 128));
+    ws.buckets.ensure(nbatch * lanes);
+    ws.lvlM[0].ensure(nbatch);
+    if (nbatch <= 16 && lanes % 16 == 0 && lanes >= 1024) ws.lvlA[0].ensure(nbatch * 128);
     const size_t hybrid_max = ctx->tune.hybrid_max > 0 ? (size_t)ctx->tune.hybrid_max : BSH_MAX;
     const bool hybrid_fold = nbatch <= hybrid_max && nbatch <= BSH_CAP && lanes % (16 * 256) == 0 &&
                              !ctx->tune.no_wide_tail && !ctx->tune.no_hybrid_fold;
     bool bcount_new = false;
     if (hybrid_fold) {
-        HIP_TRY(ws.bpart.try_ensure(BSH_CAP * (size_t)BSH_PARTS));
+        ws.bpart.ensure(BSH_CAP * (size_t)BSH_PARTS);
         if (ws.bcount.cap < BSH_CAP) {
-            HIP_TRY(ws.bcount.try_ensure(BSH_CAP));
+            ws.bcount.ensure(BSH_CAP);
             bcount_new = true;
         }
     }
@@ -2476,15 +2467,15 @@ static void enqueue_wide(MsmContext* ctx, Workspace& ws, void* d_out, const void
         // (zeroed when allocated, left at zero by every launch); k_wide_fold64 (tuning key no_wide_tree): 129 cells x
         // WFOLD parts, a counter per cell — which is more of both
         const size_t need_p = (nbatch * 128 + nbatch) * (size_t)WFOLD, need_c = nbatch * 128 + nbatch;
-        HIP_TRY(ws.wpart.try_ensure(need_p));
+        ws.wpart.ensure(need_p);
         if (ws.wcount.cap < need_c) {
-            HIP_TRY(ws.wcount.try_ensure(need_c));
+            ws.wcount.ensure(need_c);
             wcount_new = true;
         }
     }
-    if (ctx->fbw_glv) HIP_TRY(ws.digits.try_ensure(nbatch * npoints * 2 * (size_t)((nwin + 3) & ~3)));
-    if (bcount_new) HIP_TRY(hipMemsetAsync(ws.bcount.p, 0, BSH_CAP * sizeof(u32), stream));
-    if (wcount_new) HIP_TRY(hipMemsetAsync(ws.wcount.p, 0, ws.wcount.cap * sizeof(u32), stream));
+    if (ctx->fbw_glv) ws.digits.ensure(nbatch * npoints * 2 * (size_t)((nwin + 3) & ~3));
+    if (bcount_new) DEV_TRY(hipMemsetAsync(ws.bcount.p, 0, BSH_CAP * sizeof(u32), stream));
+    if (wcount_new) DEV_TRY(hipMemsetAsync(ws.wcount.p, 0, ws.wcount.cap * sizeof(u32), stream));
     if (reserve_only) return;
     WsUse ws_use(ws, stream, &ws == &ctx->ws);
     DigitParams P{npoints, nbatch, c, nwin, 1, mont, nb, ctx->n, 0, 0, nwin, (u32)nseg};
@@ -2495,7 +2486,7 @@ static void enqueue_wide(MsmContext* ctx, Workspace& ws, void* d_out, const void
                            (const u32*)d_scalars, ws.digits.p);
         acc_in = ws.digits.p;
     }
-    if (pev) HIP_TRY(hipEventRecord(pev[1], stream));
+    if (pev) DEV_TRY(hipEventRecord(pev[1], stream));
     const dim3 grid((unsigned)((lanes * nbatch + 255) / 256));
 #define KZG_FBW_LAUNCH(SPL_, GLV_)                                                                           \
     hipLaunchKernelGGL((k_fbw_accum<SPL_, GLV_>), grid, dim3(256), 0, stream, P, acc_in,                         \
@@ -2517,7 +2508,7 @@ static void enqueue_wide(MsmContext* ctx, Workspace& ws, void* d_out, const void
         else KZG_FBW_LAUNCH(4, false);
     }
 #undef KZG_FBW_LAUNCH
-    if (pev) HIP_TRY(hipEventRecord(pev[2], stream));
+    if (pev) DEV_TRY(hipEventRecord(pev[2], stream));
     Xyzz* sums = out_mode == OUT_XYZZ ? (Xyzz*)d_out : ws.lvlM[0].p;
     if (lanes <= 64) {
         // many small MSMs (segments of a table): one lane adds the few partial sums of an MSM
@@ -2532,7 +2523,7 @@ static void enqueue_wide(MsmContext* ctx, Workspace& ws, void* d_out, const void
         // one or two commitments: the partial sums folded 64 : 1, then 64 : 1 or 128 : 1, with limb-parallel additions
         const int pw2 = (int)(lanes / 64 / WFOLD);  // 8 or 16 points per wave in the second launch
         const size_t c1 = nbatch * (lanes / 64), c2 = nbatch;
-        HIP_TRY(hipMemsetAsync(ws.wcount.p, 0, (c1 + c2) * sizeof(u32), stream));
+        DEV_TRY(hipMemsetAsync(ws.wcount.p, 0, (c1 + c2) * sizeof(u32), stream));
         hipLaunchKernelGGL(k_wide_fold64, dim3((unsigned)(c1 * WFOLD)), dim3(64), 0, stream, (const Xyzz*)ws.buckets.p,
                            ws.lvlA[0].p, ws.wpart.p, ws.wcount.p, 8);
         hipLaunchKernelGGL(k_wide_fold64, dim3((unsigned)(c2 * WFOLD)), dim3(64), 0, stream, (const Xyzz*)ws.lvlA[0].p, sums,
@@ -2561,10 +2552,10 @@ static void enqueue_wide(MsmContext* ctx, Workspace& ws, void* d_out, const void
         hipLaunchKernelGGL(k_final, dim3((unsigned)((nbatch + 63) / 64)), dim3(64), 0, stream, (const Xyzz*)nullptr,
                            (const Xyzz*)ws.lvlM[0].p, d_out, nbatch, nwin, c, 1, out_mode);
     if (pev) {
-        HIP_TRY(hipEventRecord(pev[3], stream));
+        DEV_TRY(hipEventRecord(pev[3], stream));
         ctx->ev_used += 4;
     }
-    HIP_TRY(hipGetLastError());
+    DEV_TRY(hipGetLastError());
 }
 
 // How a sub-batch of a batch of large MSMs is tied to the caller's stream (see MsmContext::sub_stream): sorted and
@@ -2584,8 +2575,8 @@ static void enqueue_buckets(MsmContext* ctx, Workspace& ws, void* d_out, const v
     const size_t nb = ctx->nb;
     const size_t nsets = ctx->prepared ? nbatch : nbatch * (size_t)nwin;
     const size_t set_cap = ctx->prepared ? npoints * (size_t)nwin : (ctx->glv ? 2 * npoints : npoints);
-    HIP_TRY(ws.offsets.try_ensure(nsets * (nb + 1)));
-    HIP_TRY(ws.sorted.try_ensure(nsets * set_cap));
+    ws.offsets.ensure(nsets * (nb + 1));
+    ws.sorted.ensure(nsets * set_cap);
     // entries per accumulation lane, 2^lgc: longer chunks leave fewer pieces per bucket to fold, shorter ones more lanes
     // (A/B in one process with the tiled reduction, median ms, lgc -> time:  2^18: 5 -> 1.36, 6 -> 1.40;  2^19: 5 -> 2.13,
     //  6 -> 2.10;  2^20: 5 -> 3.70, 6 -> 3.57, 7 -> 3.49;  2^21: 6 -> 6.50, 7 -> 6.35, 8 -> 6.52;  2^22: 6 -> 13.28,
@@ -2598,13 +2589,13 @@ static void enqueue_buckets(MsmContext* ctx, Workspace& ws, void* d_out, const v
         if (v >= 2 && v <= 8) lgc = lgc_lo = v;
     }
     const size_t nchunk = (set_cap + ((size_t)1 << lgc_lo) - 1) >> lgc_lo;
-    HIP_TRY(ws.buckets.try_ensure(nsets * (nb + nchunk)));
+    ws.buckets.ensure(nsets * (nb + nchunk));
     const size_t n1 = (nb + 1) / 2, n2 = (n1 + GRP - 1) / GRP;  // level 0 folds at least 2, later levels GRP
-    HIP_TRY(ws.lvlA[0].try_ensure(nsets * n1));
-    HIP_TRY(ws.lvlM[0].try_ensure(nsets * n1));
-    HIP_TRY(ws.lvlA[1].try_ensure(nsets * n2));
-    HIP_TRY(ws.lvlM[1].try_ensure(nsets * n2));
-    HIP_TRY(ws.heavy.try_ensure(nsets * nb));
+    ws.lvlA[0].ensure(nsets * n1);
+    ws.lvlM[0].ensure(nsets * n1);
+    ws.lvlA[1].ensure(nsets * n2);
+    ws.lvlM[1].ensure(nsets * n2);
+    ws.heavy.ensure(nsets * nb);
     // lanes the accumulation wants per set: 90 % of two waves per SIMD over the sets of a launch
     const ChunkSel csel{lgc_lo, lgc, (u32)(118000 / nsets)};
     // two-level sort: coarse bins must fit the LDS counters and a point index 24 bits
@@ -2619,17 +2610,17 @@ static void enqueue_buckets(MsmContext* ctx, Workspace& ws, void* d_out, const v
                            (nb >> fb) * nsets <= MAX_BINS &&
                            npoints * nbatch >= ((size_t)1 << 15);  // below: four more launches than they save
     if (two_level) {
-        HIP_TRY(ws.tmp.try_ensure(nsets * set_cap));
-        HIP_TRY(ws.bins.try_ensure(3 * MAX_BINS + 8));
+        ws.tmp.ensure(nsets * set_cap);
+        ws.bins.ensure(3 * MAX_BINS + 8);
         // per-workgroup histograms and run starts of the partition pass (1024 scalars per workgroup)
-        HIP_TRY(ws.wghist.try_ensure(2 * ((npoints * nbatch + 1023) / 1024) * ((nb >> fb) * nsets)));
+        ws.wghist.ensure(2 * ((npoints * nbatch + 1023) / 1024) * ((nb >> fb) * nsets));
     } else {
-        HIP_TRY(ws.counts.try_ensure(nsets * nb));
-        HIP_TRY(ws.ranks.try_ensure((size_t)(ctx->glv ? 2 : 1) * nwin * nbatch * npoints));
+        ws.counts.ensure(nsets * nb);
+        ws.ranks.ensure((size_t)(ctx->glv ? 2 : 1) * nwin * nbatch * npoints);
     }
     const size_t heavy_cap = nsets * set_cap / HEAVY + 1;  // a heavy bucket holds > HEAVY entries
-    HIP_TRY(ws.heavy_list.try_ensure(2 * heavy_cap));
-    HIP_TRY(ws.nheavy.try_ensure(1));
+    ws.heavy_list.ensure(2 * heavy_cap);
+    ws.nheavy.ensure(1);
     const bool use_top = nsets <= 64;  // many independent sets (batched MSMs) keep plain tree levels busy on their own
     // few chains: run the serial tails limb-parallel, one point operation per wave
     const bool wide_tail = use_top && !ctx->tune.no_wide_tail;
@@ -2660,19 +2651,19 @@ static void enqueue_buckets(MsmContext* ctx, Workspace& ws, void* d_out, const v
             int logNb = 0;
             while (((size_t)1 << logNb) < nb) ++logNb;
             top_stride = (size_t)logNb + 2;
-            HIP_TRY(ws.lvlA[0].try_ensure(nsets * (size_t)(((logNb + DIGIT_BITS - 1) / DIGIT_BITS) * 32)));
-            HIP_TRY(ws.dense.try_ensure(nsets * nb));
+            ws.lvlA[0].ensure(nsets * (size_t)(((logNb + DIGIT_BITS - 1) / DIGIT_BITS) * 32));
+            ws.dense.ensure(nsets * nb);
             if (tiled_digits) {
-                HIP_TRY(ws.lvlA[1].try_ensure(nsets * (nb >> 5)));  // group sums
-                HIP_TRY(ws.lvlM[1].try_ensure(nsets * (nb >> 4)));  // per-tile column sums: ntiles x 32 (16-row tiles: nb / 16)
+                ws.lvlA[1].ensure(nsets * (nb >> 5));  // group sums
+                ws.lvlM[1].ensure(nsets * (nb >> 4));  // per-tile column sums: ntiles x 32 (16-row tiles: nb / 16)
                 const size_t cells = nsets * (size_t)(((logNb + DIGIT_BITS - 1) / DIGIT_BITS) * 32 + logNb + 2);
-                HIP_TRY(ws.wpart.try_ensure(cells * WSPLIT));
-                HIP_TRY(ws.wcount.try_ensure(cells));
+                ws.wpart.ensure(cells * WSPLIT);
+                ws.wcount.ensure(cells);
             }
         }
         if (use_top) {
-            HIP_TRY(ws.top.try_ensure(nsets * top_stride));
-            HIP_TRY(ws.win.try_ensure(nsets));
+            ws.top.ensure(nsets * top_stride);
+            ws.win.ensure(nsets);
         }
     }
     if (reserve_only) return;
@@ -2692,7 +2683,7 @@ static void enqueue_buckets(MsmContext* ctx, Workspace& ws, void* d_out, const v
         u32* bin_cursor = bin_start + MAX_BINS + 8;
         u32* tmp = ws.tmp.p;
         const unsigned gpart = (unsigned)((npoints * nbatch + 256 * PART_SCALARS - 1) / (256 * PART_SCALARS));
-        HIP_TRY(hipMemsetAsync(bin_count, 0, nbins * sizeof(u32), stream));
+        DEV_TRY(hipMemsetAsync(bin_count, 0, nbins * sizeof(u32), stream));
         // entries per scalar (windows x halves): the staged scatter holds 16 per scalar
         const size_t per_scalar = (size_t)nwin * (ctx->glv ? 2 : 1);
         const bool staged = per_scalar * STAGE_T * STAGE_SCALARS <= STAGE_CAP && !ctx->tune.direct_scatter;
@@ -2700,7 +2691,7 @@ static void enqueue_buckets(MsmContext* ctx, Workspace& ws, void* d_out, const v
         const bool keep_hist = staged && !ctx->tune.scatter_atomics;
         u32 *wg_hist = nullptr, *wg_off = nullptr;
         if (keep_hist) {
-            HIP_TRY(ws.wghist.try_ensure(2 * (size_t)gpart * nbins));
+            ws.wghist.ensure(2 * (size_t)gpart * nbins);
             wg_hist = ws.wghist.p;
             wg_off = wg_hist + (size_t)gpart * nbins;
         }
@@ -2721,34 +2712,34 @@ static void enqueue_buckets(MsmContext* ctx, Workspace& ws, void* d_out, const v
                                (const u32*)d_scalars, (const AffPt*)ctx->table.p, (const u32*)bin_start, bin_cursor, tmp,
                                0u, cb, nbins, fb);
         }
-        HIP_TRY(hipMemsetAsync(nheavy, 0, sizeof(u32), stream));
+        DEV_TRY(hipMemsetAsync(nheavy, 0, sizeof(u32), stream));
         hipLaunchKernelGGL(k_bin_sort, dim3(nbins), dim3(256), 0, stream, (const u32*)tmp, (const u32*)bin_start, offsets,
                            ws.sorted.p, heavy, heavy_list, nheavy, (u32)heavy_cap, cb, nb, set_cap, fb);
     } else {
-        HIP_TRY(hipMemsetAsync(ws.counts.p, 0, nsets * nb * sizeof(u32), stream));
+        DEV_TRY(hipMemsetAsync(ws.counts.p, 0, nsets * nb * sizeof(u32), stream));
         const unsigned gdig = (unsigned)((npoints * nbatch + 255) / 256);
         hipLaunchKernelGGL(k_digits<0>, dim3(gdig), dim3(256), 0, stream, P, (const u32*)d_scalars, ctx->table.p, ws.counts.p,
                            (const u32*)nullptr, (u32*)nullptr, set_cap, ws.ranks.p);
-        HIP_TRY(hipMemsetAsync(nheavy, 0, sizeof(u32), stream));
+        DEV_TRY(hipMemsetAsync(nheavy, 0, sizeof(u32), stream));
         hipLaunchKernelGGL(k_scan, dim3((unsigned)nsets), dim3(1024), 0, stream, ws.counts.p, offsets, nb, heavy, heavy_list,
                            nheavy, (u32)heavy_cap);
         hipLaunchKernelGGL(k_digits<1>, dim3(gdig), dim3(256), 0, stream, P, (const u32*)d_scalars, ctx->table.p, ws.counts.p,
                            (const u32*)ws.offsets.p, ws.sorted.p, set_cap, ws.ranks.p);
     }
-    if (pev) HIP_TRY(hipEventRecord(pev[1], stream));
+    if (pev) DEV_TRY(hipEventRecord(pev[1], stream));
     // The accumulation: VALU throughput, the chip full.  Everything after it (heavy buckets, bucket reduction, window
     // sums) is latency chains on a fraction of the chip (0.7 ms of 3.4 at n = 2^20).
     hipStream_t kst = stream;
     if (link) {  // sorted on stream; accumulated on accum_on, behind the previous sub-batch's accumulation
-        HIP_TRY(hipEventRecord(link->sorted, stream));
-        HIP_TRY(hipStreamWaitEvent(link->accum_on, link->sorted, 0));
+        DEV_TRY(hipEventRecord(link->sorted, stream));
+        DEV_TRY(hipStreamWaitEvent(link->accum_on, link->sorted, 0));
         kst = link->accum_on;
     }
     hipLaunchKernelGGL(k_accum, dim3((unsigned)((nsets * nchunk + 255) / 256)), dim3(256), 0, kst, (const u32*)offsets,
                        (const u32*)ws.sorted.p, (const AffPt*)ctx->table.p, buckets, nb, nsets, set_cap, nchunk, csel);
     if (link) {
-        HIP_TRY(hipEventRecord(link->accumulated, link->accum_on));
-        HIP_TRY(hipStreamWaitEvent(stream, link->accumulated, 0));
+        DEV_TRY(hipEventRecord(link->accumulated, link->accum_on));
+        DEV_TRY(hipStreamWaitEvent(stream, link->accumulated, 0));
     }
     hipLaunchKernelGGL(k_heavy, dim3(256, 64), dim3(64), 0, stream, buckets, (const u32*)offsets, (const u32*)heavy_list,
                        (const u32*)nheavy, (u32)heavy_cap, nb, nchunk, 1u, HSEG, csel, 0u, (u32)nsets);
@@ -2781,7 +2772,7 @@ static void enqueue_buckets(MsmContext* ctx, Workspace& ws, void* d_out, const v
                 const size_t c1 = nsets * (size_t)(J * 32), c2 = nsets * (size_t)(logNb + 2);
                 u32* cnt = ws.wcount.p;
                 Xyzz* part = ws.wpart.p;  // WSPLIT >= WSPLIT_S slots per cell
-                HIP_TRY(hipMemsetAsync(cnt, 0, (c1 + c2) * sizeof(u32), stream));
+                DEV_TRY(hipMemsetAsync(cnt, 0, (c1 + c2) * sizeof(u32), stream));
                 hipLaunchKernelGGL(k_digit_sums_wide, dim3((unsigned)(c1 * WSPLIT_S)), dim3(64), 0, stream, (const Xyzz*)Gs,
                                    (const Xyzz*)Cp, S, part, cnt, nb, logNb, J, ntiles);
                 hipLaunchKernelGGL(k_digit_bits_wide, dim3((unsigned)(c2 * WSPLIT)), dim3(64), 0, stream, (const Xyzz*)S, top,
@@ -2853,7 +2844,7 @@ static void enqueue_buckets(MsmContext* ctx, Workspace& ws, void* d_out, const v
             finM = ws.lvlM[(lvl - 1) & 1].p;
         }
     }
-    if (pev) HIP_TRY(hipEventRecord(pev[2], stream));
+    if (pev) DEV_TRY(hipEventRecord(pev[2], stream));
     if (wide_tail && !ctx->prepared && out_mode == OUT_JACOBIAN && nwin > 1) {
         // few independent Horner chains: one wave each, limb-parallel doublings
         hipLaunchKernelGGL(k_final_wide, dim3((unsigned)nbatch), dim3(64), 0, stream, finM, d_out, nwin, c);
@@ -2863,10 +2854,10 @@ static void enqueue_buckets(MsmContext* ctx, Workspace& ws, void* d_out, const v
                            c, ctx->prepared ? 1 : 0, out_mode);
     }
     if (pev) {
-        HIP_TRY(hipEventRecord(pev[3], stream));
+        DEV_TRY(hipEventRecord(pev[3], stream));
         ctx->ev_used += 4;
     }
-    HIP_TRY(hipGetLastError());
+    DEV_TRY(hipGetLastError());
 }
 
 // A batch of large MSMs whose sets together have more coarse bins than the two-level sort's LDS counters hold
@@ -2904,13 +2895,13 @@ static bool enqueue_sub_batches(MsmContext* ctx, void* d_out, const void* d_scal
     const int lanes = nside > 0 ? (int)(nsub < (size_t)nside ? nsub : (size_t)nside) : 0;  // side streams in use
     if (lanes > 0 && !ctx->sub_stream[lanes - 1]) {
         int least = 0, greatest = 0;
-        HIP_TRY(hipDeviceGetStreamPriorityRange(&least, &greatest));
+        DEV_TRY(hipDeviceGetStreamPriorityRange(&least, &greatest));
         const int prio = ctx->tune.sub_prio ? greatest : 0;
         for (int k = 0; k < lanes; ++k) {
-            if (!ctx->sub_stream[k]) HIP_TRY(hipStreamCreateWithPriority(&ctx->sub_stream[k], hipStreamNonBlocking, prio));
-            if (!ctx->ev_sub_join[k]) HIP_TRY(hipEventCreateWithFlags(&ctx->ev_sub_join[k], hipEventDisableTiming));
-            if (!ctx->ev_sorted[k]) HIP_TRY(hipEventCreateWithFlags(&ctx->ev_sorted[k], hipEventDisableTiming));
-            if (!ctx->ev_accd[k]) HIP_TRY(hipEventCreateWithFlags(&ctx->ev_accd[k], hipEventDisableTiming));
+            if (!ctx->sub_stream[k]) DEV_TRY(hipStreamCreateWithPriority(&ctx->sub_stream[k], hipStreamNonBlocking, prio));
+            if (!ctx->ev_sub_join[k]) DEV_TRY(hipEventCreateWithFlags(&ctx->ev_sub_join[k], hipEventDisableTiming));
+            if (!ctx->ev_sorted[k]) DEV_TRY(hipEventCreateWithFlags(&ctx->ev_sorted[k], hipEventDisableTiming));
+            if (!ctx->ev_accd[k]) DEV_TRY(hipEventCreateWithFlags(&ctx->ev_accd[k], hipEventDisableTiming));
         }
     }
     if (reserve_only) {  // the first sub-batch is the largest; every stream of the rotation gets its workspace
@@ -2923,10 +2914,10 @@ static bool enqueue_sub_batches(MsmContext* ctx, void* d_out, const void* d_scal
     }
     try {
         if (lanes > 0) {
-            if (!ctx->ev_sub_fork) HIP_TRY(hipEventCreateWithFlags(&ctx->ev_sub_fork, hipEventDisableTiming));
+            if (!ctx->ev_sub_fork) DEV_TRY(hipEventCreateWithFlags(&ctx->ev_sub_fork, hipEventDisableTiming));
             // whatever produced the scalars (and last used the outputs) on the caller's stream comes first
-            HIP_TRY(hipEventRecord(ctx->ev_sub_fork, stream));
-            for (int k = 0; k < lanes; ++k) HIP_TRY(hipStreamWaitEvent(ctx->sub_stream[k], ctx->ev_sub_fork, 0));
+            DEV_TRY(hipEventRecord(ctx->ev_sub_fork, stream));
+            for (int k = 0; k < lanes; ++k) DEV_TRY(hipStreamWaitEvent(ctx->sub_stream[k], ctx->ev_sub_fork, 0));
         }
         size_t k = 0;
         for (size_t b0 = 0; b0 < nbatch; b0 += per, ++k) {
@@ -2952,8 +2943,8 @@ static bool enqueue_sub_batches(MsmContext* ctx, void* d_out, const void* d_scal
         throw;
     }
     for (int j = 0; j < lanes; ++j) {
-        HIP_TRY(hipEventRecord(ctx->ev_sub_join[j], ctx->sub_stream[j]));
-        HIP_TRY(hipStreamWaitEvent(stream, ctx->ev_sub_join[j], 0));
+        DEV_TRY(hipEventRecord(ctx->ev_sub_join[j], ctx->sub_stream[j]));
+        DEV_TRY(hipStreamWaitEvent(stream, ctx->ev_sub_join[j], 0));
     }
     return true;
 }
@@ -2963,19 +2954,19 @@ static bool enqueue_sub_batches(MsmContext* ctx, void* d_out, const void* d_scal
 // synchronises the device, so callers that must not stall a running pipeline reserve during set-up)
 void msm_enqueue(MsmContext* ctx, void* d_out, const void* d_scalars, size_t npoints, size_t nbatch, int mont,
                  hipStream_t stream, int out_mode, bool reserve_only, size_t nseg) {
-    if (npoints * (nseg ? nseg : 1) > ctx->n) throw HipErr{hipErrorInvalidValue, "npoints exceeds the prepared size"};
+    if (npoints * (nseg ? nseg : 1) > ctx->n) throw DevErr{hipErrorInvalidValue, "npoints exceeds the prepared size"};
     if ((nseg || out_mode == OUT_XYZZ) && !ctx->fbw)
-        throw HipErr{hipErrorInvalidValue, "segmented / XYZZ-output MSMs need the wide-table path"};
+        throw DevErr{hipErrorInvalidValue, "segmented / XYZZ-output MSMs need the wide-table path"};
     if (nbatch == 0) return;
     const size_t nsets = ctx->prepared ? nbatch : nbatch * (size_t)ctx->nwin;
     const size_t set_cap = ctx->prepared ? npoints * (size_t)ctx->nwin : (ctx->glv ? 2 * npoints : npoints);
     if (npoints == 0) {
         if (reserve_only) return;
-        if (out_mode == OUT_COMPRESSED) throw HipErr{hipErrorInvalidValue, "empty MSM in compressed mode"};
-        HIP_TRY(hipMemsetAsync(d_out, 0, nbatch * 144, stream));
+        if (out_mode == OUT_COMPRESSED) throw DevErr{hipErrorInvalidValue, "empty MSM in compressed mode"};
+        DEV_TRY(hipMemsetAsync(d_out, 0, nbatch * 144, stream));
         return;
     }
-    if (set_cap >= ((size_t)1 << 31) || nsets * ctx->nb >= ((size_t)1 << 40)) throw HipErr{hipErrorInvalidValue, "MSM too large"};
+    if (set_cap >= ((size_t)1 << 31) || nsets * ctx->nb >= ((size_t)1 << 40)) throw DevErr{hipErrorInvalidValue, "MSM too large"};
     // the caller's stream takes its workspace before any side stream of a batch does: the handle's first workspace goes
     // to the first caller stream (MsmContext::workspace_for)
     Workspace& ws = ctx->workspace_for(stream);
@@ -3015,13 +3006,13 @@ static void msm_run_combined_batch(MsmContext* ctx, MsmContext::CombineLane& lan
     const size_t nb = batch.size(), np = batch[0]->npoints;
     try {
         DeviceGuard on_device(ctx->device);
-        HIP_TRY(on_device.err);
+        DEV_TRY(on_device.err);
         {
             std::lock_guard<std::mutex> lk(ctx->mu);  // enqueue only: the wait below runs beside the other lane's enqueue
-            if (!lane.st) HIP_TRY(hipStreamCreateWithFlags(&lane.st, hipStreamNonBlocking));
-            if (!lane.h_out) HIP_TRY(hipHostMalloc((void**)&lane.h_out, MsmContext::COMBINE_MAX * 144, hipHostMallocDefault));
-            HIP_TRY(lane.scalars.try_ensure(nb * np * 8 + 8));
-            HIP_TRY(lane.out.try_ensure(nb * 3 + 3));
+            if (!lane.st) DEV_TRY(hipStreamCreateWithFlags(&lane.st, hipStreamNonBlocking));
+            if (!lane.h_out) DEV_TRY(hipHostMalloc((void**)&lane.h_out, MsmContext::COMBINE_MAX * 144, hipHostMallocDefault));
+            lane.scalars.ensure(nb * np * 8 + 8);
+            lane.out.ensure(nb * 3 + 3);
             try {
                 bool all_slots = true;
                 for (size_t j = 0; j < nb; ++j) all_slots = all_slots && batch[j]->slot != nullptr;
@@ -3033,19 +3024,19 @@ static void msm_run_combined_batch(MsmContext* ctx, MsmContext::CombineLane& lan
                                        (uint4*)lane.scalars.p, ss, per, nb);
                 } else {  // a caller found the slot pool empty: its scalars are in pageable memory
                     for (size_t j = 0; j < nb; ++j)
-                        HIP_TRY(hipMemcpyAsync(lane.scalars.p + j * np * 8, batch[j]->slot ? (const void*)batch[j]->slot : batch[j]->scalars,
+                        DEV_TRY(hipMemcpyAsync(lane.scalars.p + j * np * 8, batch[j]->slot ? (const void*)batch[j]->slot : batch[j]->scalars,
                                                np * 32, hipMemcpyHostToDevice, lane.st));
                 }
                 msm_enqueue(ctx, lane.out.p, lane.scalars.p, np, nb, 1, lane.st, OUT_JACOBIAN);
-                HIP_TRY(hipMemcpyAsync(lane.h_out, lane.out.p, nb * 144, hipMemcpyDeviceToHost, lane.st));
+                DEV_TRY(hipMemcpyAsync(lane.h_out, lane.out.p, nb * 144, hipMemcpyDeviceToHost, lane.st));
             } catch (...) {
                 (void)hipStreamSynchronize(lane.st);  // whatever was enqueued still reads the callers' slots
                 throw;
             }
         }
-        HIP_TRY(hipStreamSynchronize(lane.st));
+        DEV_TRY(hipStreamSynchronize(lane.st));
         for (size_t j = 0; j < nb; ++j) memcpy(batch[j]->out, lane.h_out + j * 144, 144);
-    } catch (const HipErr& e) {
+    } catch (const DevErr& e) {
         for (auto* r : batch) {
             r->failed = true;
             r->err = e;
@@ -3053,7 +3044,7 @@ static void msm_run_combined_batch(MsmContext* ctx, MsmContext::CombineLane& lan
     } catch (...) {
         for (auto* r : batch) {
             r->failed = true;
-            r->err = HipErr{hipErrorUnknown, "combined MSM batch failed"};
+            r->err = DevErr{hipErrorUnknown, "combined MSM batch failed"};
         }
     }
 }
@@ -3076,27 +3067,27 @@ static void msm_run_host_combined(MsmContext* ctx, void* out, const void* scalar
 
 // host buffers in, host buffers out
 void msm_run_host(MsmContext* ctx, void* out, const void* scalars, size_t npoints, size_t nbatch, size_t nseg) {
-    if (npoints * (nseg ? nseg : 1) > ctx->n) throw HipErr{hipErrorInvalidValue, "npoints exceeds the prepared size"};
+    if (npoints * (nseg ? nseg : 1) > ctx->n) throw DevErr{hipErrorInvalidValue, "npoints exceeds the prepared size"};
     if (ctx->prepared && nbatch == 1 && npoints > 0 && npoints <= MsmContext::COMBINE_NMAX && ctx->tune.combine && !nseg) {
         msm_run_host_combined(ctx, out, scalars, npoints);
         return;
     }
     std::lock_guard<std::mutex> lk(ctx->mu);
     DeviceGuard on_device(ctx->device);
-    HIP_TRY(on_device.err);
-    HIP_TRY(ctx->ws.scalars.try_ensure(nbatch * npoints * 8 + 8));
-    HIP_TRY(ctx->ws.out.try_ensure(nbatch * 3 + 3));
+    DEV_TRY(on_device.err);
+    ctx->ws.scalars.ensure(nbatch * npoints * 8 + 8);
+    ctx->ws.out.ensure(nbatch * 3 + 3);
     if (npoints * nbatch)
-        HIP_TRY(hipMemcpyAsync(ctx->ws.scalars.p, scalars, nbatch * npoints * 32, hipMemcpyHostToDevice, ctx->stream));
+        DEV_TRY(hipMemcpyAsync(ctx->ws.scalars.p, scalars, nbatch * npoints * 32, hipMemcpyHostToDevice, ctx->stream));
     if (!ctx->prepared && npoints > 0) {
         // variable-base engine: the ~255 Horner doublings are one serial chain; a CPU core runs that chain
         // several times faster than a single GPU lane, and the result goes to the host anyway
         const int nwin = ctx->nwin;
-        HIP_TRY(ctx->ws.out.try_ensure(nbatch * (size_t)nwin * 3));
+        ctx->ws.out.ensure(nbatch * (size_t)nwin * 3);
         msm_enqueue(ctx, ctx->ws.out.p, ctx->ws.scalars.p, npoints, nbatch, 1, ctx->stream, OUT_WINDOWS);
         std::vector<blst_p1> win(nbatch * (size_t)nwin);
-        HIP_TRY(hipMemcpyAsync(win.data(), ctx->ws.out.p, win.size() * 144, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        DEV_TRY(hipMemcpyAsync(win.data(), ctx->ws.out.p, win.size() * 144, hipMemcpyDeviceToHost, ctx->stream));
+        DEV_TRY(hipStreamSynchronize(ctx->stream));
         for (size_t b = 0; b < nbatch; ++b) {
             HostJac acc;
             acc.x = acc.y = acc.z = ff::Fp::zero();
@@ -3113,8 +3104,8 @@ void msm_run_host(MsmContext* ctx, void* out, const void* scalars, size_t npoint
         return;
     }
     msm_enqueue(ctx, ctx->ws.out.p, ctx->ws.scalars.p, npoints, nbatch, 1, ctx->stream, OUT_JACOBIAN, false, nseg);
-    HIP_TRY(hipMemcpyAsync(out, ctx->ws.out.p, nbatch * 144, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    DEV_TRY(hipMemcpyAsync(out, ctx->ws.out.p, nbatch * 144, hipMemcpyDeviceToHost, ctx->stream));
+    DEV_TRY(hipStreamSynchronize(ctx->stream));
 }
 
 }  // namespace kzgamd
@@ -3127,7 +3118,7 @@ static RustError guarded(F&& f) {
     try {
         f();
         return ok_error();
-    } catch (const HipErr& e) {
+    } catch (const DevErr& e) {
         return make_error((int)e.e ? (int)e.e : 1, std::string(e.what) + ": " + hipGetErrorString(e.e));
     } catch (const std::exception& e) {
         return make_error(1, e.what());
@@ -3145,7 +3136,7 @@ static void* create_guarded(const char* who, const KzgAmdConfig* cfg, F&& make) 
             return nullptr;
         }
         return make(opt);
-    } catch (const HipErr& e) {
+    } catch (const DevErr& e) {
         fprintf(stderr, "kzg_mi355x: %s failed: %s: %s\n", who, e.what, hipGetErrorString(e.e));
         return nullptr;
     } catch (...) {
@@ -3283,7 +3274,7 @@ extern "C" RustError kzgamd_msm_prepared_batch_device(void* msm, void* d_out, co
         MsmContext* ctx = (MsmContext*)msm;
         std::lock_guard<std::mutex> lk(ctx->mu);
         kzgamd::DeviceGuard on_device(ctx->device);
-        HIP_TRY(on_device.err);
+        DEV_TRY(on_device.err);
         kzgamd::msm_enqueue(ctx, d_out, d_scalars, npoints, nbatch, scalars_mont, (hipStream_t)stream, kzgamd::OUT_JACOBIAN);
     });
 }
@@ -3297,7 +3288,7 @@ extern "C" RustError kzgamd_msm_reserve(void* msm, size_t npoints, size_t nbatch
         MsmContext* ctx = (MsmContext*)msm;
         std::lock_guard<std::mutex> lk(ctx->mu);
         kzgamd::DeviceGuard on_device(ctx->device);
-        HIP_TRY(on_device.err);
+        DEV_TRY(on_device.err);
         kzgamd::msm_enqueue(ctx, nullptr, nullptr, npoints, nbatch, 0, (hipStream_t)stream, kzgamd::OUT_JACOBIAN, true);
     });
 }
@@ -3345,7 +3336,7 @@ extern "C" RustError kzgamd_generate_points(void* d_out_affine, size_t n, uint64
     return guarded([&] {
         hipLaunchKernelGGL(k_gen_points, dim3((unsigned)((n + 127) / 128)), dim3(128), 0, (hipStream_t)stream,
                            (ff::Fp*)d_out_affine, n, seed);
-        HIP_TRY(hipGetLastError());
+        DEV_TRY(hipGetLastError());
     });
 }
 

@@ -1,4 +1,6 @@
-// Internal C++ interface of the MSM engine (shared by msm.hip and the c-kzg layer).
+// Internal C++ interface of the MSM engine (shared by msm.hip, the c-kzg layer and the generic handles).
+// msm_create, msm_reset_points, msm_enqueue and msm_run_host throw kzgamd::DevErr (host_call.h) for a failed device call
+// and for an argument the engine rejects (hipErrorInvalidValue with the reason as text), std::bad_alloc for host memory.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>

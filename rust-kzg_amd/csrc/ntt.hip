@@ -565,14 +565,11 @@ extern "C" int kzgamd_ntt_fr_device(void* vctx, void* d_out, const void* d_in, s
     if (n > ctx->W) return 1;
     if (n == 0 || (n & (n - 1))) return 2;
     if (d_out == d_in) return -3;
-    try {
+    return kzgamd::status_of([&] {
         kzgamd::DeviceGuard on_device(ctx->device);
         DEV_TRY(on_device.err);
         ntt_enqueue(ctx, (Fr*)d_out, (const Fr*)d_in, n, nbatch, inverse != 0, (hipStream_t)stream);
-    } catch (const kzgamd::DevErr& e) {
-        return kzgamd::dev_code(e.e);
-    }
-    return 0;
+    });
 }
 
 namespace {
@@ -584,8 +581,7 @@ void das_enqueue(NttCtx* ctx, Fr* d_odds, const Fr* d_evens, Fr* d_tmp, size_t n
 void run_combined_batch(NttCtx* ctx, NttCtx::CombLane& lane, const std::vector<NttCtx::HostCall*>& batch) {
     const size_t nb = batch.size(), n = batch[0]->n;
     const int kind = batch[0]->kind;
-    int rc = 0;
-    try {
+    const int rc = kzgamd::status_of([&] {
         kzgamd::DeviceGuard on_device(ctx->device);
         DEV_TRY(on_device.err);
         // each on its own test: an allocation that failed is tried again by the next batch, not taken for made
@@ -604,10 +600,8 @@ void run_combined_batch(NttCtx* ctx, NttCtx::CombLane& lane, const std::vector<N
         hipLaunchKernelGGL(k_slots_scatter, dim3(grid), dim3(256), 0, lane.st, sp, (const uint4*)lane.d_out.p, per, nb);
         DEV_TRY(hipGetLastError());
         DEV_TRY(hipStreamSynchronize(lane.st));
-    } catch (const kzgamd::DevErr& e) {
-        if (lane.st) (void)hipStreamSynchronize(lane.st);  // nothing may still read or write the callers' slots
-        rc = kzgamd::dev_code(e.e);
-    }
+    });
+    if (rc != 0 && lane.st) (void)hipStreamSynchronize(lane.st);  // nothing may still read or write the callers' slots
     for (auto* r : batch) r->rc = rc;
 }
 
@@ -642,7 +636,7 @@ extern "C" int ntt_fr(void* vctx, blst_fr* out, const blst_fr* in, size_t n, int
         if (run_host_combined(ctx, out, in, n, inverse != 0 ? 1 : 0, &rc)) return rc;
     }
     std::lock_guard<std::mutex> lk(ctx->mu);
-    try {
+    return kzgamd::status_of([&] {
         kzgamd::DeviceGuard on_device(ctx->device);
         DEV_TRY(on_device.err);
         ctx->ensure(n);
@@ -650,10 +644,7 @@ extern "C" int ntt_fr(void* vctx, blst_fr* out, const blst_fr* in, size_t n, int
         ntt_enqueue(ctx, ctx->d_b.p, ctx->d_a.p, n, 1, inverse != 0, ctx->stream);
         DEV_TRY(hipMemcpyAsync(out, ctx->d_b.p, n * sizeof(Fr), hipMemcpyDeviceToHost, ctx->stream));
         DEV_TRY(hipStreamSynchronize(ctx->stream));
-    } catch (const kzgamd::DevErr& e) {
-        return kzgamd::dev_code(e.e);
-    }
-    return 0;
+    });
 }
 
 // odds = FFT_n( w^j * IFFT_n(evens)_j ), w the 2n-th root: the values of the degree < n interpolant of
@@ -697,7 +688,7 @@ extern "C" int das_fft_extension(void* vctx, blst_fr* odds, const blst_fr* evens
         if (run_host_combined(ctx, odds, evens, n, 2, &rc)) return rc;
     }
     std::lock_guard<std::mutex> lk(ctx->mu);
-    try {
+    return kzgamd::status_of([&] {
         kzgamd::DeviceGuard on_device(ctx->device);
         DEV_TRY(on_device.err);
         ctx->ensure(2 * n);
@@ -705,10 +696,7 @@ extern "C" int das_fft_extension(void* vctx, blst_fr* odds, const blst_fr* evens
         das_enqueue(ctx, ctx->d_a.p + n, ctx->d_a.p, ctx->d_b.p, n, 1, ctx->stream);
         DEV_TRY(hipMemcpyAsync(odds, ctx->d_a.p + n, n * sizeof(Fr), hipMemcpyDeviceToHost, ctx->stream));
         DEV_TRY(hipStreamSynchronize(ctx->stream));
-    } catch (const kzgamd::DevErr& e) {
-        return kzgamd::dev_code(e.e);
-    }
-    return 0;
+    });
 }
 
 // Device-resident form: nbatch contiguous half-size lists in d_evens -> d_odds; d_scratch holds n * nbatch elements
@@ -721,14 +709,11 @@ extern "C" int kzgamd_das_fft_extension_device(void* vctx, void* d_odds, const v
     if (n & (n - 1)) return 2;
     if (n * 2 > ctx->W) return 3;
     if (d_odds == d_evens || d_scratch == d_evens || d_scratch == d_odds) return -3;
-    try {
+    return kzgamd::status_of([&] {
         kzgamd::DeviceGuard on_device(ctx->device);
         DEV_TRY(on_device.err);
         das_enqueue(ctx, (Fr*)d_odds, (const Fr*)d_evens, (Fr*)d_scratch, n, nbatch, (hipStream_t)stream);
-    } catch (const kzgamd::DevErr& e) {
-        return kzgamd::dev_code(e.e);
-    }
-    return 0;
+    });
 }
 
 // The tile plan of (kind, T) as the kernel receives it — no GPU needed: rounds[r] = {pos, M, barrier_after, element bit},

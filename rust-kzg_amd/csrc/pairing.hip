@@ -13,6 +13,7 @@
 
 #include "device_guard.h"
 #include "fp12w.hip.h"
+#include "host_call.h"
 #include "host_pairing.h"
 #include "pairing_internal.h"
 
@@ -287,14 +288,14 @@ extern "C" int kzgamd_pairings_verify_batch(bool* ok, const blst_p1* a1, const b
     if (!ok || !a1 || !a2 || !b1 || !b2) return -1;
     int device = 0;
     hipError_t e = hipGetDevice(&device);
-    if (e != hipSuccess) return -(int)e - 100;
+    if (e != hipSuccess) return kzgamd::dev_code(e);
     try {
         DeviceTable ta, tb;
-        if ((e = kzgamd::pairing_gpu::device_table(&ta, a2)) != hipSuccess) return -(int)e - 100;
-        if ((e = kzgamd::pairing_gpu::device_table(&tb, b2)) != hipSuccess) return -(int)e - 100;
+        if ((e = kzgamd::pairing_gpu::device_table(&ta, a2)) != hipSuccess) return kzgamd::dev_code(e);
+        if ((e = kzgamd::pairing_gpu::device_table(&tb, b2)) != hipSuccess) return kzgamd::dev_code(e);
         std::vector<uint8_t> verdicts(count < SLICE ? count : SLICE);  // before the workspace: nothing below throws
         Workspace w;
-        if ((e = take_workspace(&w, device)) != hipSuccess) return -(int)e - 100;
+        if ((e = take_workspace(&w, device)) != hipSuccess) return kzgamd::dev_code(e);
         for (size_t at = 0; at < count && e == hipSuccess; at += SLICE) {
             const size_t n = count - at < SLICE ? count - at : SLICE;
             e = hipMemcpyAsync(w.pts, a1 + at, n * sizeof(blst_p1), hipMemcpyHostToDevice, w.st);
@@ -307,7 +308,7 @@ extern "C" int kzgamd_pairings_verify_batch(bool* ok, const blst_p1* a1, const b
                 for (size_t i = 0; i < n; ++i) ok[at + i] = verdicts[i] != 0;
         }
         give_workspace(w, device);
-        return e == hipSuccess ? 0 : -(int)e - 100;
+        return e == hipSuccess ? 0 : kzgamd::dev_code(e);
     } catch (...) {
         return -2;
     }

@@ -231,18 +231,16 @@ void g1_msm_rows(blst_p1* out, const blst_p1* jac, size_t n, const Fr* scalars, 
     dev_rc(kzgamd_g1_to_affine_batch(aff.data(), jac, n, dev_cfg));
     kzgamd::Options opt;
     opt.device = device;
-    kzgamd::foreign([&] {
-        // the membership test where it costs less than the split saves, the unsplit engine beyond (as mult_pippenger)
-        kzgamd::MsmContext* ctx = kzgamd::msm_create(aff.data(), n, false, false, false,
-                                                     n <= ((size_t)1 << 15) ? kzgamd::G1_CHECK : kzgamd::G1_NO_SPLIT, &opt);
-        try {
-            kzgamd::msm_run_host(ctx, out, scalars, n, rows);
-        } catch (...) {
-            kzgamd::msm_destroy(ctx);
-            throw;
-        }
+    // the membership test where it costs less than the split saves, the unsplit engine beyond (as mult_pippenger)
+    kzgamd::MsmContext* ctx = kzgamd::msm_create(aff.data(), n, false, false, false,
+                                                 n <= ((size_t)1 << 15) ? kzgamd::G1_CHECK : kzgamd::G1_NO_SPLIT, &opt);
+    try {
+        kzgamd::msm_run_host(ctx, out, scalars, n, rows);
+    } catch (...) {
         kzgamd::msm_destroy(ctx);
-    });
+        throw;
+    }
+    kzgamd::msm_destroy(ctx);
 }
 
 }  // namespace

@@ -778,12 +778,13 @@ int main() {
 
 def test_host_call_frame_maps_errors_and_releases_the_handle(tmp_path):
     """csrc/host_call.h without a device (the HIP calls it makes are this program's own, counted): the status of a
-    body that returns one, of a void body, of DevErr{hipErrorOutOfMemory} (-102), of std::bad_alloc (-2) and of an int
-    thrown through kzgamd::foreign (-1099); run_call runs the body on the handle's device with its lock held,
+    body that returns one, of a void body, of DevErr{hipErrorOutOfMemory} (-102), of the MSM engine's
+    DevErr{hipErrorInvalidValue, text} (-101), of std::bad_alloc and of an int (-2); DEV_TRY throws the code with the
+    expression's text; run_call runs the body on the handle's device with its lock held,
     synchronises once on either way out and leaves the lock free after every throwing body; DevBuf grows and drops,
     ScopedBuf frees; create_handle gives dev_code or -4 and deletes what did not make it.  DevArray, the one owner of
     device memory: typed growth in elements, freed at scope exit and once only after drop(), moves, a failed hipMalloc
-    (try_ensure returns the code and leaves the array empty), a group released as a whole before any of it is allocated
+    (ensure throws the code and leaves the array empty), a group released as a whole before any of it is allocated
     (drop_all), and a creation whose init throws after ensure — nothing leaks, with no destructor naming a buffer.  Built
     with the address and undefined-behaviour sanitizers as a plain executable."""
     import shutil
@@ -794,6 +795,7 @@ def test_host_call_frame_maps_errors_and_releases_the_handle(tmp_path):
     src.write_text(r'''
 #include <cstdint>
 #include <cstdio>
+#include <cstring>
 #include <new>
 #include <string>
 #include <utility>
@@ -841,9 +843,15 @@ int main() {
     EXPECT(status_of([] {}) == 0);
     EXPECT(status_of([] { DEV_TRY(hipErrorOutOfMemory); }) == -102);
     EXPECT(status_of([]() -> int { throw std::bad_alloc(); }) == -2);
-    EXPECT(status_of([] { foreign([] { throw 5; }); }) == -1099);
-    EXPECT(status_of([] { foreign([] { throw DevErr{hipErrorOutOfMemory}; }); }) == -102);  // a DevErr passes through it
-    EXPECT(status_of([] { foreign([] {}); }) == 0);
+    EXPECT(status_of([] { throw DevErr{hipErrorInvalidValue, "npoints exceeds the prepared size"}; }) == -101);  // the engine's own
+    EXPECT(status_of([] { throw 5; }) == -2);
+    try {
+        DEV_TRY(hipErrorOutOfMemory);
+        EXPECT(false);
+    } catch (const DevErr& e) {
+        EXPECT(e.e == hipErrorOutOfMemory && !strcmp(e.what, "hipErrorOutOfMemory"));
+    }
+    EXPECT(!strcmp(DevErr{hipErrorOutOfMemory}.what, ""));  // the code alone still makes one
     // the frame of a call: one synchronisation when the body returns, one more before unwinding when it throws
     Handle h;
     int seen_device = -1;
@@ -857,7 +865,9 @@ int main() {
     syncs = 0;
     EXPECT(run_call(&h, []() -> int { throw std::bad_alloc(); }) == -2 && syncs == 1 && unlocked(h));
     syncs = 0;
-    EXPECT(run_call(&h, [] { foreign([] { throw 5; }); }) == -1099 && syncs == 1 && unlocked(h));
+    EXPECT(run_call(&h, [] { throw DevErr{hipErrorInvalidValue, "npoints exceeds the prepared size"}; }) == -101 && syncs == 1 && unlocked(h));
+    syncs = 0;
+    EXPECT(run_call(&h, [] { throw 5; }) == -2 && syncs == 1 && unlocked(h));
     EXPECT(run_call(&h, [] { return 0; }) == 0 && device == 0);
     // buffers
     {
@@ -917,10 +927,11 @@ int main() {
     {
         DevArray<uint32_t> a;
         fail_at = 1;
-        EXPECT(a.try_ensure(10) == hipErrorOutOfMemory && a.p == nullptr && a.cap == 0);
+        EXPECT(status_of([&] { a.ensure(10); }) == -102 && a.p == nullptr && a.cap == 0);
         a.ensure(10);
+        order.clear();
         fail_at = 1;
-        EXPECT(a.try_ensure(20) == hipErrorOutOfMemory && a.p == nullptr && a.cap == 0);  // the old block went first
+        EXPECT(status_of([&] { a.ensure(20); }) == -102 && a.p == nullptr && a.cap == 0 && order == "FX");  // the old block went first
         fail_at = 1;
         EXPECT(status_of([&] { a.ensure(20); }) == -102 && a.p == nullptr && a.cap == 0);
     }
@@ -929,18 +940,19 @@ int main() {
     {
         DevArray<uint32_t> a;
         DevArray<unsigned char> b;
-        auto grow = [&](size_t n) -> hipError_t {
-            drop_all(a, b);
-            hipError_t e = a.try_ensure(n);
-            if (e == hipSuccess) e = b.try_ensure(n);
-            return e;
+        auto grow = [&](size_t n) {
+            return status_of([&] {
+                drop_all(a, b);
+                a.ensure(n);
+                b.ensure(n);
+            });
         };
-        EXPECT(grow(4) == hipSuccess);
+        EXPECT(grow(4) == 0);
         order.clear();
-        EXPECT(grow(8) == hipSuccess && order == "FFMM");
+        EXPECT(grow(8) == 0 && order == "FFMM");
         order.clear();
         fail_at = 2;
-        EXPECT(grow(16) == hipErrorOutOfMemory && order == "FFMX");
+        EXPECT(grow(16) == -102 && order == "FFMX");
         EXPECT(a.p && a.cap == 16 && !b.p && b.cap == 0);  // the first block is still owned ...
     }
     EXPECT(mallocs == 14 && frees == 14);  // ... and freed once at scope exit

@@ -115,6 +115,22 @@ def test_every_size_up_to_128_into_a_garbage_filled_output(oracle, kzg):
     whole.close()
 
 
+def test_more_points_than_prepared_reports_the_engines_code_and_text(oracle, kzg):
+    """mult_pippenger_prepared with npoints = 65 on a handle prepared for 64 points: the engine rejects the call before
+    any device call, and B1 reports the error as the engine threw it — code hipErrorInvalidValue (1), and as the message
+    the engine's text, ": ", hipGetErrorString of the code."""
+    L = oracle.lib()
+    rnd = random.Random(65)
+    pts = gen_points(L, 64, rnd)
+    sc = O.fr_array([rnd.randrange(O.R) for _ in range(65)])
+    h = kzg.prepare_multi_scalar_mult(pts, 64, kzg.make_config(table_budget_gb=0.25))
+    out = kzg.BlstP1()
+    err = kzg.lib().mult_pippenger_prepared(h.handle, C.byref(out), 65, sc)
+    h.close()
+    assert err.code == 1
+    assert err.message == b"npoints exceeds the prepared size: invalid argument"
+
+
 def test_edge_scalars_and_points(oracle, kzg):
     L = oracle.lib()
     rnd = random.Random(12)
