@@ -18,6 +18,9 @@
 //   sub<K>    a + K*p - b, b normalized with value < (K-1)*p; output normalized
 // Values are only ever reduced to [0,p) at the I/O boundary (to_blst) and inside
 // the rare exact zero test.
+// These rules are pinned at their edges on the host (tests/test_host_cpu.py,
+// test_fp28_primitives_at_their_documented_bounds) and on the device, primitive by
+// primitive (tests/test_g2_arith_gpu.py, cases in tests/g2_lane_cases.py).
 #pragma once
 #include "ff.hip.h"
 

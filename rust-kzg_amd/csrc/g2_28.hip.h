@@ -2,7 +2,8 @@
 // E'(Fp2): y^2 = x^3 + 4(1 + u), in the style of g1_28.hip.h.  host_pairing.h is the specification: f2_mul / f2_sqr
 // with the same Karatsuba split, g2_dbl (dbl-2009-l), g2_add (add-2007-bl) with Z2 = 1 and in full, g2_to_affine; every
 // routine returns the value the host routine returns (tests/test_g2_lane_cpu.py and tests/test_g2_add_cpu.py compare
-// them as canonical residues).
+// them as canonical residues).  The device build is held to the table below routine by routine, against Python integers,
+// by tests/test_g2_arith_gpu.py (tests/device_checks/g2_check.hip, cases in tests/g2_lane_cases.py).
 //
 // Bounds.  An Fp2 value is two fp28 components, each NORMALIZED (limbs 0..12 < 2^28) with a value below a stated
 // multiple of p; "a < K" below means both components of a are normalized with value < K*p.  The rules of fp28.hip.h

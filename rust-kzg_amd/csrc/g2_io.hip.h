@@ -1,7 +1,8 @@
 // G2 wire format and membership on the device, one value per lane: ZCash-compressed 96-byte points <-> g2::AffPt /
 // g2::Jac, in the style of g1_io.hip.h.  host_pairing.h is the specification (f2_sqrt up to the sign of the root,
 // f2_lex_largest, g2_uncompress, g2_compress, g2_in_g2); tests/test_point_codec_cpu.py compiles this header for the
-// host and compares every routine with it and with tests/codec_model.py.
+// host and compares every routine with it and with tests/codec_model.py; tests/test_g2_arith_gpu.py runs every routine
+// of the table below on the device, one value per lane, against tests/codec_model.py (cases in tests/g2_lane_cases.py).
 //
 // Bounds, in the language of g2_28.hip.h ("a < K": both components normalized with value < K*p):
 //

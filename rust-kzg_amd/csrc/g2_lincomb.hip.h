@@ -1,7 +1,8 @@
 // The per-lane part of a G2 linear combination (setupcheck.hip), host- and device-compilable so that
 // tests/test_g2_add_cpu.py runs the very walk the kernel runs against host_pairing.h: one term k * P by a left-to-right
-// double-and-add over the affine form of P, and the pairwise tree that sums 64 terms.  Only routines of g2_28.hip.h,
-// inside the bounds its table states:
+// double-and-add over the affine form of P, and the pairwise tree that sums 64 terms.  tests/test_g2_arith_gpu.py runs
+// term (one point and scalar per lane) and tree_step (the 64 slots in LDS) on the device against Python integers.  Only
+// routines of g2_28.hip.h, inside the bounds its table states:
 //   from_blst_jacobian  X, Y, Z < 2 (products)             -> to_affine takes X, Y, Z < 15; x, y canonical
 //   the walk            acc is the affine point (canonical, Z = one), or what dbl (X, Y < 2, Z < 10) or madd
 //                       (X, Y < 3, Z < 10) left: dbl takes X, Y < 15, Z < 21, madd X1, Y1 < 3, Z1 < 10
