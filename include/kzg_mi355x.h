@@ -657,6 +657,54 @@ int kzgamd_verify_trusted_setup(void *ntt, unsigned *failed, const blst_p1 *g1_m
                                 const KzgAmdConfig *cfg);
 int kzgamd_verify_trusted_setup_file(void *ntt, unsigned *failed, FILE *in, const uint8_t seed[32], const KzgAmdConfig *cfg);
 
+/* A prepared bucket MSM in G2 ON THE GPU: many linear combinations over ONE fixed set of points (a setup [s^j]G2, a
+ * ceremony transcript), singly or in batches.  A handle, thread-safe like every handle: calls on one handle take turns,
+ * calls on different handles run beside each other.  Host buffers in and out.
+ *
+ * kzgamd_g2_msm_new: a handle over points[0 .. npoints) on the calling thread's current device (cfg->device, when cfg is
+ * given and names one).  Points are Jacobian with canonical coordinates and any Z; Z == 0 is the identity, whatever X
+ * and Y hold.  The points are the caller's responsibility, like every blst_p2 this library accepts: for points outside
+ * the subgroup every result is still the sum under the curve's group law.  npoints == 0 is allowed (points may then be
+ * NULL): every sum of such a handle is the identity.
+ * What the handle keeps: the table 2^(8k) * points[i], k < 32, as affine points of 240 bytes, 7680 bytes per point
+ * (kzgamd_g2_msm_info: table_bytes): 252 MB for 2^15 points, 8 GB for 2^20.  Creation doubles every point 248 times
+ * and inverts 32 times per point on the GPU, 65536 points per launch, and needs 0.7 GB of workspace beside the table
+ * while it runs.  Measured on an MI355X with the upload (2026-10-21, profiles/g2_msm_time.jsonl, median of 5): 6.3 ms at
+ * 65 points, 6.5 ms at 2^12, 8.1 ms at 2^15, 140 ms at 2^20.
+ * *err (err may be NULL):  0 ok;  2 the table would exceed cfg->table_budget_bytes (0: no cap but the memory that is
+ * free);  -1 points is NULL with npoints > 0;  -2 a malformed cfg or an unknown tuning key;  other negatives: device
+ * errors.  NULL is returned on any error, and nothing stays allocated.
+ * cfg may be NULL.  Its tuning string takes TWO keys, of this call alone, read at creation only, not listed by
+ * kzgamd_tuning_keys and not carried by the environment:
+ *     g2msm_segment=<entries one lane accumulates: a power of two, at least 2>
+ *     g2msm_pass_entries=<cap on the (point, window) entries sorted and accumulated in one pass: a multiple of 32, at
+ *                         least 32; a call above the cap runs in several passes, and the pass results are added>
+ * Any other key fails the creation with -2.
+ *
+ * kzgamd_g2_msm: out[b] = sum_{i < n} scalars[b * n + i] * points[i] for b < nbatch, n <= npoints: the first n points
+ * are used, as kzgamd_kzg_commit treats len.  Scalars are Montgomery blst_fr.  Every output is Jacobian with Z = one and
+ * canonical coordinates, or all-zero for the identity: the result of a call is one fixed byte string, whatever order
+ * the device added the terms in.  n == 0 gives identities (out is still required when nbatch > 0); nbatch == 0
+ * succeeds, nothing is written and no pointer is looked at.
+ * Return codes:  0 ok;  1 n > npoints;  -1 a needed pointer is NULL;  -(100 + hipError_t) a device error.
+ * Every scalar is recoded into 32 signed base-256 digits; every non-zero digit is one table point added into one of 128
+ * buckets of its batch item (at most 32 mixed additions per point and no doubling, against 256 doublings and about 128
+ * additions of kzgamd_g2_lincomb), and the buckets are summed with their indices as weights.
+ * This call is the faster form from the smallest count measured, 65 points, and the recommended one wherever a point
+ * set is used more than once.  Medians of 5, kzgamd_g2_msm / kzgamd_g2_lincomb on the same inputs in the same run
+ * (2026-10-21, profiles/g2_msm_time.jsonl; the five runs of either call lie within 1.8 ms of each other at every count):
+ * 1.7 / 17.8 ms at 65 points, 2.6 / 17.8 ms at 2^12, 3.6 / 18.5 ms at 2^15, 28.7 / 287 ms at 2^20; 16 vectors over 2^15
+ * points 15.0 ms in one call against 297 ms in 16.  A handle used once pays its creation too: 8.0 / 17.8 ms at 65 points,
+ * 11.7 / 18.5 ms at 2^15, 169 / 287 ms at 2^20, still ahead.  Counts below 65 were not measured.
+ *
+ * kzgamd_g2_msm_info: the shape of a handle (any pointer may be NULL): its points, the window width in bits, the two
+ * tuning values and the bytes of its table.  0, or -1 for a NULL handle.
+ * kzgamd_g2_msm_free gives back every byte of HBM; NULL is a no-op. */
+void *kzgamd_g2_msm_new(const blst_p2 *points, size_t npoints, const KzgAmdConfig *cfg, int *err);
+void kzgamd_g2_msm_free(void *h);
+int kzgamd_g2_msm(void *h, blst_p2 *out, const blst_fr *scalars, size_t n, size_t nbatch);
+int kzgamd_g2_msm_info(void *h, size_t *npoints, int *window_bits, size_t *segment, size_t *pass_entries, size_t *table_bytes);
+
 typedef struct { uint8_t bytes[2048]; } Cell;
 C_KZG_RET compute_cells_and_kzg_proofs(Cell *cells, KZGProof *proofs, const Blob *blob, const CKZGSettings *s);
 C_KZG_RET kzgamd_compute_cells_and_kzg_proofs_batch(Cell *cells, KZGProof *proofs, const Blob *blobs, size_t n,

@@ -92,6 +92,7 @@ EXPORTS = [
     "kzgamd_g2_uncompress_batch", "kzgamd_p2_in_g2", "kzgamd_codec_info",
     "kzgamd_write_trusted_setup_file", "kzgamd_read_trusted_setup_file",
     "kzgamd_g2_lincomb", "kzgamd_g2_lincomb_info", "kzgamd_verify_trusted_setup", "kzgamd_verify_trusted_setup_file",
+    "kzgamd_g2_msm_new", "kzgamd_g2_msm_free", "kzgamd_g2_msm", "kzgamd_g2_msm_info",
     "kzgamd_load_trusted_setup_file_multi", "kzgamd_free_trusted_setup_multi", "kzgamd_blob_to_kzg_commitment_batch_multi",
     "kzgamd_compute_blob_kzg_proof_batch_multi", "kzgamd_compute_cells_and_kzg_proofs_batch_multi",
     "kzgamd_verify_blob_kzg_proof_batch_multi", "kzgamd_mult_pippenger_prepared_multi", "kzgamd_shard_range",
@@ -398,6 +399,14 @@ def lib():
     L.kzgamd_g2_lincomb.argtypes = [vp, vp, vp, C.c_size_t, vp]
     L.kzgamd_g2_lincomb_info.restype = C.c_int
     L.kzgamd_g2_lincomb_info.argtypes = [vp]
+    L.kzgamd_g2_msm_new.restype = vp
+    L.kzgamd_g2_msm_new.argtypes = [vp, C.c_size_t, vp, C.POINTER(C.c_int)]
+    L.kzgamd_g2_msm_free.restype = None
+    L.kzgamd_g2_msm_free.argtypes = [vp]
+    L.kzgamd_g2_msm.restype = C.c_int
+    L.kzgamd_g2_msm.argtypes = [vp, vp, vp, C.c_size_t, C.c_size_t]
+    L.kzgamd_g2_msm_info.restype = C.c_int
+    L.kzgamd_g2_msm_info.argtypes = [vp, vp, vp, vp, vp, vp]
     L.kzgamd_verify_trusted_setup.restype = C.c_int
     L.kzgamd_verify_trusted_setup.argtypes = [vp, vp, vp, vp, vp, C.c_size_t, C.c_size_t, vp, vp]
     L.kzgamd_verify_trusted_setup_file.restype = C.c_int
@@ -1491,6 +1500,45 @@ def g2_lincomb_info() -> int:
     out = C.c_size_t(0)
     lib().kzgamd_g2_lincomb_info(C.byref(out))
     return out.value
+
+
+class G2Msm:
+    """A prepared bucket MSM in G2 (kzgamd_g2_msm_new): the table 2^(8k) * points[i] of BlstP2[npoints] (any Z) on the
+    GPU.  config: the device, table_budget_bytes, and the tuning keys g2msm_segment / g2msm_pass_entries."""
+
+    def __init__(self, points, npoints, config=None):
+        err = C.c_int(0)
+        self.npoints = npoints
+        self.handle = lib().kzgamd_g2_msm_new(_addr(points) if npoints else None, npoints, _cfgp(config), C.byref(err))
+        if not self.handle:
+            self.handle = None
+            raise KzgAmdError("kzgamd_g2_msm_new: %d" % err.value)
+
+    def g2_msm(self, scalars, n, nbatch=1):
+        """BlstP2[nbatch]: out[b] = sum_{i < n} scalars[b * n + i] * points[i] (Montgomery blst_fr[nbatch * n]); every
+        output has Z = one, or is all-zero for the identity; nbatch == 0 gives an empty array"""
+        out = (BlstP2 * nbatch)()
+        rc = lib().kzgamd_g2_msm(self.handle, out if nbatch else None, _addr(scalars) if n and nbatch else None, n, nbatch)
+        if rc != 0:
+            raise KzgAmdError("kzgamd_g2_msm: %d" % rc)
+        return out
+
+    def info(self):
+        """the shape of the handle: npoints, window_bits, segment, pass_entries, table_bytes"""
+        np_, seg, pe, tb, wb = C.c_size_t(0), C.c_size_t(0), C.c_size_t(0), C.c_size_t(0), C.c_int(0)
+        lib().kzgamd_g2_msm_info(self.handle, C.byref(np_), C.byref(wb), C.byref(seg), C.byref(pe), C.byref(tb))
+        return {"npoints": np_.value, "window_bits": wb.value, "segment": seg.value, "pass_entries": pe.value, "table_bytes": tb.value}
+
+    def close(self):
+        if self.handle:
+            lib().kzgamd_g2_msm_free(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def verify_trusted_setup(g1_monomial, g1_lagrange, g2_monomial, num_g1, num_g2, fft_settings=None, seed=None, config=None):

@@ -6,8 +6,8 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(CSRC, "libkzg_mi355x.so")
-SOURCES = ["msm.hip", "ckzg.hip", "ckzg_verify.hip", "ckzg_7594.hip", "ckzg_vcells.hip", "ntt.hip", "fftg1.hip", "fk20.hip", "kzg.hip", "poly.hip", "zeropoly.hip", "multi.hip", "pairing.hip", "groupmul.hip", "codec.hip", "setupcheck.hip"]
-HEADERS = ["ff.hip.h", "host_call.h", "combine.h", "slot_gather.hip.h","fp28.hip.h", "g1_28.hip.h", "g1_io.hip.h", "msm_internal.h", "ckzg_internal.h", "sha256.h", "host_g1.h", "host_pairing.h", "host_fp64.h", "ff28.hip.h", "fr29.hip.h", "frscan.hip.h", "ntt_internal.h", "poly_internal.h", "device_guard.h", "fpw.hip.h", "g1w.hip.h", "glv.hip.h", "ntt_plan.h", "ckzg_shared.h", "config.h", "fp12w.hip.h", "pairing_internal.h", "g2_28.hip.h", "g2_io.hip.h", "g2_lincomb.hip.h", "setupcheck_internal.h",
+SOURCES = ["msm.hip", "ckzg.hip", "ckzg_verify.hip", "ckzg_7594.hip", "ckzg_vcells.hip", "ntt.hip", "fftg1.hip", "fk20.hip", "kzg.hip", "poly.hip", "zeropoly.hip", "multi.hip", "pairing.hip", "groupmul.hip", "codec.hip", "setupcheck.hip", "g2msm.hip"]
+HEADERS = ["ff.hip.h", "host_call.h", "combine.h", "slot_gather.hip.h","fp28.hip.h", "g1_28.hip.h", "g1_io.hip.h", "msm_internal.h", "ckzg_internal.h", "sha256.h", "host_g1.h", "host_pairing.h", "host_fp64.h", "ff28.hip.h", "fr29.hip.h", "frscan.hip.h", "ntt_internal.h", "poly_internal.h", "device_guard.h", "fpw.hip.h", "g1w.hip.h", "glv.hip.h", "ntt_plan.h", "ckzg_shared.h", "config.h", "fp12w.hip.h", "pairing_internal.h", "g2_28.hip.h", "g2_io.hip.h", "g2_lincomb.hip.h", "g2_bucket.hip.h", "setupcheck_internal.h",
            os.path.join("..", "..", "include", "kzg_mi355x.h")]
 
 

@@ -37,6 +37,7 @@
 #include "g1_28.hip.h"
 #include "g1_io.hip.h"
 #include "g2_28.hip.h"
+#include "g2_bucket.hip.h"
 #include "host_call.h"
 #include "host_fp64.h"
 #include "host_g1.h"
@@ -79,13 +80,9 @@ __global__ void __launch_bounds__(256) k_fr_powers(Fr* __restrict__ out, Fr s, F
     }
 }
 
-// digit k of the signed base-256 recoding: returns |d_k| in [0, 128], sets neg to all-ones when d_k < 0; carry in/out
-__device__ __forceinline__ u32 signed_digit(const Fr& k, int w, u32& carry, u32& neg) {
-    const u32 v = ((k.v[w >> 2] >> (8 * (w & 3))) & 0xffu) + carry;
-    carry = v > (u32)HALF ? 1u : 0u;
-    neg = 0u - carry;
-    return carry ? 256u - v : v;
-}
+// digit k of the signed base-256 recoding: g2_bucket.hip.h has it, for this file and for g2msm.hip
+using g2b::signed_digit;
+static_assert(WBITS == g2b::WBITS && NWIN == g2b::NWIN && HALF == g2b::HALF, "one recoding");
 
 // ---------------------------------------------------------------- G1
 // lane k < 32: tmp[k][j - 1] = j * 2^(8k) * B, j = 1 .. 128, as XYZZ (entry 0 normalised: ZZ = ZZZ = 1).

@@ -116,6 +116,12 @@ extern "C" {
                                      cfg: *const KzgAmdConfig) -> c_int;
     fn kzgamd_group_mul_info(slice_points: *mut usize, g1_window_bits: *mut c_int, g2_window_bits: *mut c_int) -> c_int;
 
+    pub fn kzgamd_g2_msm_new(points: *const blst_p2, npoints: usize, cfg: *const KzgAmdConfig, err: *mut c_int) -> *mut c_void;
+    pub fn kzgamd_g2_msm_free(h: *mut c_void);
+    pub fn kzgamd_g2_msm(h: *mut c_void, out: *mut blst_p2, scalars: *const blst_fr, n: usize, nbatch: usize) -> c_int;
+    pub fn kzgamd_g2_msm_info(h: *mut c_void, npoints: *mut usize, window_bits: *mut c_int, segment: *mut usize,
+                              pass_entries: *mut usize, table_bytes: *mut usize) -> c_int;
+
     fn kzgamd_g1_compress_batch(out48: *mut u8, points: *const blst_p1, n: usize, cfg: *const KzgAmdConfig) -> c_int;
     fn kzgamd_g1_to_affine_batch(out: *mut blst_p1_affine, points: *const blst_p1, n: usize, cfg: *const KzgAmdConfig) -> c_int;
     fn kzgamd_g1_uncompress_batch(out: *mut blst_p1, status: *mut u8, in48: *const u8, n: usize, check_subgroup: c_int,
